@@ -42,7 +42,7 @@ sys.path.insert(0, ROOT)
 
 from stm32_speech_recognition_amd import Engine, synth  # noqa: E402
 from stm32_speech_recognition_amd import dist_util as du  # noqa: E402
-from stm32_speech_recognition_amd.engine import results_from_torch, vad_from_torch  # noqa: E402
+from stm32_speech_recognition_amd.engine import VAD_DTYPE, results_from_torch, vad_from_torch  # noqa: E402
 
 T = 256            # frames per utterance (metric: "256-frame, 100 templates")
 K_DEFAULT = 100    # templates
@@ -95,7 +95,19 @@ def parse_args(argv=None):
                          "at K = 100) or the 16-byte result records [B] (1 MB per rank; SURVEY.md 8(e) names both)")
     ap.add_argument("--other-scale", type=int, default=1,
                     help="tests: divide the other_configs batches by this and run them whatever the headline shape is")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its LAST step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: per-utterance records in full, scores and MFCC rows on a "
+                         "fixed seeded sample of utterances; see dump_outputs()).  Inputs are seeded: the same arguments give "
+                         "the same inputs, so two builds can be compared file for file")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.scorer == "dp":
+        ap.error("--dump-outputs covers the recognition path; --scorer dp is a side measurement")
+    return args
 
 
 def free_port():
@@ -104,6 +116,65 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: everything written, in all
+DUMP_RECORD_ROWS = 131072     # per-utterance records (results, VAD) in full up to this many utterances, else a sample
+DUMP_SAMPLE_ROWS = 1024       # utterances whose score row and MFCC rows are written
+DUMP_SEED = 20261015          # the sample is a function of the row count alone
+
+
+def dump_rows(n, cap):
+    """row indices written for an n-row output: all of them when n <= cap, else a fixed seeded sample of cap rows, sorted"""
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False)).astype(np.int64)
+
+
+def snapshot_outputs(results, scores=None, mfcc=None, vad=None, gathered=None):
+    """host copy of the arrays a caller of the timed path receives (engine outputs; at N > 1 also the all-gathered exchange
+    buffer), as float32 / float64 numpy arrays (exact for the s16 / s32 / u32 values they hold) within DUMP_LIMIT_BYTES.
+    Every array is row-sampled by dump_rows(); the sampled row numbers are written too (*_rows)."""
+    def pick(t, rows):
+        return t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy()
+
+    B = results.shape[0]
+    d = {}
+    rows = dump_rows(B, DUMP_RECORD_ROWS)
+    d["record_rows"] = rows.astype(np.float64)
+    r = pick(results, rows).view(np.uint32)
+    for i, f in enumerate(("best_tpl", "min_dis", "frm_num", "status")):  # sr_result
+        d[f] = r[:, i].astype(np.float64)
+    if vad is not None:  # sr_vad_rec without its padding word
+        v = pick(vad, rows).view(np.uint8).reshape(-1, VAD_DTYPE.itemsize).copy().view(VAD_DTYPE).reshape(-1)
+        for f in ("mid_val", "n_thl", "z_thl", "s_thl", "seg", "frm_num", "status"):
+            d["vad_" + f] = v[f].astype(np.float64)
+    used = sum(a.nbytes for a in d.values())
+    per_utt = 8 * (scores.shape[1] if scores is not None else 0) + 4 * (mfcc[0].numel() if mfcc is not None else 0)
+    per_utt += 8 * (gathered.shape[1] if gathered is not None else 0) + 16
+    n = max(1, min(DUMP_SAMPLE_ROWS, (DUMP_LIMIT_BYTES - used) // max(per_utt, 1)))
+    rows = dump_rows(B, n)
+    if scores is not None or mfcc is not None:
+        d["sample_rows"] = rows.astype(np.float64)
+    if scores is not None:  # u32 DTW distance of every template slot
+        d["scores"] = pick(scores, rows).view(np.uint32).astype(np.float64)
+    if mfcc is not None:  # [n, max_frames, n_coef] s16, rows >= frm_num zero
+        d["mfcc"] = pick(mfcc, rows).astype(np.float32)
+    if gathered is not None:  # the exchange buffer every rank holds after the step: all ranks' rows, global order
+        grows = dump_rows(gathered.shape[0], n)
+        d["gathered_rows"] = grows.astype(np.float64)
+        d["gathered"] = pick(gathered, grows).view(np.uint32).astype(np.float64)
+    total = sum(a.nbytes for a in d.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget"
+    return d
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print(f"bench.py: wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values())} bytes) to {directory}", file=sys.stderr)
 
 
 def self_launch(args):
@@ -253,9 +324,10 @@ class ClockSampler:
 FORCE_DIST = False  # test hook SR_BENCH_FORCE_DIST=1: initialise the process group and run the exchange even at N = 1
 
 
-def measure(workload, B, Kt, steps, warmup, rank, world, local_rank, dist, gain=1.0, exchange="scores"):
+def measure(workload, B, Kt, steps, warmup, rank, world, local_rank, dist, gain=1.0, exchange="scores", dump=False):
     """K timed steps of one workload on this rank's GPU (barrier + synchronize on both sides, max over ranks), then an
-    untimed isolated pass (whole batch as one chunk on one stream) for the per-kernel durations.  Returns a dict."""
+    untimed isolated pass (whole batch as one chunk on one stream) for the per-kernel durations.  Returns a dict;
+    dump=True: its "dump" entry holds snapshot_outputs() of the last timed step."""
     rate, eng_cfg, Kt, n_words = workload_setup(workload, Kt)
     dev = torch.device("cuda", local_rank)
     S = synth.buf_len_for(T, rate)
@@ -309,6 +381,10 @@ def measure(workload, B, Kt, steps, warmup, rank, world, local_rank, dist, gain=
         dt = time.perf_counter() - t0
     dt_rank = dt
     dt = du.max_over_ranks(dt, dev, 2 if (use_dist and world == 1) else world)
+    # the last timed step's outputs, copied before the diagnostics below reuse its buffers
+    last = (n_step[0] - 1) % len(outs)
+    dumped = snapshot_outputs(outs[last]["results"], outs[last]["scores"], outs[last]["mfcc"], outs[last]["vad"],
+                              xchg.gathered[last] if xchg is not None else None) if dump else None
     stage = eng.stage_ms()  # hipEvent timings of the timed steps, each kernel on the stream it was launched on
     eng.set_profiling(False)
     exchange_kind, exchange = exchange, None
@@ -364,7 +440,7 @@ def measure(workload, B, Kt, steps, warmup, rank, world, local_rank, dist, gain=
         dist.all_gather_into_tensor(sample_pcm.view(torch.uint8), pcm[:ns].contiguous().view(torch.uint8))
     return dict(dt=dt, stage=stage, stage_iso=stage_iso, acc=acc, eng=eng, pcm=pcm, out=out, tm=tm, tfr=tfr, S=S, rate=rate,
                 eng_cfg=eng_cfg, K=Kt, n_words=n_words, sclk=clk.summary(), exchange=exchange, gain=gain, exchange_kind=xkey,
-                gathered=xchg.gathered[0] if xchg is not None else None, sample_pcm=sample_pcm)
+                gathered=xchg.gathered[0] if xchg is not None else None, sample_pcm=sample_pcm, dump=dumped)
 
 
 SURVEY_GAIN = 2.4        # synth.make_utterances gain that gives SURVEY.md 8(d)'s sinusoid amplitudes (200-600: 64-300 x 2.4 = 154-720)
@@ -722,8 +798,10 @@ def run_rank(args):
         out_stream.flush()
         return 0
     m = measure(args.workload, B, args.templates, args.steps, args.warmup, rank, world, local_rank, dist, gain=args.gain,
-                exchange=args.exchange)
+                exchange=args.exchange, dump=args.dump_outputs is not None and rank == 0)
     if rank == 0:
+        if m["dump"] is not None:
+            dump_outputs(args.dump_outputs, m["dump"])
         line = headline(args, m, world, backend)
         if FORCE_DIST:
             line["config"]["parallelism"] += " -- TEST HOOK: process group and score exchange forced at N = 1"
@@ -998,6 +1076,8 @@ def run_single_process(args):
         me.recognize_dev(pl, rl, al, streams=sl)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs is not None:  # the last timed step: every device's results (global order), device 0's gathered matrix
+        dump_outputs(args.dump_outputs, snapshot_outputs(torch.cat([r.cpu() for r in rl]), gathered=al[0]))
     stage = e0.stage_ms()
     e0.set_profiling(False)
     e0.set_pipeline(streams=1)

@@ -20,3 +20,13 @@ def have_reference():
 
 
 needs_reference = pytest.mark.skipif(not have_reference(), reason="/root/reference not present (GPU box)")
+
+
+def have_ref_objects():
+    """the reference's own objects, compiled by build() into oracle/_ref/ where the reference tree exists (they travel with
+    the working tree to where it does not)"""
+    return have_reference() or all(os.path.exists(os.path.join(ROOT, "oracle", "_ref", f))
+                                   for f in ("libsr_ref.so", "libsr_ref320.so"))
+
+
+needs_ref_objects = pytest.mark.skipif(not have_ref_objects(), reason="oracle/_ref/ not built: no reference tree at build time")

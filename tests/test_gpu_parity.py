@@ -1375,6 +1375,37 @@ def _multi_case(devices, golden):
     multi_case(devices, golden)
 
 
+# The N = 2 tests that take one MI355X per rank run on two devices where the node has them.  On a one-GPU node they run the
+# same N = 2 code path with both ranks on device 0 instead of skipping; RCCL refuses two ranks on one device, so there the
+# collective is gloo (torch.distributed ranks, bench.py test hooks SR_BENCH_BACKEND / SR_BENCH_DEVICE) or the in-process RCCL
+# double (sr_multi, tests/fake_rccl).
+TWO_DEVICES = torch.cuda.device_count() >= 2
+
+
+def _n2_hooks(launcher):
+    """extra environment of an N = 2 bench.py run: none on a two-GPU node, the one-device stand-ins otherwise"""
+    if TWO_DEVICES:
+        return {}
+    if launcher == "single":
+        import multi_case as mc
+        return dict(SR_BENCH_DEVICE="0", SR_RCCL_LIBRARY=mc.FAKE_RCCL)
+    return dict(SR_BENCH_BACKEND="gloo", SR_BENCH_DEVICE="0")
+
+
+def _multi_case_process(devices, Bs):
+    """tests/multi_case.py in a process of its own over tests/fake_rccl/librccl.so.1 (csrc/sr_multi.cpp binds its collective
+    library once per process) -> its report"""
+    import json
+    import subprocess
+    import multi_case as mc
+    assert os.path.exists(mc.FAKE_RCCL), "tests/fake_rccl/librccl.so.1 missing: run __graft_entry__.build()"
+    env = dict(os.environ, SR_RCCL_LIBRARY=mc.FAKE_RCCL)  # multi_case.py switches the duplicate-device hook on itself
+    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "multi_case.py"), ",".join(map(str, devices)),
+                        ",".join(map(str, Bs))], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    return json.loads([l for l in p.stdout.splitlines() if l.startswith("MULTI_CASE ")][-1][len("MULTI_CASE "):])
+
+
 @pytest.mark.parametrize("n", [2, 3])
 def test_multi_gpu_bookkeeping_with_in_process_collective_double(n):
     """The N > 1 index arithmetic of csrc/sr_multi.cpp (block offsets of the in-place all-gather, padded last shard,
@@ -1382,16 +1413,8 @@ def test_multi_gpu_bookkeeping_with_in_process_collective_double(n):
     device 0 (development hook "multi_allow_dup") over tests/fake_rccl/librccl.so.1 (SR_RCCL_LIBRARY), an in-process stand-in
     that performs the all-gather as stream-ordered device copies between the ranks' buffers.  Own process: the
     collective library is bound once per process, and the other tests of this module use the real RCCL."""
-    import json
-    import subprocess
-    import multi_case as mc
-    assert os.path.exists(mc.FAKE_RCCL), "tests/fake_rccl/librccl.so.1 missing: run __graft_entry__.build()"
-    env = dict(os.environ, SR_RCCL_LIBRARY=mc.FAKE_RCCL)  # multi_case.py switches the duplicate-device hook on itself
     Bs = [37, 24, n - 1, 1]                 # uneven shards; even shards; B < n (empty last shard); a single capture
-    p = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "multi_case.py"), ",".join(["0"] * n),
-                        ",".join(map(str, Bs))], env=env, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
-    rep = json.loads([l for l in p.stdout.splitlines() if l.startswith("MULTI_CASE ")][-1][len("MULTI_CASE "):])
+    rep = _multi_case_process([0] * n, Bs)
     assert [c["B"] for c in rep["cases"]] == Bs and all(c["n"] == n for c in rep["cases"])
     # the double really carried the exchange: every gather is n*(n-1) copies (the own block is in place)
     assert rep["fake_allgathers"] >= 2 * len(Bs) and rep["fake_copies"] == rep["fake_allgathers"] * n * (n - 1), rep
@@ -1401,9 +1424,14 @@ def test_multi_gpu_c_abi_single_device(golden):
     _multi_case([0], golden)
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two MI355X in one node")
 def test_multi_gpu_c_abi_two_devices(golden):
-    _multi_case([0, 1], golden)
+    """sr_multi_* on two devices over RCCL; on a one-GPU node both devices are device 0 over the in-process RCCL double"""
+    if TWO_DEVICES:
+        _multi_case([0, 1], golden)
+        return
+    rep = _multi_case_process([0, 0], [37])
+    assert [(c["n"], c["B"]) for c in rep["cases"]] == [(2, 37)]
+    assert rep["fake_allgathers"] >= 2 and rep["fake_copies"] == rep["fake_allgathers"] * 2, rep
 
 
 def _run_bench(extra, env_extra, timeout=900):
@@ -1421,6 +1449,36 @@ def _run_bench(extra, env_extra, timeout=900):
     lines = p.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), p.stdout[-2000:]       # exactly one line on stdout
     return json.loads(lines[0]), p.stderr
+
+
+def test_bench_dump_outputs_are_the_timed_path_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: the last timed step's arrays as float32 / float64 .npy files within 64 MB, identical for two
+    runs with different --steps (the inputs are seeded), and equal to what the JSON line reports (accuracy, steps)"""
+    runs = []
+    for steps in (1, 3):
+        d = tmp_path / f"steps{steps}"
+        j, _ = _run_bench(["--batch", "4096", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
+                           "--dump-outputs", str(d)], {})
+        assert j["steps"] == steps
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith(".npy") for f in files) and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        runs.append((j, arrays))
+    (j1, a1), (_, a3) = runs
+    assert a1.keys() == a3.keys() and {"best_tpl", "min_dis", "frm_num", "status", "scores", "mfcc", "vad_seg"} <= a1.keys()
+    for k in a1:
+        assert np.array_equal(a1[k], a3[k]), k
+    B = 4096
+    assert np.array_equal(a1["record_rows"], np.arange(B)) and (a1["frm_num"] == 256).all() and (a1["status"] == 0).all()
+    rows = a1["sample_rows"].astype(np.int64)
+    assert a1["scores"].shape == (len(rows), 100) and a1["mfcc"].shape == (len(rows), 320, 12)
+    assert np.array_equal(a1["scores"].min(1), a1["min_dis"][rows])           # the record's min_dis is the row minimum
+    assert not a1["mfcc"][:, 256:].any()                                         # rows >= frm_num zeroed
+    rng = np.random.default_rng(2026)   # bench.py's stream: the template lengths, then the spoken word of every utterance
+    rng.integers(192, 321, 100)
+    words = rng.integers(0, 20, B)
+    assert float((a1["best_tpl"].astype(np.int64) % 20 == words).mean()) == j1["top1_word_accuracy"] > 0.9
 
 
 def test_bench_plain_command_launches_its_own_ranks():
@@ -1451,7 +1509,7 @@ def _check_multi_rank_line(j, n, B, launcher, exchange="scores"):
     # what one rank receives per step: the whole score matrix (north_star) or, --exchange results, 16 bytes per utterance
     assert x["ranks_in_communicator"] == n and x["allgather_bytes_per_rank_out"] == n * B * (100 * 4 if exchange == "scores" else 16)
     assert ("result records" in j["config"]["parallelism"]) == (exchange == "results")
-    r = j["roofline"]  # an N = 8 line carries roofline, cpu_baseline, exchange and a parity flag
+    r = j["roofline"]  # an N > 1 line carries roofline, cpu_baseline, exchange and a parity flag
     assert 0 < r["frac"] < 1 and 0 < r["timed_step_frac"] < 1 and "valu_frac" in r and "valu_frac_vs_2cycle_peak" in r
     if launcher == "ranks":
         assert "exposed_allgather_ms" in x and "allgather_ms" in x
@@ -1464,27 +1522,33 @@ def _check_multi_rank_line(j, n, B, launcher, exchange="scores"):
         assert cb["port"]["gpu_results_identical_on_sample"] is True and cb["cores_1"]["value"] > 0
 
 
-def test_bench_eight_ranks_dry_run():
-    """The metric is quoted at 1/2/4/8 MI355X and no multi-GPU node is on this side: `python bench.py --gpus 8` exactly as
-    the driver types it, eight ranks started by the script itself, here all on device 0 and exchanging over gloo (test
-    hooks).  One JSON line with eight per-rank step times, the in-place shard check of measure() on every rank (a failed
+# ranks of the multi-rank dry runs below, all on device 0: with the test process itself that is 5 processes holding the one GPU,
+# within the bound a shared node puts on processes per GPU (6); the world-size-8 bookkeeping runs in tests/test_sharding_gloo.py
+DRY_RUN_RANKS = 4
+
+
+def test_bench_four_ranks_dry_run():
+    """The metric is quoted at 1/2/4/8 MI355X and no multi-GPU node is on this side: `python bench.py --gpus 4` exactly as
+    the driver types it, four ranks started by the script itself, here all on device 0 and exchanging over gloo (test
+    hooks).  One JSON line with four per-rank step times, the in-place shard check of measure() on every rank (a failed
     assert there is a non-zero exit code here), the host baseline, and a parity flag that covers a sample of EVERY rank's
     shard read back from the gathered matrix.  Then BASELINE configs[3]'s arithmetic (a fixed global batch split over
-    eight ranks, --scaling strong) at a reduced size."""
+    the ranks, --scaling strong) at a reduced size."""
+    n = DRY_RUN_RANKS
     hooks = dict(SR_BENCH_BACKEND="gloo", SR_BENCH_DEVICE="0")
-    j, _ = _run_bench(["--gpus", "8", "--batch", "2048", "--steps", "2", "--warmup", "1", "--cpu-sample", "256"], hooks, timeout=1500)
-    _check_multi_rank_line(j, 8, 2048, "ranks")
-    assert len(j["exchange"]["step_ms_per_rank"]) == 8 and j["scaling"] == "weak"
+    j, _ = _run_bench(["--gpus", str(n), "--batch", "2048", "--steps", "2", "--warmup", "1", "--cpu-sample", "256"], hooks, timeout=1500)
+    _check_multi_rank_line(j, n, 2048, "ranks")
+    assert len(j["exchange"]["step_ms_per_rank"]) == n and j["scaling"] == "weak"
     # the cheaper exchange the driver can A/B against the default (round 6): gather the 16-byte result records instead of the
     # score matrix; parity then reads argmin / distance of every rank's sample from the gathered records
-    j, _ = _run_bench(["--gpus", "8", "--batch", "2048", "--steps", "2", "--warmup", "1", "--cpu-sample", "256", "--exchange", "results"],
+    j, _ = _run_bench(["--gpus", str(n), "--batch", "2048", "--steps", "2", "--warmup", "1", "--cpu-sample", "256", "--exchange", "results"],
                       hooks, timeout=1500)
-    _check_multi_rank_line(j, 8, 2048, "ranks", exchange="results")
-    j, _ = _run_bench(["--gpus", "8", "--scaling", "strong", "--batch", "16384", "--steps", "2", "--warmup", "1", "--cpu-sample", "128"],
-                      hooks, timeout=1500)
-    _check_multi_rank_line(j, 8, 2048, "ranks")
-    assert j["scaling"] == "strong" and "global batch 16384" in j["config"]["workload"]
-    assert abs(j["value"] - 16384 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-6
+    _check_multi_rank_line(j, n, 2048, "ranks", exchange="results")
+    j, _ = _run_bench(["--gpus", str(n), "--scaling", "strong", "--batch", str(n * 2048), "--steps", "2", "--warmup", "1", "--cpu-sample",
+                       "128"], hooks, timeout=1500)
+    _check_multi_rank_line(j, n, 2048, "ranks")
+    assert j["scaling"] == "strong" and f"global batch {n * 2048}" in j["config"]["workload"]
+    assert abs(j["value"] - n * 2048 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-6
 
 
 def test_bench_eight_devices_single_process_dry_run():
@@ -1522,20 +1586,23 @@ def test_bench_plain_command_single_process_launcher():
     assert j["top1_word_accuracy"] == 1.0 and j["roofline"]["frac"] > 0
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two MI355X in one node")
 @pytest.mark.parametrize("launcher", ["ranks", "single"])
 def test_bench_plain_command_over_rccl(launcher):
     """the driver's own line at N = 2 (`python bench.py --gpus 2 ...`, nothing else): one rank per GPU over RCCL, and
-    the single-process launcher over the same RCCL"""
+    the single-process launcher over the same RCCL; on a one-GPU node the same command on device 0 (_n2_hooks)"""
     j, _ = _run_bench(["--gpus", "2", "--launcher", launcher, "--batch", "4096", "--steps", "2", "--warmup", "1",
-                       "--no-cpu-baseline"], {})
-    assert j["n_gpus"] == 2 and j["value"] > 0 and "RCCL" in j["config"]["parallelism"]
-    assert "TEST HOOK" not in j["config"]["parallelism"] and j["top1_word_accuracy"] == 1.0
+                       "--no-cpu-baseline"], _n2_hooks(launcher))
+    assert j["n_gpus"] == 2 and j["value"] > 0 and j["launcher"].startswith(launcher) and j["top1_word_accuracy"] == 1.0
+    assert abs(j["value"] - 2 * 4096 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-6
+    if TWO_DEVICES:
+        assert "RCCL" in j["config"]["parallelism"] and "TEST HOOK" not in j["config"]["parallelism"]
+    else:
+        assert "TEST HOOK" in j["config"]["parallelism"]
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two MI355X in one node")
 def test_bench_two_ranks_over_rccl():
-    """bench.py under torch.distributed.run at N = 2 (WORLD_SIZE set by the launcher): one rank per GPU, backend nccl"""
+    """bench.py under torch.distributed.run at N = 2 (WORLD_SIZE set by the launcher): one rank per GPU, backend nccl;
+    on a one-GPU node both ranks on device 0 over gloo (_n2_hooks)"""
     import json
     import subprocess
     from bench import free_port
@@ -1543,13 +1610,19 @@ def test_bench_two_ranks_over_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SR_BENCH_BACKEND", None)
     env.pop("SR_BENCH_DEVICE", None)
+    env.update(_n2_hooks("ranks"))
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
                           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
-    assert line["n_gpus"] == 2 and line["value"] > 0 and "RCCL" in line["config"]["parallelism"]
+    assert line["n_gpus"] == 2 and line["value"] > 0 and line["top1_word_accuracy"] == 1.0
+    assert line["exchange"]["ranks_in_communicator"] == 2 and line["exchange"]["backend"] == ("nccl" if TWO_DEVICES else "gloo")
+    if TWO_DEVICES:
+        assert "RCCL" in line["config"]["parallelism"] and "TEST HOOK" not in line["config"]["parallelism"]
+    else:
+        assert "TEST HOOK" in line["config"]["parallelism"]
 
 
 def test_bench_other_configs_and_roofline_keys():

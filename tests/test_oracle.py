@@ -2,20 +2,23 @@
 
  * tier (ii) (own restatement) against the committed golden fixtures, which were produced by
    tier (i) = the reference's own .C objects  -> runs anywhere, including the GPU box;
- * tier (ii) against tier (i) live on fresh random inputs, and the regenerated constant tables
-   against the reference headers / assembly table -> only where /root/reference exists.
+ * the regenerated constant tables against the reference headers' / assembly table's values
+   (tests/golden/ref_tables.npz, tests/golden/make_ref_tables.py) -> runs anywhere;
+ * tier (ii) against tier (i) live on fresh random inputs -> where the reference's objects were built (oracle/_ref/);
+ * the reference's assembly FFT run from its source text -> only where the reference tree exists.
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
 import oracle_lib as ol
-from conftest import REFERENCE, needs_reference
+from conftest import REFERENCE, have_ref_objects, needs_ref_objects, needs_reference
 from stm32_speech_recognition_amd import synth
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "ref_golden.npz")
+# the reference's constant tables and its 12-bit ADC capture, as values (tests/golden/make_ref_tables.py)
+REF_TABLES = os.path.join(os.path.dirname(__file__), "golden", "ref_tables.npz")
 
 
 @pytest.fixture(scope="module")
@@ -24,40 +27,32 @@ def golden():
 
 
 @pytest.fixture(scope="module")
+def ref_tables():
+    return np.load(REF_TABLES)
+
+
+@pytest.fixture(scope="module")
 def oracle():
     return ol.Oracle(max_frames=119)
 
 
-def _ref_text(rel):
-    return open(os.path.join(REFERENCE, rel), "rb").read().decode("latin1")
-
-
 # ----------------------------------------------------------------------------- tables
-@needs_reference
-def test_tables_regenerate_reference_headers(oracle):
+def test_tables_regenerate_reference_headers(oracle, ref_tables):
     """MFCC_Arg.h:6-44 -- every constant table regenerates with 0 mismatches."""
-    src = _ref_text("Src/Speech_Recog/MFCC_Arg.h")
     t = oracle.tables()
     for name, key in (("hamm", "hamm"), ("tri_cen", "tri_cen"), ("tri_odd", "tri_odd"), ("tri_even", "tri_even"),
                       ("dct_arg", "dct")):
-        m = re.search(name + r"\[\]\s*=\s*\{([^}]*)\}", src)
-        want = np.array([int(v) for v in re.findall(r"-?\d+", m.group(1))])
+        want = ref_tables[name]
         got = t[key].astype(np.int64)
         assert len(want) == len(got), name
         assert (want != got).sum() == 0, name
 
 
-@needs_reference
-def test_twiddles_regenerate_asm_table():
+def test_twiddles_regenerate_asm_table(ref_tables):
     """cr4_fft_1024_stm32.s:285-629 -- all 1020 (Kr', Ki) entries regenerate exactly."""
     import ctypes as C
-    s = _ref_text("Src/BSP/cr4_fft_1024_stm32.s")
-    tab = s[s.index("TableFFT_V7", s.index("passloop_v7")):]
-    tab = tab[tab.index("\n"):]
-    hw = [int(h, 16) for line in tab.splitlines() if "DCW" in line
-          for h in re.findall(r"0x([0-9a-fA-F]{4})", line.split(";")[0])]
-    hw = np.array(hw, dtype=np.uint16).view(np.int16)
-    assert len(hw) == 2040
+    hw = ref_tables["fft_table"]
+    assert hw.dtype == np.int16 and len(hw) == 2040
     L = ol.Oracle().L
     kr = np.zeros(1020, dtype=np.int16)
     ki = np.zeros(1020, dtype=np.int16)
@@ -65,28 +60,16 @@ def test_twiddles_regenerate_asm_table():
     assert (hw[0::2] != kr).sum() == 0 and (hw[1::2] != ki).sum() == 0
 
 
-def _asm_table():
-    s = _ref_text("Src/BSP/cr4_fft_1024_stm32.s")
-    tab = s[s.index("TableFFT_V7", s.index("passloop_v7")):]
-    tab = tab[tab.index("\n"):]
-    hw = [int(h, 16) for line in tab.splitlines() if "DCW" in line
-          for h in re.findall(r"0x([0-9a-fA-F]{4})", line.split(";")[0])]
-    return np.array(hw, dtype=np.uint16).view(np.int16)
-
-
-@needs_reference
-def test_product_tables_regenerate_reference_headers_and_asm_table():
+def test_product_tables_regenerate_reference_headers_and_asm_table(ref_tables):
     """The PRODUCT's generator (csrc/sr_tables.cpp through the host-only C-ABI call sr_build_tables), not the oracle's
     copy of the formulas: MFCC_Arg.h:6-44 and cr4_fft_1024_stm32.s:285-629 regenerate with 0 mismatches."""
     from stm32_speech_recognition_amd import engine
     t = engine.build_tables()
-    src = _ref_text("Src/Speech_Recog/MFCC_Arg.h")
     for name, key in (("hamm", "hamm"), ("tri_cen", "tri_cen"), ("tri_odd", "tri_odd"), ("tri_even", "tri_even"),
                       ("dct_arg", "dct")):
-        m = re.search(name + r"\[\]\s*=\s*\{([^}]*)\}", src)
-        want = np.array([int(v) for v in re.findall(r"-?\d+", m.group(1))])
+        want = ref_tables[name]
         assert len(want) == len(t[key]) and (want != t[key].astype(np.int64)).sum() == 0, name
-    hw = _asm_table()
+    hw = ref_tables["fft_table"]
     assert len(hw) == 2040 and np.array_equal(hw[0::2], t["tw_kr"]) and np.array_equal(hw[1::2], t["tw_ki"])
 
 
@@ -477,7 +460,7 @@ def test_synth_yields_exact_frame_count():
 
 
 # ----------------------------------------------------------------------------- tier (ii) == tier (i), live
-@needs_reference
+@needs_ref_objects
 def test_tier2_equals_tier1_on_fresh_inputs(oracle):
     r = ol.RefLib()
     rng = np.random.default_rng(77)
@@ -512,7 +495,7 @@ def test_tier2_equals_tier1_on_fresh_inputs(oracle):
             assert d1 == d2
 
 
-@needs_reference
+@needs_ref_objects
 def test_tier2_equals_reference_objects_at_benchmark_shape():
     """BASELINE configs[2]'s shape (256-frame utterances, 100 templates of 192..320 frames) through the REFERENCE'S OWN
     compiled VAD.C / MFCC.C / DTW.C: the objects are built with vv_tim_max = 3210 ms instead of 1200 (the one constant
@@ -557,7 +540,7 @@ def test_tier2_equals_reference_objects_at_benchmark_shape():
     assert (ores["best_tpl"] % NW == words).mean() > 0.9          # the workload is a recognition task, not noise
 
 
-@needs_reference
+@needs_ref_objects
 def test_tier2_dtw_equals_tier1_random_features(oracle):
     r = ol.RefLib()
     rng = np.random.default_rng(123)
@@ -572,12 +555,11 @@ def test_tier2_dtw_equals_tier1_random_features(oracle):
         assert d1 == d2, (p, na, nb)
 
 
-@needs_reference
-def test_reference_adc_dump_probe_values(oracle):
-    """SURVEY.md section 8c probe: the reference's own 12-bit capture 'STM32 123.txt' (read in place)."""
-    txt = _ref_text("Matlab/语音样本/STM32 123.txt".encode("utf-8").decode("utf-8"))
-    vals = np.array([int(x) for x in re.findall(r"\d+", txt)], dtype=np.uint16)
-    assert len(vals) == 16000
+def test_reference_adc_dump_probe_values(oracle, ref_tables):
+    """SURVEY.md section 8c probe: the reference's own 12-bit capture 'STM32 123.txt' (its values, tests/golden/ref_tables.npz);
+    where the reference's objects were built, they must read it the same way."""
+    vals = ref_tables["adc_stm32_123"]
+    assert vals.dtype == np.uint16 and len(vals) == 16000
     rc, a = oracle.noise_atap(vals)
     assert a.astuple() == (2213, 172, 2, 9524)
     seg = oracle.vad(vals, a)
@@ -588,6 +570,8 @@ def test_reference_adc_dump_probe_values(oracle):
     assert list(m0[0]) == [353, 719, 516, 439, -174, -29, -18, -48, 29, -113, -23, -5]
     pad = np.zeros((1, 12), np.int16)
     assert oracle.dtw(np.concatenate([m0, pad]), n0, np.concatenate([m1, pad]), n1) == 3874
+    if not have_ref_objects():
+        return
     r = ol.RefLib()
     a1, s1 = r.vad(vals)
     assert a1.astuple() == a.astuple() and np.array_equal(s1, seg)

@@ -41,7 +41,9 @@ def _worker(rank, world, port, B_total, K, q):
     assert per_rank == [10.0 + r for r in range(world)]
     best, mn = du.argmin_first(gathered)
     q.put((rank, lo, hi, gathered.numpy().view(np.uint32).copy(), t, best.numpy(), mn.numpy()))
-    torch.distributed.barrier()
+    # gloo's monitored_barrier stays on the CPU; barrier() probes the accelerator first, which opens the GPU in every
+    # rank where one exists (8 ranks + the test process would exceed what a shared GPU node admits)
+    torch.distributed.monitored_barrier()
     torch.distributed.destroy_process_group()
 
 
@@ -78,7 +80,7 @@ def _pipeline_worker(rank, world, port, B_local, K, steps, q, kind="scores"):
     for i in range(max(0, steps - 2), steps):
         seen.append((i, x.gathered[i % 2].numpy().view(np.uint32).copy()))
     q.put((rank, seen))
-    torch.distributed.barrier()
+    torch.distributed.monitored_barrier()  # CPU-only, as in _worker
     torch.distributed.destroy_process_group()
 
 
