@@ -2,6 +2,7 @@
 // gfx950 (MI355X, CDNA4) only; wave = 64 lanes; no MFMA (the path has no dense contraction), integer VALU + LDS.
 // Every kernel reproduces the reference's integer arithmetic bit for bit; cited lines are relative to the reference tree.
 #include "sr_dtw_dev.h"
+#include "sr_dtw_plan.h"
 
 namespace sr {
 
@@ -620,12 +621,8 @@ __global__ void __launch_bounds__(1024) k_dtw_lds(const DtwLdsArgs a)
     a.d.scores[(size_t)b * K + a.tpl_orig[ks]] = score;
 }
 
-// pick U: maximise resident lanes doing useful work (LDS 160 KiB/CU, 32 waves/CU, 1024 threads/workgroup), then give
-// what is left of the workgroup's LDS share to the tie-threshold table (tie_g entries of one byte, a power of two).
-// gfx950 hands out LDS in granules of 1280 bytes (160 KiB / 128): three workgroups fit a CU only if each stays within
-// 42 granules = 53 760 bytes -- 20 bytes more and the third one silently does not (measured: mean waves per SIMD 5.0 -> 3.3),
-// although hipOccupancyMaxActiveBlocksPerMultiprocessor still reports 3.
-constexpr size_t kLdsGranule = 1280, kCuLds = 160 * 1024;
+// pick U: maximise resident lanes doing useful work (the CU's LDS in whole granules, 32 waves/CU, 1024 threads/workgroup),
+// then give what is left of the workgroup's LDS share to the tie-threshold table (tie_g entries of one byte, a power of two).
 __host__ __device__ inline size_t dtw_lds_fixed(uint32_t U, uint32_t max_frames, uint32_t row_words = 6)
 {
     const size_t per_u = (size_t)(dtw_lds_row_stride(max_frames, row_words) + dtw_lds_nrm_stride(max_frames)) * 4;
@@ -639,10 +636,10 @@ __host__ __device__ inline size_t dtw_lds_fixed(uint32_t U, uint32_t max_frames,
 // enough resident waves to cover the LDS / L2 latency of the walk, and -- measured at K = 500 -- how many lanes share a
 // template row: the texture addresser is the limit there, and U = 6 x 167 templates runs 12 % faster than U = 2 x 500
 // (30.2 vs 34.3 ms per 65 536 utterances), while U = 10 x 100 (one workgroup per CU) loses 10 %.
-uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, size_t *lds_bytes, uint32_t *tie_g, uint32_t *kc_out, uint32_t row_words)
+uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, const LdsBudget &budget, uint32_t *lds_bytes, uint32_t *tie_g,
+                        uint32_t *kc_out, uint32_t row_words)
 {
     const uint32_t kMinTie = 4096;  // below 4096 every threshold is the exact square: the least useful table
-    auto blocks_for = [](size_t lds) { return (uint32_t)(kCuLds / ((lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule)); };
     uint32_t best_u = 0, best_g = 0, best_kc = 0;
     double best = 0;
     // development hooks (sr_dev_hook): force U / the table size / cap the templates per workgroup.  A forced combination
@@ -659,17 +656,17 @@ uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, size_t *lds_bytes, uint
         kc = (K + chunks - 1) / chunks;             // equal chunks
         const uint64_t pairs = (uint64_t)U * kc;
         const size_t lds = dtw_lds_fixed(U, max_frames, row_words);
-        if (lds + kMinTie > 150 * 1024) break;
+        if (lds + kMinTie > budget.stage_cap) break;
         const uint32_t waves = (uint32_t)((pairs + 63) / 64);
-        uint32_t blocks = blocks_for(lds + kMinTie);
+        uint32_t blocks = budget.wgs_per_cu(lds + kMinTie);
         if (blocks > 32 / waves) blocks = 32 / waves;
         if (blocks > 8) blocks = 8;
         if (blocks < 1) continue;
         uint32_t g = kMinTie;  // the largest table that does not cost a resident workgroup
-        while (g < (uint32_t)kTieMax && blocks_for(lds + 2 * g) >= blocks) g *= 2;
+        while (g < (uint32_t)kTieMax && budget.wgs_per_cu(lds + 2 * g) >= blocks) g *= 2;
         if (force_g >= kMinTie && force_g <= (uint32_t)kTieMax) {
             g = force_g & ~1023u;
-            if (blocks_for(lds + g) < 1) continue;  // a forced table that does not fit beside the utterances
+            if (budget.wgs_per_cu(lds + g) < 1) continue;  // a forced table that does not fit beside the utterances
         }
         const double eff = (double)K / ((double)chunks * 64.0 * waves / U);  // lanes that carry a pair, over all chunks
         const double resident = (double)(blocks * waves);
@@ -689,34 +686,32 @@ uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, size_t *lds_bytes, uint
             best_kc = kc;
         }
     }
-    if (best_u && lds_bytes) *lds_bytes = dtw_lds_fixed(best_u, max_frames, row_words) + best_g;
+    if (best_u && lds_bytes) *lds_bytes = (uint32_t)(dtw_lds_fixed(best_u, max_frames, row_words) + best_g);
     if (tie_g) *tie_g = best_g;
     if (kc_out) *kc_out = best_kc;
     return best_u;
 }
 
-void launch_dtw(const DtwArgs &a, hipStream_t s)
+void launch_dtw(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
 {
     const uint64_t n = (uint64_t)a.B * a.K;
     if (!n) return;
-    // U (utterances per workgroup) and the LDS size were chosen once, when the template store was set
-    const uint32_t U = a.tplR ? a.lds_u : 0;
-    // GENERIC front end with another feature width: up to 12 coefficients ride the staged kernel's 12-wide form (rows zero-padded
-    // to 12 in its LDS image and in the length-sorted store), 13..16 its 16-wide form; stores that cannot be staged take k_dtw_gen
-    if (a.n_coef != (uint32_t)kCoef && !U) {
+    if (p.lds_u) {
+        // other feature widths (GENERIC front end): up to 12 coefficients ride the 12-wide form (rows zero-padded), 13..16 the 16-wide one
+        const uint32_t U = p.lds_u, Kc = p.lds_kc;
+        DtwLdsArgs la{a, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, U, a.tie_delta, p.lds_tie_g, Kc};
+        const dim3 grid((a.B + U - 1) / U, (a.K + Kc - 1) / Kc), block((uint32_t)(((uint64_t)U * Kc + 63) / 64 * 64));
+        if (a.n_coef > (uint32_t)kCoef) hipLaunchKernelGGL(k_dtw_lds<Dtw16>, grid, block, p.lds_bytes, s, la);
+        else hipLaunchKernelGGL(k_dtw_lds<Dtw12>, grid, block, p.lds_bytes, s, la);
+    } else if (a.n_coef != (uint32_t)kCoef) {  // stores that cannot be staged, other feature widths
         hipLaunchKernelGGL(k_dtw_gen, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, s, a);
-        return;
-    }
-    const size_t lds = a.lds_bytes;
-    if (U) {
-        const uint32_t Kc = (a.lds_kc && a.lds_kc < a.K) ? a.lds_kc : a.K, chunks = (a.K + Kc - 1) / Kc;
-        DtwLdsArgs la{a, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, U, a.tie_delta, a.tie_g, Kc};
-        const uint32_t threads = (uint32_t)(((uint64_t)U * Kc + 63) / 64 * 64);
-        if (a.n_coef > (uint32_t)kCoef) hipLaunchKernelGGL(k_dtw_lds<Dtw16>, dim3((a.B + U - 1) / U, chunks), dim3(threads), lds, s, la);
-        else hipLaunchKernelGGL(k_dtw_lds<Dtw12>, dim3((a.B + U - 1) / U, chunks), dim3(threads), lds, s, la);
     } else {  // very long sequences / very many templates: generic global-memory walk
         hipLaunchKernelGGL(k_dtw, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, s, a);
     }
+}
+const char *dtw_lds_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_dtw_lds<Dtw12>, "k_dtw_lds<Dtw12>"}, {(const void *)k_dtw_lds<Dtw16>, "k_dtw_lds<Dtw16>"}}, bytes);
 }
 
 // argmin with strict '<' in slot order (main.c:276-291): first minimum wins; all dis_err -> slot 0

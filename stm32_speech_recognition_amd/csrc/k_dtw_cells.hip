@@ -12,8 +12,8 @@
 // Same arithmetic as k_dtw_gen (any feature width up to 16 coefficients, plain template store), so the scores are identical.
 #include <vector>
 
-#include "sr_dtw_cells.h"
 #include "sr_dtw_dev.h"
+#include "sr_dtw_plan.h"
 
 namespace sr {
 namespace cells {
@@ -165,13 +165,6 @@ size_t dtw_cells_lds(uint32_t max_frames, uint32_t tpl_rows, uint32_t max_points
     return ((size_t)max_frames * cells::kInWords + (size_t)tpl_rows * cells::kRowWords + 3 * ((size_t)max_frames + 1) + max_points) *
            sizeof(uint32_t);
 }
-bool dtw_cells_fits(const DtwArgs &a)
-{
-    // two rows per sequence at least (the do-while of DTW.C:150-188 reads row 1 even of 1-frame sequences); the jump over two
-    // steps must fit 11 bits; one workgroup's LDS
-    return a.cells_points != 0 && a.max_frames >= 2 && a.tpl_rows >= 2 && a.tpl_rows <= 1023 && a.n_coef >= 1 && a.n_coef <= 16 &&
-           dtw_cells_lds(a.max_frames, a.tpl_rows, a.cells_points) <= 150 * 1024;
-}
 
 #ifdef SR_CELLS_TIMING
 // development build only (-DSR_CELLS_TIMING): s_memtime at the phase boundaries of the workgroup of pair (0, 0)
@@ -321,7 +314,7 @@ __global__ void __launch_bounds__(cells::kThreads) k_dtw_cells(const DtwArgs a, 
                     if (!(w & kStopBit) && !((w >> kErrShift) & 3u)) {
                         const uint32_t w2 = s_pt[c + (w >> kJumpShift)];
                         // costs, outside counts and jumps add up field by field (no carry: 2 x 65 535 < 2^17, 1 + 1 < 4, the jump
-                        // bound is checked by dtw_cells_fits); the second step decides whether the walk ends
+                        // bound is checked by plan_dtw); the second step decides whether the walk ends
                         w = (w + (w2 & ~(kStopBit | kTwoBit))) | (w2 & kStopBit) | kTwoBit;
                     }
                 }
@@ -426,15 +419,19 @@ __global__ void __launch_bounds__(cells::kThreads) k_dtw_cells(const DtwArgs a, 
     CELLS_T(5);  // slot scan (only if this pair was the last one)
 }
 
-void launch_dtw_cells(const DtwArgs &a, hipStream_t s)
+void launch_dtw_cells(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
 {
     if (!a.B || !a.K) return;
-    const size_t lds = dtw_cells_lds(a.max_frames, a.tpl_rows, a.cells_points);
+    const size_t lds = p.cells_bytes;
     for (uint32_t b0 = 0; b0 < a.B; b0 += 65535) {  // utterances are the grid's second dimension
         const uint32_t nb = a.B - b0 < 65535 ? a.B - b0 : 65535;
         if (a.n_coef <= (uint32_t)kCoef) hipLaunchKernelGGL(k_dtw_cells<6>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
         else hipLaunchKernelGGL(k_dtw_cells<8>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
     }
+}
+const char *dtw_cells_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_dtw_cells<6>, "k_dtw_cells<6>"}, {(const void *)k_dtw_cells<8>, "k_dtw_cells<8>"}}, bytes);
 }
 
 }  // namespace sr

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "sr_dtw_dev.h"
+#include "sr_dtw_plan.h"
 
 namespace sr {
 
@@ -335,38 +336,25 @@ static uint32_t dp_band_lds(uint32_t tpl_rows, int G, int waves, uint32_t *rows_
 // three of them fit a CU instead of one: their waves pile up on two of the four SIMDs)
 static int dp_waves_for(int G) { (void)G; return 4; }
 
-void launch_dtw_dp(const DtwArgs &a, hipStream_t s)
+void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hipStream_t s)
 {
     if (!a.B || !a.K) return;
-    int G = (int)a.dp_lanes;  // 0 = choose
+    int G = (int)lanes;  // 4 / 8 / 16 lanes per pair of the band kernel, 1 = k_dtw_dp_wave64, 0 = choose
     uint32_t rp = 0;
     if (G != 1 && G != 4 && G != 8 && G != 16) {
-        // 8 lanes per pair while three of its workgroups fit a CU's 160 KiB (handed out in granules of 1280 bytes): 111 ms
-        // per 65 536 x 100 pairs at a 320-frame cap; one granule more and only two fit (153 ms) -- then 16 lanes per pair
-        // (half the boundary columns, 120 ms with three or four workgroups per CU) is the better shape
-        auto wgs = [&](int g) { return (160u * 1024u) / ((dp_band_lds(a.tpl_rows, g, dp_waves_for(g), nullptr) + 1279u) / 1280u * 1280u); };
+        // 8 lanes per pair while three of its workgroups fit a CU (MI355X: 160 KiB in granules of 1 280 bytes): 111 ms per
+        // 65 536 x 100 pairs at a 320-frame cap; one granule more and only two fit (153 ms) -- then 16 lanes per pair (half
+        // the boundary columns, 120 ms with three or four workgroups per CU) is the better shape
+        auto wgs = [&](int g) { return budget.wgs_per_cu(dp_band_lds(a.tpl_rows, g, dp_waves_for(g), nullptr)); };
         G = (wgs(8) >= 3 || wgs(16) < 3) ? 8 : 16;
     }
-    if (G != 1 && (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > 150u * 1024u)) {
+    if (G != 1 && (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > budget.stage_cap)) {
         G = 16;  // fewer pairs per wave: fewer boundary columns
-        if (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > 150u * 1024u) G = 1;
-    }
-    if (G == 1) {
-        const size_t lds = (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4;
-        for (uint32_t b0 = 0; b0 < a.B; b0 += 65535u * 4u) {  // grid.y <= 65 535
-            DtwArgs sa = a;
-            sa.B = (a.B - b0 < 65535u * 4u) ? a.B - b0 : 65535u * 4u;
-            sa.mfcc = a.mfcc + (size_t)b0 * a.max_frames * kCoef;
-            sa.vad = a.vad ? a.vad + b0 : nullptr;
-            sa.in_frames = a.in_frames ? a.in_frames + b0 : nullptr;
-            sa.scores = a.scores + (size_t)b0 * a.K;
-            hipLaunchKernelGGL(k_dtw_dp_wave64, dim3(a.K, (sa.B + 3) / 4), dim3(256), lds, s, sa);
-        }
-        return;
+        if (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > budget.stage_cap) G = 1;
     }
     const int W = dp_waves_for(G);
-    const size_t lds = dp_band_lds(a.tpl_rows, G, W, &rp);
-    const uint32_t per_wg = (uint32_t)(W * (64 / G));
+    const uint32_t per_wg = G == 1 ? 4u : (uint32_t)(W * (64 / G));  // utterances per workgroup (k_dtw_dp_wave64: one per wave)
+    const size_t lds = G == 1 ? (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4 : dp_band_lds(a.tpl_rows, G, W, &rp);
     // the utterance blocks are the grid's second dimension (<= 65 535): larger batches go out in slices
     const uint32_t slice = 65535u * per_wg;
     for (uint32_t b0 = 0; b0 < a.B; b0 += slice) {
@@ -376,12 +364,18 @@ void launch_dtw_dp(const DtwArgs &a, hipStream_t s)
         sa.vad = a.vad ? a.vad + b0 : nullptr;
         sa.in_frames = a.in_frames ? a.in_frames + b0 : nullptr;
         sa.scores = a.scores + (size_t)b0 * a.K;
-        DpBandArgs ba{sa, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, rp};
         const dim3 grid(a.K, (sa.B + per_wg - 1) / per_wg), block(64 * W);
-        if (G == 4) hipLaunchKernelGGL((k_dtw_dp_band<4, 4>), grid, block, lds, s, ba);
+        DpBandArgs ba{sa, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, rp};
+        if (G == 1) hipLaunchKernelGGL(k_dtw_dp_wave64, grid, block, lds, s, sa);
+        else if (G == 4) hipLaunchKernelGGL((k_dtw_dp_band<4, 4>), grid, block, lds, s, ba);
         else if (G == 8) hipLaunchKernelGGL((k_dtw_dp_band<8, 4>), grid, block, lds, s, ba);
         else hipLaunchKernelGGL((k_dtw_dp_band<16, 4>), grid, block, lds, s, ba);
     }
+}
+const char *dtw_dp_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_dtw_dp_wave64, "k_dtw_dp_wave64"}, {(const void *)k_dtw_dp_band<4, 4>, "k_dtw_dp_band<4, 4>"},
+                              {(const void *)k_dtw_dp_band<8, 4>, "k_dtw_dp_band<8, 4>"}, {(const void *)k_dtw_dp_band<16, 4>, "k_dtw_dp_band<16, 4>"}}, bytes);
 }
 
 }  // namespace sr

@@ -31,7 +31,7 @@
 #include <algorithm>
 
 #include "sr_dtw_dev.h"
-#include "sr_dtw_quad.h"
+#include "sr_dtw_plan.h"
 
 namespace sr {
 namespace quad {
@@ -235,58 +235,50 @@ __global__ void __launch_bounds__(quad::kThreads) k_dtw_quad(const DtwArgs a, ui
 
 // workgroup shape for a store: PU utterances x PK templates per workgroup, the most pairs (<= 64) whose records fit the LDS
 // budget; false = not even 1 x 4 fits (very long sequences)
-bool dtw_quad_pick(const DtwArgs &a, uint32_t *pu, uint32_t *pk, size_t *lds)
+bool dtw_quad_pick(uint32_t K, uint32_t max_frames, uint32_t tpl_rows, uint32_t n_coef, const LdsBudget &lds, uint32_t *pu,
+                   uint32_t *pk, uint32_t *lds_bytes)
 {
-    if (a.max_frames < 2 || a.tpl_rows < 2 || a.n_coef < 1 || a.n_coef > 16 || !a.K) return false;
-    const int words = a.n_coef <= (uint32_t)kCoef ? 6 : 8;
-    const size_t in_rec = quad::rec_bytes(a.max_frames, words), tp_rec = quad::rec_bytes(a.tpl_rows, words);
+    if (max_frames < 2 || tpl_rows < 2 || n_coef < 1 || n_coef > 16 || !K) return false;
+    const int words = n_coef <= (uint32_t)kCoef ? 6 : 8;
+    const size_t in_rec = quad::rec_bytes(max_frames, words), tp_rec = quad::rec_bytes(tpl_rows, words);
     static const uint32_t shapes[][2] = {{8, 8}, {4, 16}, {4, 8}, {2, 16}, {4, 4}, {2, 8}, {1, 16}, {2, 4}, {1, 8}, {1, 4}};
     uint64_t best = 0;
-    // LDS of the device the engine runs on (MI355X: 128 granules of 1 280 bytes per CU, all of which one workgroup may take)
-    const size_t cu_gran = (a.dev_lds_cu ? a.dev_lds_cu : 160u * 1024u) / 1280, wg_max = a.dev_lds_wg ? a.dev_lds_wg : 160u * 1024u;
+    const size_t cu_gran = lds.per_cu / lds.granule;
     for (const auto &sh : shapes) {  // the most pairs resident per CU (workgroups by LDS granules, at most 8 of four waves)
-        const size_t need = sh[0] * in_rec + sh[1] * tp_rec, gran = (need + 1279) / 1280;
-        if (gran + 8 > cu_gran || need > wg_max) continue;
-        const uint64_t per_cu = std::min<uint64_t>(8, cu_gran / gran) * sh[0] * sh[1];
+        const size_t need = sh[0] * in_rec + sh[1] * tp_rec, gran = (need + lds.granule - 1) / lds.granule;
+        if (gran + 8 > cu_gran || need > lds.per_wg) continue;
+        const uint64_t per_cu = std::min<uint64_t>(8, lds.wgs_per_cu(need)) * sh[0] * sh[1];
         if (per_cu <= best) continue;
         best = per_cu;
         *pu = sh[0];
         *pk = sh[1];
-        *lds = need;
+        *lds_bytes = (uint32_t)need;
     }
     return best != 0;
 }
-bool dtw_quad_fits(const DtwArgs &a)
-{
-    uint32_t pu, pk;
-    size_t lds;
-    return dtw_quad_pick(a, &pu, &pk, &lds);
-}
 
-void launch_dtw_quad(const DtwArgs &a, hipStream_t s)
+void launch_dtw_quad(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
 {
     if (!a.B || !a.K) return;
-    uint32_t pu = 0, pk = 0;
-    size_t lds = 0;
-    if (!dtw_quad_pick(a, &pu, &pk, &lds)) return;  // callers check dtw_quad_fits first
-    if (lds > 64 * 1024) {  // above the default limit the kernel's dynamic LDS has to be allowed explicitly (once per instance)
-        const void *f = a.n_coef <= (uint32_t)kCoef ? (a.tpl_neg2_ok ? (const void *)k_dtw_quad<6, true> : (const void *)k_dtw_quad<6, false>)
-                                                    : (a.tpl_neg2_ok ? (const void *)k_dtw_quad<8, true> : (const void *)k_dtw_quad<8, false>);
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(a.dev_lds_wg ? a.dev_lds_wg : 160u * 1024u));
-    }
-    const uint32_t gx = (a.K + pk - 1) / pk;
+    const uint32_t pu = p.quad_pu, pk = p.quad_pk, gx = (a.K + pk - 1) / pk;
+    const size_t lds = p.quad_bytes;
     for (uint32_t b0 = 0; b0 < a.B; b0 += 65535u * pu) {  // utterance groups are the grid's second dimension
         const uint32_t nb = a.B - b0 < 65535u * pu ? a.B - b0 : 65535u * pu;
         const dim3 grid(gx, (nb + pu - 1) / pu);
         const dim3 blk(quad::kThreads);
         if (a.n_coef <= (uint32_t)kCoef) {
-            if (a.tpl_neg2_ok) hipLaunchKernelGGL((k_dtw_quad<6, true>), grid, blk, lds, s, a, pu, pk, b0);
+            if (p.quad_neg2) hipLaunchKernelGGL((k_dtw_quad<6, true>), grid, blk, lds, s, a, pu, pk, b0);
             else hipLaunchKernelGGL((k_dtw_quad<6, false>), grid, blk, lds, s, a, pu, pk, b0);
         } else {
-            if (a.tpl_neg2_ok) hipLaunchKernelGGL((k_dtw_quad<8, true>), grid, blk, lds, s, a, pu, pk, b0);
+            if (p.quad_neg2) hipLaunchKernelGGL((k_dtw_quad<8, true>), grid, blk, lds, s, a, pu, pk, b0);
             else hipLaunchKernelGGL((k_dtw_quad<8, false>), grid, blk, lds, s, a, pu, pk, b0);
         }
     }
+}
+const char *dtw_quad_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_dtw_quad<6, true>, "k_dtw_quad<6, true>"}, {(const void *)k_dtw_quad<6, false>, "k_dtw_quad<6, false>"},
+                              {(const void *)k_dtw_quad<8, true>, "k_dtw_quad<8, true>"}, {(const void *)k_dtw_quad<8, false>, "k_dtw_quad<8, false>"}}, bytes);
 }
 
 }  // namespace sr

@@ -102,22 +102,15 @@ struct DtwArgs {
     uint32_t tpl_rows;        // rows allocated per template
     uint32_t *scores;         // [B][K]
     sr_result *results;       // [B] (argmin kernel)
-    // length-sorted, row-interleaved copy of the store for k_dtw_lds (NULL -> generic kernel)
+    // length-sorted, row-interleaved copy of the store for k_dtw_lds / k_dtw_dp_band
     const void *tplR;             // [tpl_rows][K] 32-byte rows: 12 x s16 | u32 squared norm | pad  (48-byte rows of 16 x s16 when n_coef > 12)
     const uint32_t *tpl_frames_s; // [K]
     const uint32_t *tpl_orig;     // [K]
-    uint32_t lds_u;               // utterances per k_dtw_lds workgroup (0 -> generic kernel), see dtw_lds_pick_u
-    uint32_t lds_bytes;           // dynamic LDS of k_dtw_lds for that choice
     const int8_t *tie_delta;      // DevTables::tie_delta
-    uint32_t tie_g;               // entries of it the workgroup stages in LDS (a multiple of 1024, <= kTieMax)
-    uint32_t lds_kc;              // templates per k_dtw_lds workgroup (dtw_lds_pick_u); the store is walked in K / lds_kc chunks
     uint32_t n_coef;              // s16 per feature row: 12 everywhere except the GENERIC front end (1..16)
-    uint32_t dp_lanes;            // k_dtw_dp only: lanes per pair of the band kernel (4 / 8 / 16; 0 = default 8; 1 = k_dtw_dp_wave64)
     uint32_t *pair_count;         // k_dtw_cells only: [B] zeroed counters of finished pairs (the last one does the slot scan); may be NULL
-    uint32_t cells_points;        // k_dtw_cells only: most band points of any pair of this store (dtw_cells_max_points; 0 = kernel not usable)
-    uint32_t tpl_neg2_ok;         // k_dtw_quad only: every coefficient of the store lies in [-16383, 16384], so -2 * coefficient fits s16 (checked when the store is set)
+    uint32_t cells_points;        // k_dtw_cells only: most band points of any pair of this store (DtwPlan::cells_points)
     uint32_t cells_literal;       // k_dtw_cells only: development hook "cells_literal" -- every pair takes the literal fallback walk
-    uint32_t dev_cus, dev_lds_cu, dev_lds_wg;  // compute units / LDS bytes per CU / LDS bytes one workgroup may take on this device (sr_create); 0 = MI355X's 256 / 160 KiB / 160 KiB
 };
 
 // get_mdl (DTW.C:217-296): P independent pairs
@@ -146,13 +139,7 @@ void launch_mfcc_gen(const MfccArgs &a, hipStream_t s);  // GENERIC front end (k
 uint32_t mfcc_frames_per_tile(uint32_t frame_len);        // frames one work item of the frame kernel covers
 uint32_t mfcc_frames_per_tile_small(uint32_t frame_len, uint32_t which);  // ... of its forms for underfilled launches (MfccArgs::small_tiles - 1)
 uint32_t mfcc_resident_workgroups(uint32_t frame_len);  // occupancy x CUs on the current device
-void launch_dtw(const DtwArgs &a, hipStream_t s);
-// utterances per k_dtw_lds workgroup for K templates / max_frames rows (0 = use the generic kernel); tuning
-// override: development hooks dtw_u / dtw_kc / dtw_tie_g (sr_dev_hook), read when the template store is set
-// (row_words: packed coefficient pairs per feature row of the staged kernel's form: 6 = up to 12 coefficients, 8 = 13..16)
-uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, size_t *lds_bytes, uint32_t *tie_g, uint32_t *kc, uint32_t row_words = 6);
-void launch_argmin(const DtwArgs &a, hipStream_t s);
-void launch_dtw_dp(const DtwArgs &a, hipStream_t s);  // opt-in non-reference full-DP scorer
+void launch_argmin(const DtwArgs &a, hipStream_t s);  // (the DTW launchers: sr_dtw_plan.h)
 // generic complex 1024-point Q15 FFT, n arrays (cr4_fft_1024_stm32 semantics)
 void launch_fft_q15(const uint32_t *in, uint32_t *out, uint32_t n, const DevTables &t, hipStream_t s);
 // magnitude*10 of bins 0..511 of zero-padded real frames: fft() of MFCC.C:27-62.

@@ -1,0 +1,69 @@
+// sr_dtw_plan.h -- which DTW kernel runs, in what shape, with how much LDS.  Everything that depends only on the template
+// store and the device is decided once, when the store is set (plan_dtw, sr_launch.cpp), from the device's LDS figures;
+// launch_dtw_auto then only compares the launch's pairs with the plan's thresholds and calls one of the launchers below.
+#pragma once
+#include <cstdint>
+#include <initializer_list>
+#include <utility>
+#include <vector>
+
+#include "sr_device.h"
+
+namespace sr {
+
+// LDS of the engine's device (sr_create reads it from the device; the defaults are MI355X's)
+struct LdsBudget {
+    uint32_t per_cu = 160 * 1024;     // bytes per CU
+    uint32_t per_wg = 160 * 1024;     // bytes one workgroup may take
+    uint32_t granule = 1280;          // allocation unit (gfx950: 128 per CU)
+    uint32_t stage_cap = 150 * 1024;  // what the LDS-staged kernels plan one workgroup with: min(150 KiB, per_wg)
+    // Workgroups of `bytes` that fit a CU.  LDS goes out in whole granules: three workgroups fit an MI355X CU only if each
+    // stays within 42 granules = 53 760 bytes -- 20 bytes more and the third one silently does not (measured: mean waves per
+    // SIMD 5.0 -> 3.3), although hipOccupancyMaxActiveBlocksPerMultiprocessor still reports 3.
+    uint32_t wgs_per_cu(size_t bytes) const { return (uint32_t)(per_cu / ((bytes + granule - 1) / granule * granule)); }
+};
+
+// the DTW launch plan of one template store (sr_engine::plan)
+struct DtwPlan {
+    uint32_t lds_u = 0, lds_kc = 0, lds_tie_g = 0, lds_bytes = 0;  // k_dtw_lds: U utterances x Kc templates (U = 0: not staged)
+    uint32_t cells_points = 0, cells_bytes = 0;  // k_dtw_cells: most band points of any pair (0 = does not fit) and its LDS
+    uint32_t quad_pu = 0, quad_pk = 0, quad_bytes = 0;  // k_dtw_quad: PU utterances x PK templates (PU = 0: does not fit)
+    bool quad_neg2 = false;                      // k_dtw_quad's instance with -2 * coefficient template rows (tpl_staged_ok)
+    uint64_t cells_pairs = 0, quad_pairs = 0;    // automatic mode: k_dtw_cells up to cells_pairs pairs, then k_dtw_quad up to quad_pairs
+};
+
+// Shapes (called by plan_dtw).  U utterances per k_dtw_lds workgroup for K templates / max_frames rows (0 = not staged); the
+// development hooks dtw_u / dtw_kc / dtw_tie_g override it.  row_words: packed coefficient pairs per feature row of the
+// staged kernel's form: 6 = up to 12 coefficients, 8 = 13..16.
+uint32_t dtw_lds_pick_u(uint32_t K, uint32_t max_frames, const LdsBudget &lds, uint32_t *lds_bytes, uint32_t *tie_g, uint32_t *kc,
+                        uint32_t row_words = 6);
+// the most points of dtw_limit's band any (utterance, template) pair of a store can have (0: not worth setting up).
+// by_len: the engine's cache per template length (the frame cap of an engine never changes), so that a store that grows
+// slot by slot -- dtw()'s model cache -- pays per new length
+uint32_t dtw_cells_max_points(uint32_t max_frames, const uint32_t *frames, const uint8_t *valid, uint32_t K, std::vector<uint32_t> &by_len);
+size_t dtw_cells_lds(uint32_t max_frames, uint32_t tpl_rows, uint32_t max_points);
+// k_dtw_quad's workgroup: pu utterances x pk templates (pu * pk <= 64 pairs) and its LDS bytes; false = not even 1 x 4 fits
+bool dtw_quad_pick(uint32_t K, uint32_t max_frames, uint32_t tpl_rows, uint32_t n_coef, const LdsBudget &lds, uint32_t *pu,
+                   uint32_t *pk, uint32_t *lds_bytes);
+
+// Launchers, identical scores in every form: k_dtw_lds / k_dtw_gen / k_dtw (the batch kernels); k_dtw_cells, one workgroup
+// per pair (a few hundred pairs); k_dtw_quad, four lanes per pair (a few thousand to ~100 000)
+void launch_dtw(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
+void launch_dtw_cells(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
+void launch_dtw_quad(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
+void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &lds, hipStream_t s);  // opt-in full-DP scorer (sr_set_dp_lanes)
+
+// sr_create: let every instance of the file's kernels take up to `bytes` of dynamic LDS (the default limit is 64 KiB);
+// returns the name of an instance that was refused, or nullptr
+const char *dtw_lds_allow_lds(uint32_t bytes);
+const char *dtw_cells_allow_lds(uint32_t bytes);
+const char *dtw_quad_allow_lds(uint32_t bytes);
+const char *dtw_dp_allow_lds(uint32_t bytes);
+inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
+{
+    for (const auto &k : kernels)
+        if (hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return k.second;
+    return nullptr;
+}
+
+}  // namespace sr

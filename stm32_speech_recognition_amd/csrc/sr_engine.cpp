@@ -124,14 +124,14 @@ int sr_dev_hook(const char *name, int64_t value)
 int sr_dtw_geometry(uint32_t n_templates, uint32_t max_frames, uint32_t out[5])
 {
     if (!out || !n_templates || max_frames < 2 || max_frames > 16383) return fail(SR_ERR_BAD_ARG, "null / zero argument");
-    size_t lds = 0;
-    uint32_t tie_g = 0, kc = 0;
-    const uint32_t U = dtw_lds_pick_u(n_templates, max_frames, &lds, &tie_g, &kc);
+    uint32_t lds = 0, tie_g = 0, kc = 0;
+    const LdsBudget mi355x;  // no device: MI355X's figures
+    const uint32_t U = dtw_lds_pick_u(n_templates, max_frames, mi355x, &lds, &tie_g, &kc);
     out[0] = U;
     out[1] = U ? kc : 0;
     out[2] = U ? tie_g : 0;
-    out[3] = U ? (uint32_t)lds : 0;
-    out[4] = U ? (uint32_t)((160u * 1024u) / ((lds + 1279) / 1280 * 1280)) : 0;
+    out[3] = U ? lds : 0;
+    out[4] = U ? mi355x.wgs_per_cu(lds) : 0;
     return SR_OK;
 }
 
@@ -230,10 +230,19 @@ int sr_create(const sr_config *cfg, sr_engine **out)
     {  // what launch-shape decisions need to know about THIS device (a partitioned or CU-masked part is not 256 CUs)
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) h->n_cu = (uint32_t)v;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && v > 0) h->lds_per_cu = (uint32_t)v;
+        LdsBudget &lds = h->lds;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && v > 0) lds.per_cu = (uint32_t)v;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && v > 0)
-            h->lds_per_wg = std::max<uint32_t>((uint32_t)v, 64u * 1024u) > h->lds_per_cu ? h->lds_per_cu : std::max<uint32_t>((uint32_t)v, 64u * 1024u);
+            lds.per_wg = std::min(std::max<uint32_t>((uint32_t)v, 64u * 1024u), lds.per_cu);
+        lds.stage_cap = std::min(lds.stage_cap, lds.per_wg);
         (void)hipGetLastError();
+    }
+    // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
+    for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds}) {
+        if (const char *kernel = allow(h->lds.per_wg)) {
+            delete h;
+            return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));
+        }
     }
     build_tables(h->host, fe);
     warn_log_table();
@@ -334,7 +343,8 @@ int sr_create(const sr_config *cfg, sr_engine **out)
             (void)fail(SR_OK, msg);
         }
     }
-    if (h->s_pcnt.reserve(kPairCounters) != SR_OK || hipMemset(h->s_pcnt.p, 0, kPairCounters * sizeof(uint32_t)) != hipSuccess) {
+    if (h->s_pcnt.reserve(kPairCounters) != SR_OK || hipMemset(h->s_pcnt.p, 0, kPairCounters * sizeof(uint32_t)) != hipSuccess ||
+        hipEventCreateWithFlags(&h->ev_cells, hipEventDisableTiming) != hipSuccess) {
         sr_destroy(h);
         return fail(SR_ERR_HIP, "pair counters");
     }
@@ -350,6 +360,7 @@ void sr_destroy(sr_engine *h)
     (void)hipDeviceSynchronize();
     if (h->table_blob) (void)hipFree(h->table_blob);
     if (h->ev_scratch) (void)hipEventDestroy(h->ev_scratch);
+    if (h->ev_cells) (void)hipEventDestroy(h->ev_cells);
     h->tpl.release();
     h->tpl_frames.release();
     h->tpl_valid.release();
@@ -470,36 +481,17 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
     n_frames_s.release();
     n_orig.release();
     h->tpl_staged_ok = fits;
-    {
-        size_t lds = 0;
-        uint32_t tie_g = 0, kc = 0;
-        h->dtw_u = h->tpl_staged_ok ? dtw_lds_pick_u(K, h->cfg.max_frames, &lds, &tie_g, &kc, nc > (uint32_t)kCoef ? 8u : 6u) : 0;
-        h->dtw_lds = (uint32_t)lds;
-        h->dtw_tie_g = tie_g;
-        h->dtw_kc = kc;
-        if (dev_hook(kHookDtwDebug))
-                std::fprintf(stderr, "sr_engine: k_dtw_lds geometry for K = %u, %u rows: U = %u, Kc = %u, tie table %u, LDS %zu bytes\n", K,
-                             h->cfg.max_frames, h->dtw_u, kc, tie_g, lds);
-    }
+    h->K = K;
+    h->tpl_rows = rows;
+    h->tpl_stride = rows * nc;
+    plan_dtw(h, f.data(), v.data());
     // Chunk count of the device-resident pipeline by store size (round-4 sweeps, profiles/experiments/RESULTS.md): with
     // 100 templates 3 streams x 6..15 chunks are equivalent (22.3 ms per 65 536 utterances); with 500 templates the DTW
     // launches dominate and fewer, longer chunks win by 1 % (3 x 6: 45.0-46.2 ms, 3 x 12: 45.2-46.7).
-    // small launches: the most band points any pair of this store can have (k_dtw_cells keeps one word per point in LDS)
-    // -- capped at what a workgroup's LDS holds beside the rows: a pair with more points than that (utterances near the frame
-    // cap against the longest templates) is walked literally by its workgroup, which costs what the batch kernel costs
-    h->cells_points = dtw_cells_max_points(h->cfg.max_frames, f.data(), v.data(), K, h->cells_by_len);
-    {
-        const size_t fixed = dtw_cells_lds(h->cfg.max_frames, rows, 0), budget = 150 * 1024;
-        const size_t room = fixed < budget ? (budget - fixed) / sizeof(uint32_t) : 0;
-        if (h->cells_points > room) h->cells_points = room >= 4096 ? (uint32_t)room : 0u;
-    }
     // Large stores: the DTW is most of a step (70 % at K = 500), every chunk adds one drain of its long workgroups, and there
     // is little left to overlap it with: one chunk per stream.  Measured at 65 536 x 500 (profiles/experiments/RESULTS.md):
     // 3 streams x 3 chunks 44.4-44.6 ms, x 6: 44.8-44.9, x 12: 45.2; x 4 (one chunk left over on one stream): 45.4.
     if (!h->pipe_user_set) h->pipe_max_chunks = K >= 256 ? h->pipe_streams : 12;
-    h->K = K;
-    h->tpl_rows = rows;
-    h->tpl_stride = rows * nc;
     return SR_OK;
 }
 

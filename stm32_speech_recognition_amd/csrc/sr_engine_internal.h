@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "sr_device.h"
-#include "sr_dtw_cells.h"
+#include "sr_dtw_plan.h"
 #include "sr_tables.h"
 
 namespace sr {
@@ -88,7 +88,8 @@ struct sr_engine {
     sr_config cfg;
     int device = 0;
     uint32_t noise_len = 0, atap_frm = 0;
-    uint32_t n_cu = 256, lds_per_cu = 160 * 1024, lds_per_wg = 160 * 1024;  // of the engine's device (sr_create): launch-shape decisions use these, not MI355X's figures
+    uint32_t n_cu = 256;  // compute units of the engine's device (sr_create)
+    LdsBudget lds;        // its LDS (sr_create): every DTW launch shape is planned from these figures, not MI355X's
     uint32_t mag_cheap_max = 0;  // kMagCheapMax once the device sweep at sr_create has confirmed the cheap magnitude form on this chip, else 0
     uint32_t mfcc_tile = 64, mfcc_tile_mid = 64, mfcc_tile_small = 64, mfcc_grid_cap = 0;  // frames per k_mfcc work item (batch form / the two forms for underfilled launches), resident workgroups
     uint32_t frame_len = 160, hop = 80;          // 160/80 reference, 320/160 extension, or the generic front end's framing
@@ -106,10 +107,9 @@ struct sr_engine {
     DevBuf<uint32_t> tplR;         // [rows][K] 32-byte rows (12 x s16 | norm | pad), templates ordered by length
     DevBuf<uint32_t> tpl_frames_s, tpl_orig;
     uint32_t K = 0, tpl_rows = 0, tpl_stride = 0;
-    uint32_t dtw_u = 0, dtw_lds = 0, dtw_tie_g = 0, dtw_kc = 0;  // k_dtw_lds geometry for this store (0 = generic kernel)
+    DtwPlan plan;                  // which DTW kernel serves this store, in what shape (plan_dtw, when the store is set)
     uint32_t dp_lanes = 0;         // sr_set_dp_lanes: lanes per pair of the opt-in full-DP scorer (0 = default)
-    uint32_t cells_points = 0;     // most band points of any pair of this store (k_dtw_cells' LDS; 0 = not usable)
-    std::vector<uint32_t> cells_by_len;  // ... per template length, computed once (dtw_cells_max_points)
+    std::vector<uint32_t> cells_by_len;  // most band points per template length, computed once (dtw_cells_max_points)
     int small_launch = 0;          // sr_set_small_launch: 0 = automatic (k_dtw_cells for a few hundred pairs, k_dtw_quad up to two rounds of the chip), 1 = never, 2 / 3 = k_dtw_cells / k_dtw_quad whenever it fits
     // scratch used when the caller does not ask for an intermediate (or passes host buffers)
     DevBuf<uint16_t> s_pcm;
@@ -125,12 +125,11 @@ struct sr_engine {
     // The counters are hidden per-engine state shared by every launch: two small calls in flight on DIFFERENT caller streams
     // would both count in them.  They therefore belong to one caller stream at a time (internal chunk streams are forked from /
     // joined to it, so its order covers them); a call on any other stream leaves the slot scan to k_argmin -- unless the last
-    // launch that used the counters has COMPLETED (ev_cells, recorded behind every such launch): then nothing is in flight in
-    // them and the calling stream becomes the owner (round 6; before, the first stream kept them for the engine's lifetime,
-    // e.g. the internal stream of a first host-buffer call, or a stream the caller had destroyed since).
+    // call that used the counters has COMPLETED: ev_cells is recorded on that call's caller-level stream after its join, so it
+    // covers every chunk, and once it has completed nothing counts in them and the calling stream becomes the owner.
     hipStream_t cells_owner = nullptr;
     bool cells_owner_set = false;
-    hipEvent_t ev_cells = nullptr;
+    hipEvent_t ev_cells = nullptr;  // created with s_pcnt (sr_create)
     // An asynchronous *_dev call that was handed no buffer for an intermediate uses the engine's scratch (s_vad, s_mfcc,
     // s_scores, s_vad2) on the CALLER's stream.  The event marks the end of the last such call; the host-buffer entry points,
     // which reuse the same scratch on internal or the null stream, order their stream behind it first (order_after_scratch_users).
@@ -174,4 +173,5 @@ VadArgs vad_args(const sr_engine *h, const uint16_t *pcm, uint64_t stride, uint3
 MfccArgs mfcc_args(const sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B, const sr_vad_rec *d_vad, int16_t *d_mfcc);
 DtwArgs dtw_args(const sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_vad, const uint32_t *d_in_frames, uint32_t B,
                      uint32_t *d_scores, sr_result *d_results);
+void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid);
 bool launch_dtw_auto(sr_engine *h, DtwArgs &a, uint32_t b0, hipStream_t s, hipStream_t owner);

@@ -440,7 +440,8 @@ int sr_dtw_batch(sr_engine *h, const int16_t *in_mfcc, const uint32_t *in_frames
         pc.upload(h->s_mfcc.p, in_mfcc, msz * 2);
         pc.upload(h->s_u32a.p, in_frames, (size_t)B * 4);
         DtwArgs a = dtw_args(h, h->s_mfcc.p, nullptr, h->s_u32a.p, B, h->s_scores.p, h->s_results.p);
-        if (!launch_dtw_auto(h, a, 0, pc.stream(), pc.stream())) launch_argmin(a, pc.stream());
+        if (launch_dtw_auto(h, a, 0, pc.stream(), pc.stream())) (void)hipEventRecord(h->ev_cells, pc.stream());
+        else launch_argmin(a, pc.stream());
         const hipError_t le = hipGetLastError();
         const uint8_t *sc_back = pc.download(h->s_scores.p, sc_bytes);
         const uint8_t *res_back = results ? pc.download(h->s_results.p, res_bytes) : nullptr;
@@ -453,7 +454,8 @@ int sr_dtw_batch(sr_engine *h, const int16_t *in_mfcc, const uint32_t *in_frames
     HIP_TRY(hipMemcpy(h->s_mfcc.p, in_mfcc, msz * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->s_u32a.p, in_frames, (size_t)B * 4, hipMemcpyHostToDevice));
     DtwArgs a = dtw_args(h, h->s_mfcc.p, nullptr, h->s_u32a.p, B, h->s_scores.p, h->s_results.p);
-    if (!launch_dtw_auto(h, a, 0, nullptr, nullptr)) launch_argmin(a, nullptr);
+    if (launch_dtw_auto(h, a, 0, nullptr, nullptr)) HIP_TRY(hipEventRecord(h->ev_cells, nullptr));
+    else launch_argmin(a, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(scores, h->s_scores.p, (size_t)B * h->K * 4, hipMemcpyDeviceToHost));
     if (results) HIP_TRY(hipMemcpy(results, h->s_results.p, (size_t)B * sizeof(sr_result), hipMemcpyDeviceToHost));

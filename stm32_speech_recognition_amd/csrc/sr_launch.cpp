@@ -1,7 +1,6 @@
 // Device-resident entry points of the C ABI (include/sr_engine.h): argument checks, the launch-argument blocks of the kernels,
 // and the sequencing of VAD -> frame kernel -> DTW -> slot scan on the caller's stream and the internal chunk streams.
 #include "sr_engine_internal.h"
-#include "sr_dtw_quad.h"
 
 using namespace sr;
 // ---- device-resident pipeline ---------------------------------------------------------------------
@@ -139,79 +138,77 @@ DtwArgs dtw_args(const sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_
     a.tplR = h->tplR.p;
     a.tpl_frames_s = h->tpl_frames_s.p;
     a.tpl_orig = h->tpl_orig.p;
-    a.lds_u = h->dtw_u;
-    a.lds_bytes = h->dtw_lds;
     a.tie_delta = h->dev.tie_delta;
-    a.tie_g = h->dtw_tie_g;
-    a.lds_kc = h->dtw_kc;
     a.n_coef = h->nc;
-    a.dp_lanes = h->dp_lanes;
     a.pair_count = nullptr;
-    a.cells_points = h->cells_points;
-    a.tpl_neg2_ok = h->tpl_staged_ok ? 1u : 0u;
+    a.cells_points = h->plan.cells_points;
     a.cells_literal = dev_hook(kHookCellsLiteral) != 0 ? 1u : 0u;
-    a.dev_cus = h->n_cu;
-    a.dev_lds_cu = h->lds_per_cu;
-    a.dev_lds_wg = h->lds_per_wg;
     return a;
 }
 
-// dtw for every pair of the launch: the batch kernels (k_dtw_lds / k_dtw_gen / k_dtw), or -- a few hundred pairs, i.e. a GPU
-// that would otherwise idle behind a handful of serial walks -- one workgroup per pair (k_dtw_cells).  Same scores.
-// Measured (profiles/r04_small_launch_sweep.json, profiles/experiments/RESULTS.md): 110-frame captures against 80 slots of up
-// to 119 frames: 80 / 320 / 640 / 1 280 / 2 560 / 5 120 pairs take 25 / 33 / 44 / 65 / 115 / 212 us with one workgroup per pair
-// against 126 us for the batch kernel at any of these sizes; 256-frame captures against 100 templates of 192-320 frames (the
-// benchmark's shapes): 100 / 400 pairs 60 / 107 us against 215.  A pair costs in proportion to its band (~ frames^2), the
-// batch kernel's latency grows with the frames, so the automatic mode stops at 320 000 / max_frames pairs (2 689 / 1 000).
-// Round 5: where the four-lanes-per-pair form (k_dtw_quad, below) can take over, one workgroup per pair only pays up to
-// 120 000 / max_frames pairs (1 008 / 375): 640 / 1 280 / 2 560 pairs take 44 / 65 / 114 us against a flat 49 us there.
-static uint64_t small_launch_pairs(const DtwArgs &a) { return (dtw_quad_fits(a) ? 120000u : 320000u) / (a.max_frames > 64 ? a.max_frames : 64u); }
-// returns true when the slot scan (argmin) has been done as well: k_dtw_cells with result records asked for and the utterances
-// b0 .. b0 + B of the call within the counters
-// Mid-sized launches: four lanes per pair (k_dtw_quad.hip).  Its workgroups hold PU x PK pairs with both sequences in LDS; a
-// "round" is what the chip holds at once (workgroups per CU by LDS, at most 8, x 256 CUs).  The batch kernel's time is flat up
-// to ~400 000 pairs (126 us at the firmware's shapes), a round of the quad kernel takes a third of that, so the automatic mode
-// hands it launches of up to two rounds (profiles/r05_small_launch_sweep.json).
-static uint64_t quad_launch_pairs(const sr_engine *h, const DtwArgs &a)
+// The DTW plan of the store just set (h->K, tpl_rows, tpl_staged_ok are its): which kernel serves how many pairs, in what shape.
+void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid)
 {
-    uint32_t pu = 0, pk = 0;
-    size_t lds = 0;
-    if (!dtw_quad_pick(a, &pu, &pk, &lds)) return 0;
-    const uint64_t granules = (uint64_t)h->lds_per_cu / 1280;  // gfx950 hands out LDS in granules of 1 280 bytes (128 per CU on MI355X)
-    const uint64_t per_cu = std::min<uint64_t>(8, granules / ((lds + 1279) / 1280));
-    return 2 * (uint64_t)h->n_cu * per_cu * pu * pk;
+    DtwPlan p;
+    const LdsBudget &lds = h->lds;
+    const uint32_t K = h->K, R = h->cfg.max_frames, rows = h->tpl_rows, nc = h->nc;
+    // the batch kernel: k_dtw_lds where the store can be staged, else k_dtw_gen / k_dtw
+    if (h->tpl_staged_ok) p.lds_u = dtw_lds_pick_u(K, R, lds, &p.lds_bytes, &p.lds_tie_g, &p.lds_kc, nc > (uint32_t)kCoef ? 8u : 6u);
+    if (dev_hook(kHookDtwDebug))
+        std::fprintf(stderr, "sr_engine: k_dtw_lds geometry for K = %u, %u rows: U = %u, Kc = %u, tie table %u, LDS %u bytes\n", K, R,
+                     p.lds_u, p.lds_kc, p.lds_tie_g, p.lds_bytes);
+    // k_dtw_cells: the most band points any pair of this store can have (one word per point in LDS) -- capped at what a
+    // workgroup's LDS holds beside the rows: a pair with more points than that (utterances near the frame cap against the
+    // longest templates) is walked literally by its workgroup, which costs what the batch kernel costs
+    p.cells_points = dtw_cells_max_points(R, frames, valid, K, h->cells_by_len);
+    const size_t fixed = dtw_cells_lds(R, rows, 0), room = fixed < lds.stage_cap ? (lds.stage_cap - fixed) / sizeof(uint32_t) : 0;
+    if (p.cells_points > room) p.cells_points = room >= 4096 ? (uint32_t)room : 0u;
+    // two rows per sequence at least (the do-while of DTW.C:150-188 reads row 1 even of 1-frame sequences); the jump over two
+    // steps must fit 11 bits; one workgroup's LDS
+    const size_t cells = dtw_cells_lds(R, rows, p.cells_points);
+    if (p.cells_points && R >= 2 && rows >= 2 && rows <= 1023 && nc >= 1 && nc <= 16 && cells <= lds.stage_cap) p.cells_bytes = (uint32_t)cells;
+    (void)dtw_quad_pick(K, R, rows, nc, lds, &p.quad_pu, &p.quad_pk, &p.quad_bytes);  // (writes nothing when nothing fits)
+    p.quad_neg2 = h->tpl_staged_ok;
+    // The automatic mode.  Measured (profiles/r04_small_launch_sweep.json, profiles/experiments/RESULTS.md): 110-frame captures
+    // against 80 slots of up to 119 frames: 80 / 320 / 640 / 1 280 / 2 560 / 5 120 pairs take 25 / 33 / 44 / 65 / 115 / 212 us
+    // with one workgroup per pair against 126 us for the batch kernel at any of these sizes; 256-frame captures against 100
+    // templates of 192-320 frames (the benchmark's shapes): 100 / 400 pairs 60 / 107 us against 215.  A pair costs in
+    // proportion to its band (~ frames^2), the batch kernel's latency grows with the frames, so k_dtw_cells takes launches of up
+    // to 320 000 / max_frames pairs (2 689 / 1 000).  Round 5: where k_dtw_quad can take over, one workgroup per pair only
+    // pays up to 120 000 / max_frames pairs (1 008 / 375): 640 / 1 280 / 2 560 pairs take 44 / 65 / 114 us against a flat
+    // 49 us there.
+    if (p.cells_bytes) p.cells_pairs = (p.quad_pu ? 120000u : 320000u) / std::max(R, 64u);
+    // k_dtw_quad: a "round" is what the chip holds at once (workgroups per CU by LDS, at most 8, x the CUs).  The batch kernel's
+    // time is flat up to ~400 000 pairs (126 us at the firmware's shapes), a round of the quad kernel takes a third of that, so
+    // the automatic mode hands it launches of up to two rounds (profiles/r05_small_launch_sweep.json).
+    if (p.quad_pu) p.quad_pairs = 2 * (uint64_t)h->n_cu * std::min(8u, lds.wgs_per_cu(p.quad_bytes)) * p.quad_pu * p.quad_pk;
+    h->plan = p;
 }
-// `owner` = the caller-level stream of the call (the counters belong to one caller stream, see sr_engine::cells_owner)
+
+// dtw for every pair of the launch in the form the plan and sr_set_small_launch choose.  true: k_dtw_cells counted in the
+// pair counters and did the slot scan; the caller records ev_cells on `owner`, its caller-level stream, after its join
 bool launch_dtw_auto(sr_engine *h, DtwArgs &a, uint32_t b0, hipStream_t s, hipStream_t owner)
 {
+    const DtwPlan &p = h->plan;
     const uint64_t pairs = (uint64_t)a.B * a.K;
-    if (h->small_launch != 1 && h->small_launch != 3 && dtw_cells_fits(a) && (h->small_launch == 2 || pairs <= small_launch_pairs(a))) {
+    const int mode = h->small_launch;
+    if (p.cells_bytes && (mode == 2 || (mode == 0 && pairs <= p.cells_pairs))) {
         bool counters = a.results && (uint64_t)b0 + a.B <= kPairCounters;
         if (counters) {
-            if (!h->ev_cells && hipEventCreateWithFlags(&h->ev_cells, hipEventDisableTiming) != hipSuccess) {
-                (void)hipGetLastError();
-                h->ev_cells = nullptr;
-            }
-            // another stream may take the counters over once the last launch that used them is done (nothing counts in them then)
-            if (h->cells_owner_set && h->cells_owner != owner && h->ev_cells && hipEventQuery(h->ev_cells) == hipSuccess)
-                h->cells_owner_set = false;
-            (void)hipGetLastError();  // hipErrorNotReady of the query is not an error of this call
-            if (!h->cells_owner_set) {
+            // another stream may take the counters over once the last call that used them is done (nothing counts in them then)
+            if (!h->cells_owner_set || (h->cells_owner != owner && hipEventQuery(h->ev_cells) == hipSuccess)) {
                 h->cells_owner = owner;
                 h->cells_owner_set = true;
             }
-            counters = h->cells_owner == owner && h->ev_cells != nullptr;
+            (void)hipGetLastError();  // hipErrorNotReady of the query is not an error of this call
+            counters = h->cells_owner == owner;
         }
         a.pair_count = counters ? h->s_pcnt.p + b0 : nullptr;
-        launch_dtw_cells(a, s);
-        if (a.pair_count) (void)hipEventRecord(h->ev_cells, s);
-        return a.pair_count != nullptr;
+        launch_dtw_cells(a, p, s);
+        return counters;
     }
-    if ((h->small_launch == 3 && dtw_quad_fits(a)) || (h->small_launch == 0 && pairs <= quad_launch_pairs(h, a))) {
-        launch_dtw_quad(a, s);
-        return false;
-    }
-    launch_dtw(a, s);
+    if (p.quad_pu && (mode == 3 || (mode == 0 && pairs <= p.quad_pairs))) launch_dtw_quad(a, p, s);
+    else launch_dtw(a, p, s);
     return false;
 }
 
@@ -222,7 +219,8 @@ int sr_dtw_batch_dev(sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_va
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
     ENTER_DEVICE(h);
     DtwArgs a = dtw_args(h, d_mfcc, d_vad, nullptr, B, d_scores, d_results);
-    if (!launch_dtw_auto(h, a, 0, (hipStream_t)stream, (hipStream_t)stream) && d_results) launch_argmin(a, (hipStream_t)stream);
+    if (launch_dtw_auto(h, a, 0, (hipStream_t)stream, (hipStream_t)stream)) HIP_TRY(hipEventRecord(h->ev_cells, (hipStream_t)stream));
+    else if (d_results) launch_argmin(a, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SR_OK;
 }
@@ -281,6 +279,7 @@ int sr_recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_str
     }
     const uint32_t per = (B + n_chunks - 1) / n_chunks;
     uint32_t c = 0;
+    bool counted = false;
     for (uint32_t b0 = 0; b0 < B; b0 += per, c++) {
         const uint32_t n = std::min(per, B - b0);
         hipStream_t sc = (n_chunks == 1) ? s : h->st_pipe[c % n_streams];
@@ -296,6 +295,7 @@ int sr_recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_str
         if (prof) HIP_TRY(hipEventRecord(ev[2], sc));
         DtwArgs da = dtw_args(h, mc, vc, nullptr, n, d_scores + (size_t)b0 * h->K, d_results + b0);
         const bool scanned = launch_dtw_auto(h, da, b0, sc, s);
+        counted |= scanned;
         if (prof) HIP_TRY(hipEventRecord(ev[3], sc));
         if (!scanned) launch_argmin(da, sc);
         if (prof) HIP_TRY(hipEventRecord(ev[4], sc));
@@ -306,6 +306,7 @@ int sr_recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_str
             HIP_TRY(hipStreamWaitEvent(s, h->ev_join[i], 0));  // the caller's stream continues after every chunk
         }
     }
+    if (counted) HIP_TRY(hipEventRecord(h->ev_cells, s));  // after the join: covers the counting of every chunk
     if (prof) {
         HIP_TRY(hipEventRecord(h->ev_call[2 * h->calls_used + 1], s));
         h->ev_used += c;
@@ -343,13 +344,16 @@ int sr_recognize_segments_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_
     }
     VadArgs va = vad_args(h, d_pcm, pcm_stride, buf_len, h->noise_len, B, d_vad);
     launch_vad(va, s);
+    bool counted = false;
     for (uint32_t sg = 0; sg < h->cfg.max_seg; sg++) {
         launch_select_segment(d_vad, h->s_vad2.p, B, sg, h->cfg.max_frames, h->frame_len, h->hop, s);
         launch_mfcc(mfcc_args(h, d_pcm, pcm_stride, B, h->s_vad2.p, h->s_mfcc.p), s);
         DtwArgs da = dtw_args(h, h->s_mfcc.p, h->s_vad2.p, nullptr, B, d_scores + (size_t)sg * B * h->K,
                               d_results + (size_t)sg * B);
-        if (!launch_dtw_auto(h, da, 0, s, s)) launch_argmin(da, s);
+        if (launch_dtw_auto(h, da, 0, s, s)) counted = true;
+        else launch_argmin(da, s);
     }
+    if (counted) HIP_TRY(hipEventRecord(h->ev_cells, s));
     HIP_TRY(hipGetLastError());
     return mark_scratch_user(h, s);
 }
@@ -363,11 +367,11 @@ int sr_dtw_dp_batch_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_i
     if (!h || !d_mfcc || !d_scores || (!d_in_frames && !d_vad)) return fail(SR_ERR_BAD_ARG, "null argument");
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
     if (h->nc != (uint32_t)kCoef) return fail(SR_ERR_BAD_CONFIG, "the full-DP scorer is built for 12-coefficient records");
-    if ((size_t)h->tpl_rows * 48 > 150 * 1024) return fail(SR_ERR_BAD_ARG, "templates too long for the LDS-staged DP kernel");
+    if ((size_t)h->tpl_rows * 48 > h->lds.stage_cap) return fail(SR_ERR_BAD_ARG, "templates too long for the LDS-staged DP kernel");
     ENTER_DEVICE(h);
     DtwArgs a = dtw_args(h, d_mfcc, d_vad, d_in_frames, B, d_scores, nullptr);
     if (!h->tpl_staged_ok) a.tplR = nullptr;  // coefficients beyond +-16383: the band kernel's -2*coef rows do not hold them
-    launch_dtw_dp(a, (hipStream_t)stream);
+    launch_dtw_dp(a, h->dp_lanes, h->lds, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SR_OK;
 }
