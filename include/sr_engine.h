@@ -207,6 +207,26 @@ int sr_mfcc_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32
 int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                          const int32_t *start, const int32_t *end, const uint32_t *mid, int16_t *mfcc, uint32_t *frm_num,
                          uint32_t *status);
+/* Per-frame intermediate values of get_mfcc for segment 0, emitted by the same frame kernels at the point where each value
+ * exists (no second transform): feat[b][max_frames][width], frame-major, rows >= frm_num (and every row of a failed record)
+ * zeroed.  Widths (sr_frame_feature_width): reference front end 512 / 512 / 24 / 24, extension 256 / 256 / 40 / 40,
+ * GENERIC nfft/2 for the two spectrum kinds and n_mel for the two Mel kinds; 0 for an unknown kind.
+ * The extension front end's FFT words are its 512-point transform's bins (oracle/q15_fft.c), not cr4_fft_1024_stm32's.
+ * LOGMEL of a Mel energy of 0 is 0 (log(0) = -inf; the cast gives 0 on the firmware's and common hosts' compilers). */
+#define SR_FEAT_FFT 1    /* u32 x nfft/2: packed (re low16, im high16) words of cr4_fft_1024_stm32's output, bins 0..nfft/2-1 */
+#define SR_FEAT_MAG 2    /* u32 x nfft/2: |X|*10 exactly as fft() returns it (MFCC.C:49-60) */
+#define SR_FEAT_MEL 3    /* u32 x n_mel:  pow_spct before the log, u32-wrapping terms (MFCC.C:128-162) */
+#define SR_FEAT_LOGMEL 4 /* u32 x n_mel:  (u32)(log(pow_spct)*100) as the DCT consumes it (MFCC.C:165-170) */
+uint32_t sr_frame_feature_width(const sr_engine *h, int kind);
+/* DEVICE buffers, same inputs and alignment rules as sr_mfcc_batch_dev; d_mfcc (may be NULL) receives the MFCC rows of the
+ * same launch, identical to sr_mfcc_batch_dev's.  Asynchronous on `stream`. */
+int sr_frame_features_batch_dev(sr_engine *h, int kind, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B,
+                                const sr_vad_rec *d_vad, uint32_t *d_feat, int16_t *d_mfcc, void *stream);
+/* HOST buffers, same inputs and per-record failure semantics as sr_mfcc_batch_status (frm_num, status; a failed record
+ * has all-zero feature rows); mfcc and status may be NULL. */
+int sr_frame_features_batch(sr_engine *h, int kind, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                            const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t *feat, int16_t *mfcc,
+                            uint32_t *frm_num, uint32_t *status);
 /* all-pairs greedy DTW of B feature sequences (in_mfcc[b*max_frames*n_coef], in_frames[b]) against the store */
 int sr_dtw_batch(sr_engine *h, const int16_t *in_mfcc, const uint32_t *in_frames, uint32_t B, uint32_t *scores,
                  sr_result *results);

@@ -31,9 +31,14 @@ constexpr int kMelPad = kMel + 1;
 __device__ __forceinline__ constexpr int mel_chunk_word(int j) { return 256 * ((j >> 2) & 1) + 4 * ((j >> 3) ^ (4 * ((j >> 2) & 1))) + (j & 3); }
 constexpr int mfcc_wave_lds_words(int fpw) { return kXchgWords + fpw * kMelPad + 64; }
 
-template <int kFPW>
-__global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
+// Args = MfccArgs: the frame kernel.  Args = MfccFeatArgs<kind>: the same kernel, which also stores one intermediate value
+// per frame into a.feat[b][max_frames][width] at the point where it exists (sr_frame_features_batch_dev).  Every feature
+// store sits under `if constexpr`, so k_mfcc<kFPW, MfccArgs> compiles to the instructions it had before the parameter existed.
+template <int kFPW, typename Args = MfccArgs>
+__global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 {
+    constexpr int kFeat = mfcc_feat_kind<Args>;
+    constexpr uint32_t kFeatW = (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) ? kBins : kMel;  // feature words per frame
     constexpr int kWaveLdsWords = mfcc_wave_lds_words(kFPW);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_dctM[kCoef * kMelPad];
@@ -153,6 +158,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
         const uint16_t *row = a.pcm + (uint64_t)b * a.pcm_stride;
         int16_t *out = a.mfcc + (uint64_t)b * a.max_frames * kCoef;
         const uint32_t f0 = tile * (kMfccWaves * kFPW) + w * kFPW;
+        uint32_t *frow = nullptr;  // feature rows of utterance b
+        if constexpr (kFeat != 0) frow = a.feat + (uint64_t)b * a.max_frames * kFeatW;
         uint32_t nf = 0;  // frames this wave really has
         if (f0 < nfrm) nf = (nfrm - f0 < (uint32_t)kFPW) ? nfrm - f0 : (uint32_t)kFPW;
 
@@ -202,6 +209,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
             for (int e3 = 0; e3 < 4; e3++) {
                 bfly_pk<true>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
                               k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
+                if constexpr (kFeat == SR_FEAT_FFT) {  // x[j], x[j + 256] as the asm stores them: bins lane + 64 e3 (+ 256)
+                    uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
+                    fr[0] = u[e3][0];
+                    fr[256] = u[e3][1];
+                }
                 nn[2 * e3] = (uint32_t)sdot2z(u[e3][0], u[e3][0]);
                 nn[2 * e3 + 1] = (uint32_t)sdot2z(u[e3][1], u[e3][1]);
             }
@@ -241,6 +253,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
                     const f32x2 m = f32x2{__builtin_amdgcn_sqrtf((float)(int)nn[2 * e3]), __builtin_amdgcn_sqrtf((float)(int)nn[2 * e3 + 1])} *
                                     f32x2{10.0f, 10.0f};
                     const uint32_t m0 = cvt_u32(m.x), m1 = cvt_u32(m.y);
+                    if constexpr (kFeat == SR_FEAT_MAG) {  // the QUIET / MID tiers' magnitudes
+                        uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
+                        fr[0] = m0;
+                        fr[256] = m1;
+                    }
                     eb[kEs * e3] = umul24(m0, m0);
                     eb[kEs * e3 + kEh] = umul24(m1, m1);
                 }
@@ -250,6 +267,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
                     // both bins' roots and the x10 in packed f32 operations (plain IEEE multiplies and fused multiply-adds, see sqrt_rn_int)
                     const f32x2 m = sqrt_rn_int2(f32x2{(float)(int)nn[2 * e3], (float)(int)nn[2 * e3 + 1]}) * f32x2{10.0f, 10.0f};
                     const uint32_t m0 = cvt_u32(m.x), m1 = cvt_u32(m.y);  // < 2^19
+                    if constexpr (kFeat == SR_FEAT_MAG) {  // the LOUD tier's
+                        uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
+                        fr[0] = m0;
+                        fr[256] = m1;
+                    }
                     eb[kEs * e3] = umul24(m0, m0);
                     eb[kEs * e3 + kEh] = umul24(m1, m1);
                 }
@@ -307,6 +329,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
                 const uint32_t *X = (lane & 1) ? moff : buf + 2 * kBins;
                 const uint32_t hi = buf[p_hi] + X[x_hi], lo = f_lo ? buf[p_lo] + X[x_lo] : 0u;
                 powb[fi * kMelPad + lane] = hi - lo;
+                if constexpr (kFeat == SR_FEAT_MEL) frow[(f0 + fi) * kFeatW + lane] = hi - lo;
             }
             wave_sync();
         }
@@ -334,6 +357,13 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
             }
         }
         wave_sync();
+        if constexpr (kFeat == SR_FEAT_LOGMEL) {  // the log stage's outputs as the DCT reads them, un-shifted: word t = fi*24 + h
+            uint32_t *fw = frow + f0 * kFeatW;
+            for (uint32_t t = lane; t < nf * kFeatW; t += 64) {
+                const uint32_t fi = t / kFeatW, h = t - fi * kFeatW;
+                fw[t] = powb[fi * kMelPad + h] >> 14;
+            }
+        }
         // output t = fi*12 + h of the wave's tile goes to out[(f0 + fi)*12 + h] = out_w[t]: consecutive lanes store
         // consecutive s16; fi = t / 12 by a 24-bit multiply (exact for t < 2^13), all index arithmetic in 32 bits
         // (left to the compiler the 64-bit subscript became eight v_mad_u64_u32 per round)
@@ -358,6 +388,10 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
             const uint32_t r0 = f0 + nf, r1 = (f0 + kFPW < a.max_frames) ? f0 + kFPW : a.max_frames;
             for (uint32_t t = r0 * kCoef + lane; t < r1 * kCoef && r0 < r1; t += 64) out[t] = 0;
         }
+        if constexpr (kFeat != 0) {  // feature rows >= frm_num of this tile, likewise
+            const uint32_t r0 = f0 + nf, r1 = (f0 + kFPW < a.max_frames) ? f0 + kFPW : a.max_frames;
+            for (uint32_t t = r0 * kFeatW + lane; t < r1 * kFeatW && r0 < r1; t += 64) frow[t] = 0;
+        }
     }
 }
 
@@ -365,6 +399,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const MfccArgs a)
 uint32_t mfcc_ext_frames_per_tile();
 int mfcc_ext_occupancy(int *per_cu);
 void launch_mfcc_ext(const MfccArgs &a, uint32_t grid, hipStream_t s);
+void launch_mfcc_ext_features(const MfccArgs &a, int kind, uint32_t *feat, uint32_t grid, hipStream_t s);
 
 uint32_t mfcc_frames_per_tile(uint32_t frame_len) { return frame_len == 320 ? mfcc_ext_frames_per_tile() : (uint32_t)(kMfccWaves * kFramesPerWave); }
 // frames per work item of the underfilled-launch forms, 0 = mid, 1 = small (the extension kernel has one form)
@@ -415,6 +450,44 @@ void launch_mfcc(const MfccArgs &a, hipStream_t s)
     }
     const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWave) * sizeof(uint32_t);
     hipLaunchKernelGGL(k_mfcc<kFramesPerWave>, dim3(grid), dim3(64 * kMfccWaves), lds, s, a);
+}
+
+template <int kFPW, int kKind>
+static void launch_mfcc_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
+{
+    const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFPW) * sizeof(uint32_t);
+    hipLaunchKernelGGL((k_mfcc<kFPW, MfccFeatArgs<kKind>>), dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_feat_args<kKind>(a, feat));
+}
+template <int kFPW>
+static void launch_mfcc_feat_form(const MfccArgs &a, int kind, uint32_t *feat, uint32_t grid, hipStream_t s)
+{
+    switch (kind) {
+    case SR_FEAT_FFT: launch_mfcc_feat_kind<kFPW, SR_FEAT_FFT>(a, feat, grid, s); break;
+    case SR_FEAT_MAG: launch_mfcc_feat_kind<kFPW, SR_FEAT_MAG>(a, feat, grid, s); break;
+    case SR_FEAT_MEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_MEL>(a, feat, grid, s); break;
+    case SR_FEAT_LOGMEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_LOGMEL>(a, feat, grid, s); break;
+    default: break;  // (kinds are checked by the entry point)
+    }
+}
+
+// the feature kernels in the form and grid launch_mfcc would pick for the same arguments
+void launch_mfcc_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s)
+{
+    if (a.generic) {
+        launch_mfcc_gen_features(a, kind, feat, s);
+        return;
+    }
+    if (a.n_items == 0) return;
+    const uint32_t cap = a.grid_cap ? a.grid_cap : 4096u;
+    const uint32_t grid = a.n_items < cap ? a.n_items : cap;
+    if (a.frame_len == 320)
+        launch_mfcc_ext_features(a, kind, feat, grid, s);
+    else if (a.small_tiles == 2)
+        launch_mfcc_feat_form<kFramesPerWaveSmall>(a, kind, feat, grid, s);
+    else if (a.small_tiles == 1)
+        launch_mfcc_feat_form<kFramesPerWaveMid>(a, kind, feat, grid, s);
+    else
+        launch_mfcc_feat_form<kFramesPerWave>(a, kind, feat, grid, s);
 }
 
 }  // namespace sr

@@ -51,9 +51,17 @@ __device__ __forceinline__ uint32_t row_scan_incl(uint32_t v)
 // LDS per CU): mean waves per SIMD 2.74 -> 3.43, but the kernel alone stayed at 14.5 ms (its waits are the texture
 // addresser's, not latency that more waves would hide) and the pipelined step got SLOWER (51.5 vs 50.6 ms) because the
 // two workgroups took the whole LDS of a CU and the DTW workgroups of the other streams could no longer co-reside.
-__global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs a)
+// Args = MfccFeatArgs<kind>: also the per-frame intermediate values (see k_mfcc; every feature store under `if constexpr`).
+// The two spectrum kinds store 16 words per lane and frame from inside the radix-2 pass, where the kernel already sits at the
+// 168-VGPR limit of three waves per SIMD: they are built for two (no scratch); every other instantiation keeps three.
+template <typename Args>
+constexpr int mfcc_ext_waves_per_simd = (mfcc_feat_kind<Args> == SR_FEAT_FFT || mfcc_feat_kind<Args> == SR_FEAT_MAG) ? 2 : 3;
+template <typename Args = MfccArgs>
+__global__ void __launch_bounds__(64 * ext::kWaves, mfcc_ext_waves_per_simd<Args>) k_mfcc_ext(const Args a)
 {
     using namespace ext;
+    constexpr int kFeat = mfcc_feat_kind<Args>;
+    constexpr uint32_t kFeatW = (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) ? kBinsE : kMelE;  // feature words per frame
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_dctM[kCoef * kMelEPad];  // same exact-division-by-100 device as k_mfcc (see there)
     __shared__ int s_dctS[kCoef * kMelEPad];
@@ -204,6 +212,8 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
         int16_t *out = a.mfcc + (uint64_t)b * a.max_frames * kCoef;
         const uint32_t f0 = tile * kTile + w * kFpw;
         const uint32_t nf = cur.nf;
+        uint32_t *frow = nullptr;  // feature rows of utterance b
+        if constexpr (kFeat != 0) frow = a.feat + (uint64_t)b * a.max_frames * kFeatW;
         const int mid = cur.mid;
 
         for (uint32_t fb = 0; fb < nf; fb += kGrp) {
@@ -292,6 +302,8 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
             }
             wave_sync();  // the exchange image has been consumed by every lane: reuse it for the energies
             // ---- radix-2 pass for bins k = gl + 16 m < 256, |X|*10, energy
+            uint32_t *fl = nullptr;  // bin gl of this lane's frame in the feature rows (bins gl + 16 m at immediate offsets)
+            if constexpr (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) fl = frow + (f0 + (live ? fi : 0u)) * kFeatW + gl;
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const u32x4 wq = s_w512[c * 16 + gl];
@@ -307,10 +319,19 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
                     const int t_re = (int)(((uint32_t)((int)(e << 16) >> 1)) + ((uint32_t)pr << 1));
                     const int t_im = (int)(((uint32_t)((int)(e & 0xFFFF0000u) >> 1)) + ((uint32_t)pi << 1));
                     const uint32_t xk = pk_hi16(t_re, t_im);  // (re, im) of X[k] as stored 16-bit values
+                    if constexpr (kFeat == SR_FEAT_FFT) {
+                        if (live) fl[16 * m] = xk;
+                    }
                     nrm[h2] = (float)sdot2z(xk, xk);
                 }
                 const f32x2 mg = sqrt_rn_int2(f32x2{nrm[0], nrm[1]}) * f32x2{10.0f, 10.0f};
                 const uint32_t mag0 = cvt_u32(mg.x), mag1 = cvt_u32(mg.y);
+                if constexpr (kFeat == SR_FEAT_MAG) {
+                    if (live) {
+                        fl[16 * (2 * c)] = mag0;
+                        fl[16 * (2 * c + 1)] = mag1;
+                    }
+                }
                 xb[g * kEStride + gl + 20 * (2 * c)] = mag0 * mag0;  // bin k = gl + 16 m at k + 4*(k >> 4)
                 xb[g * kEStride + gl + 20 * (2 * c + 1)] = mag1 * mag1;
             }
@@ -357,6 +378,9 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
                     const int f_lo = (int)(f_lohi[q] >> 16), ih = (int)(f_lohi[q] & 0xFFFFu) - 1, il = f_lo - 1;
                     const uint32_t hi = P[ih] + X[ih >> 4], lo = f_lo ? P[il] + X[il >> 4] : 0u;
                     if (live) powb[fi * kMelEPad + h] = hi - lo;
+                    if constexpr (kFeat == SR_FEAT_MEL) {
+                        if (live) frow[(f0 + fi) * kFeatW + h] = hi - lo;
+                    }
                 }
             }
             wave_sync();
@@ -380,6 +404,13 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
             }
         }
         wave_sync();
+        if constexpr (kFeat == SR_FEAT_LOGMEL) {  // the log stage's outputs as the DCT reads them, un-shifted: word t = fi*40 + h
+            uint32_t *fw = frow + f0 * kFeatW;
+            for (uint32_t t = lane; t < nf * kFeatW; t += 64) {
+                const uint32_t fi = t / kFeatW, h = t - fi * kFeatW;
+                fw[t] = powb[fi * kMelEPad + h] >> 14;
+            }
+        }
         {   // see k_mfcc: out[(f0 + fi)*12 + h] = out_w[t], 32-bit index arithmetic
             int16_t *out_w = out + (size_t)f0 * kCoef;
 #pragma unroll
@@ -400,6 +431,10 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
             const uint32_t r0 = f0 + nf, r1 = (f0 + kFpw < a.max_frames) ? f0 + kFpw : a.max_frames;
             for (uint32_t t = r0 * kCoef + lane; t < r1 * kCoef && r0 < r1; t += 64) out[t] = 0;
         }
+        if constexpr (kFeat != 0) {  // feature rows >= frm_num of this tile, likewise
+            const uint32_t r0 = f0 + nf, r1 = (f0 + kFpw < a.max_frames) ? f0 + kFpw : a.max_frames;
+            for (uint32_t t = r0 * kFeatW + lane; t < r1 * kFeatW && r0 < r1; t += 64) frow[t] = 0;
+        }
         cur = nx1;
         nx1 = nx2;
         nx2 = item_info(item + 3 * gridDim.x);
@@ -409,13 +444,29 @@ __global__ void __launch_bounds__(64 * ext::kWaves, 3) k_mfcc_ext(const MfccArgs
 uint32_t mfcc_ext_frames_per_tile() { return (uint32_t)ext::kTile; }
 int mfcc_ext_occupancy(int *per_cu)
 {
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_mfcc_ext, 64 * ext::kWaves,
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_mfcc_ext<MfccArgs>, 64 * ext::kWaves,
                                                              (size_t)ext::kWaves * ext::kWaveWords * sizeof(uint32_t));
 }
 void launch_mfcc_ext(const MfccArgs &a, uint32_t grid, hipStream_t s)
 {
     const size_t lds = (size_t)ext::kWaves * ext::kWaveWords * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_mfcc_ext, dim3(grid), dim3(64 * ext::kWaves), lds, s, a);
+    hipLaunchKernelGGL(k_mfcc_ext<MfccArgs>, dim3(grid), dim3(64 * ext::kWaves), lds, s, a);
+}
+template <int kKind>
+static void launch_mfcc_ext_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
+{
+    const size_t lds = (size_t)ext::kWaves * ext::kWaveWords * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_mfcc_ext<MfccFeatArgs<kKind>>, dim3(grid), dim3(64 * ext::kWaves), lds, s, mfcc_feat_args<kKind>(a, feat));
+}
+void launch_mfcc_ext_features(const MfccArgs &a, int kind, uint32_t *feat, uint32_t grid, hipStream_t s)
+{
+    switch (kind) {
+    case SR_FEAT_FFT: launch_mfcc_ext_feat_kind<SR_FEAT_FFT>(a, feat, grid, s); break;
+    case SR_FEAT_MAG: launch_mfcc_ext_feat_kind<SR_FEAT_MAG>(a, feat, grid, s); break;
+    case SR_FEAT_MEL: launch_mfcc_ext_feat_kind<SR_FEAT_MEL>(a, feat, grid, s); break;
+    case SR_FEAT_LOGMEL: launch_mfcc_ext_feat_kind<SR_FEAT_LOGMEL>(a, feat, grid, s); break;
+    default: break;  // (kinds are checked by the entry point)
+    }
 }
 
 }  // namespace sr

@@ -71,8 +71,11 @@ __device__ __forceinline__ void fft_real_half(const uint32_t *__restrict__ in, u
     }
 }
 
-__global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const MfccArgs a)
+// Args = MfccFeatArgs<kind>: also the per-frame intermediate values (see k_mfcc; every feature store under `if constexpr`)
+template <typename Args = MfccArgs>
+__global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const Args a)
 {
+    constexpr int kFeat = mfcc_feat_kind<Args>;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t *fin = smem + (size_t)w * kGenWaveWords, *fout = fin + kNfft, *buf = fout + kNfft, *en = buf + kXchgWords,
@@ -101,8 +104,13 @@ __global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const MfccArgs a)
         const uint32_t b = (uint32_t)(item / a.max_frames), f = (uint32_t)(item - (uint64_t)b * a.max_frames);
         const sr_vad_rec *rec = a.vad + b;
         int16_t *out = a.mfcc + ((uint64_t)b * a.max_frames + f) * nc;
+        const uint32_t feat_w = (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) ? (uint32_t)kBins : nm;  // feature words per frame
+        uint32_t *frow = nullptr;  // this frame's feature row
+        if constexpr (kFeat != 0) frow = a.feat + ((uint64_t)b * a.max_frames + f) * feat_w;
         if (f >= rec->frm_num) {  // rows >= frm_num are zero so that every row of the output is defined
             if ((uint32_t)lane < nc) out[lane] = 0;
+            if constexpr (kFeat != 0)
+                for (uint32_t i = lane; i < feat_w; i += 64) frow[i] = 0;
             continue;
         }
         const int mid = (int)rec->atap.mid_val;
@@ -116,6 +124,8 @@ __global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const MfccArgs a)
         wave_sync();
         fft_real_half(fin, fout, buf, lane, gtw);  // cr4_fft_1024_stm32 (.s:95-281), bins 0..511
         wave_sync();
+        if constexpr (kFeat == SR_FEAT_FFT)
+            for (uint32_t i = lane; i < (uint32_t)kBins; i += 64) frow[i] = fout[i];
         // ---- |X| * 10 and energy (MFCC.C:49-60, 128-133), u32 wrap: bins 8*lane .. 8*lane + 7 of this lane
         uint32_t e[8];
         {
@@ -125,6 +135,10 @@ __global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const MfccArgs a)
             for (int k = 0; k < 8; k += 2) {
                 const f32x2 m = sqrt_rn_int2(f32x2{(float)sdot2z(wd[k], wd[k]), (float)sdot2z(wd[k + 1], wd[k + 1])}) * f32x2{10.0f, 10.0f};
                 const uint32_t m0 = cvt_u32(m.x), m1 = cvt_u32(m.y);
+                if constexpr (kFeat == SR_FEAT_MAG) {
+                    frow[8 * lane + k] = m0;
+                    frow[8 * lane + k + 1] = m1;
+                }
                 e[k] = m0 * m0;
                 e[k + 1] = m1 * m1;
             }
@@ -151,6 +165,8 @@ __global__ void __launch_bounds__(64 * kGenWaves) k_mfcc_gen(const MfccArgs a)
             const uint32_t *Pp = fout + ((lane & 1) ? kBins : 0);
             const uint32_t hi = Pp[f_hi - 1], lo = f_lo ? Pp[f_lo - 1] : 0u;
             pw[lane] = log100_u32(hi - lo, a.t.log_thr);  // MFCC.C:165-170
+            if constexpr (kFeat == SR_FEAT_MEL) frow[lane] = hi - lo;
+            if constexpr (kFeat == SR_FEAT_LOGMEL) frow[lane] = pw[lane];
         }
         wave_sync();
         // ---- DCT (MFCC.C:173-183): per-term truncating / 100, s16 accumulator (= the low 16 bits of the integer sum, so
@@ -179,7 +195,27 @@ void launch_mfcc_gen(const MfccArgs &a, hipStream_t s)
     if (!n) return;
     const uint64_t wgs = (n + kGenWaves - 1) / kGenWaves;
     const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
-    hipLaunchKernelGGL(k_mfcc_gen, dim3(grid), dim3(64 * kGenWaves), (size_t)kGenWaves * kGenWaveWords * sizeof(uint32_t), s, a);
+    hipLaunchKernelGGL(k_mfcc_gen<MfccArgs>, dim3(grid), dim3(64 * kGenWaves), (size_t)kGenWaves * kGenWaveWords * sizeof(uint32_t), s, a);
+}
+template <int kKind>
+static void launch_mfcc_gen_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mfcc_gen<MfccFeatArgs<kKind>>, dim3(grid), dim3(64 * kGenWaves), (size_t)kGenWaves * kGenWaveWords * sizeof(uint32_t),
+                       s, mfcc_feat_args<kKind>(a, feat));
+}
+void launch_mfcc_gen_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s)
+{
+    const uint64_t n = (uint64_t)a.B * a.max_frames;  // the grid of launch_mfcc_gen
+    if (!n) return;
+    const uint64_t wgs = (n + kGenWaves - 1) / kGenWaves;
+    const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
+    switch (kind) {
+    case SR_FEAT_FFT: launch_mfcc_gen_feat_kind<SR_FEAT_FFT>(a, feat, grid, s); break;
+    case SR_FEAT_MAG: launch_mfcc_gen_feat_kind<SR_FEAT_MAG>(a, feat, grid, s); break;
+    case SR_FEAT_MEL: launch_mfcc_gen_feat_kind<SR_FEAT_MEL>(a, feat, grid, s); break;
+    case SR_FEAT_LOGMEL: launch_mfcc_gen_feat_kind<SR_FEAT_LOGMEL>(a, feat, grid, s); break;
+    default: break;  // (kinds are checked by the entry point)
+    }
 }
 
 }  // namespace sr

@@ -88,6 +88,26 @@ struct MfccArgs {
     DevTables t;
 };
 
+// launch arguments of the feature kernels (sr_frame_features_batch_dev): the frame kernel's block + the feature output
+// feat[B][max_frames][width], kind = SR_FEAT_*.  A separate type, so that the frame kernels' own argument block stays as it is;
+// the kernels are templates on the argument type (mfcc_feat_kind<MfccArgs> = 0: no feature stores).
+template <int kKind>
+struct MfccFeatArgs : MfccArgs {
+    uint32_t *feat;
+};
+template <typename Args>
+constexpr int mfcc_feat_kind = 0;
+template <int kKind>
+constexpr int mfcc_feat_kind<MfccFeatArgs<kKind>> = kKind;
+template <int kKind>
+inline MfccFeatArgs<kKind> mfcc_feat_args(const MfccArgs &a, uint32_t *feat)
+{
+    MfccFeatArgs<kKind> f;
+    static_cast<MfccArgs &>(f) = a;
+    f.feat = feat;
+    return f;
+}
+
 struct DtwArgs {
     const int16_t *mfcc;      // [B][max_frames][12]
     const sr_vad_rec *vad;    // frm_num / status per utterance (or NULL with in_frames)
@@ -136,6 +156,9 @@ void launch_select_segment(const sr_vad_rec *in, sr_vad_rec *out, uint32_t B, ui
                            uint32_t frame_len, uint32_t hop, hipStream_t s);
 void launch_mfcc(const MfccArgs &a, hipStream_t s);
 void launch_mfcc_gen(const MfccArgs &a, hipStream_t s);  // GENERIC front end (k_mfcc_gen.hip)
+// the same kernels' per-frame intermediate values (kind = SR_FEAT_*) into feat[B][max_frames][width], MFCC rows into a.mfcc
+void launch_mfcc_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s);
+void launch_mfcc_gen_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s);
 uint32_t mfcc_frames_per_tile(uint32_t frame_len);        // frames one work item of the frame kernel covers
 uint32_t mfcc_frames_per_tile_small(uint32_t frame_len, uint32_t which);  // ... of its forms for underfilled launches (MfccArgs::small_tiles - 1)
 uint32_t mfcc_resident_workgroups(uint32_t frame_len);  // occupancy x CUs on the current device

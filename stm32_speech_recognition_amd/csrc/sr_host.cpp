@@ -307,17 +307,11 @@ int sr_vad_debug_masks(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, u
 // Per-item failure, as get_mfcc has it (MFCC.C:102-107: a segment shorter than a frame underflows the u32 frame count,
 // which then exceeds vv_frm_max -> frm_num = 0): one bad record yields frm_num[b] = 0, an all-zero MFCC record and
 // status[b] != 0; the other records of the batch are processed.
-int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
-                         const int32_t *start, const int32_t *end, const uint32_t *mid, int16_t *mfcc, uint32_t *frm_num,
-                         uint32_t *status)
+// The per-utterance records the frame kernel consumes (what k_vad would have produced) for explicit segments.
+static int mfcc_records(const sr_engine *h, uint32_t buf_len, uint32_t B, const int32_t *start, const int32_t *end,
+                        const uint32_t *mid, uint32_t *frm_num, uint32_t *status, std::vector<sr_vad_rec> &recs)
 {
-    if (!h || !pcm || !start || !end || !mid || !mfcc) return fail(SR_ERR_BAD_ARG, "null argument");
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_DEVICE(h);
-    if (int rc_ord_ = order_after_scratch_users(h, nullptr)) return rc_ord_;  // the null stream reuses the scratch buffers
-    // build the per-utterance records the frame kernel consumes (what k_vad would have produced)
-    std::vector<sr_vad_rec> recs(B);
+    recs.resize(B);
     for (uint32_t b = 0; b < B; b++) {
         sr_vad_rec &r = recs[b];
         std::memset(&r, 0, sizeof r);
@@ -341,6 +335,20 @@ int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride,
         if (frm_num) frm_num[b] = r.frm_num;
         if (status) status[b] = r.status;
     }
+    return SR_OK;
+}
+
+int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                         const int32_t *start, const int32_t *end, const uint32_t *mid, int16_t *mfcc, uint32_t *frm_num,
+                         uint32_t *status)
+{
+    if (!h || !pcm || !start || !end || !mid || !mfcc) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (B == 0) return SR_OK;
+    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
+    ENTER_DEVICE(h);
+    if (int rc_ord_ = order_after_scratch_users(h, nullptr)) return rc_ord_;  // the null stream reuses the scratch buffers
+    std::vector<sr_vad_rec> recs;
+    if (int rc_rec = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs)) return rc_rec;
     uint64_t ds = ((uint64_t)buf_len + 7) & ~7ull;
     const size_t mbytes = (size_t)B * h->cfg.max_frames * h->nc * 2;
     int rc;
@@ -366,6 +374,38 @@ int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride,
     HIP_TRY(hipMemcpy(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec), hipMemcpyHostToDevice));
     if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
     HIP_TRY(hipMemcpy(mfcc, h->s_mfcc.p, (size_t)B * h->cfg.max_frames * h->nc * 2, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+// the frame kernels' per-frame intermediate values for explicit segments: the records of sr_mfcc_batch_status, staged like
+// its large-batch path
+int sr_frame_features_batch(sr_engine *h, int kind, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                            const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t *feat, int16_t *mfcc,
+                            uint32_t *frm_num, uint32_t *status)
+{
+    if (!h || !pcm || !start || !end || !mid || !feat) return fail(SR_ERR_BAD_ARG, "null argument");
+    const uint32_t width = sr_frame_feature_width(h, kind);
+    if (!width) return fail(SR_ERR_BAD_ARG, "unknown feature kind " + std::to_string(kind));
+    if (B == 0) return SR_OK;
+    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
+    ENTER_DEVICE(h);
+    if (int rc_ord_ = order_after_scratch_users(h, nullptr)) return rc_ord_;  // the null stream reuses the scratch buffers
+    std::vector<sr_vad_rec> recs;
+    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
+    if (rc) return rc;
+    uint64_t ds = 0;
+    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
+    if ((rc = h->s_vad.reserve(B))) return rc;
+    const size_t n_mfcc = (size_t)B * h->cfg.max_frames * h->nc, n_feat = (size_t)B * h->cfg.max_frames * width;
+    if ((rc = h->s_mfcc.reserve(n_mfcc))) return rc;
+    struct FeatBuf : DevBuf<uint32_t> {
+        ~FeatBuf() { release(); }
+    } df;
+    if ((rc = df.reserve(n_feat))) return rc;
+    HIP_TRY(hipMemcpy(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec), hipMemcpyHostToDevice));
+    if ((rc = sr_frame_features_batch_dev(h, kind, h->s_pcm.p, ds, B, h->s_vad.p, df.p, h->s_mfcc.p, nullptr))) return rc;
+    HIP_TRY(hipMemcpy(feat, df.p, n_feat * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (mfcc) HIP_TRY(hipMemcpy(mfcc, h->s_mfcc.p, n_mfcc * sizeof(int16_t), hipMemcpyDeviceToHost));
     return SR_OK;
 }
 

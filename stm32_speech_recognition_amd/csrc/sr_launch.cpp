@@ -376,6 +376,42 @@ int sr_dtw_dp_batch_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_i
     return SR_OK;
 }
 
+// per-frame intermediate values of the front end (SR_FEAT_*), emitted by the frame kernels themselves
+uint32_t sr_frame_feature_width(const sr_engine *h, int kind)
+{
+    if (!h) return 0;
+    const uint32_t bins = h->frame_len == 320 && !h->generic ? 256u : (uint32_t)kBins;  // nfft / 2: 512 except the extension front end
+    switch (kind) {
+    case SR_FEAT_FFT:
+    case SR_FEAT_MAG: return bins;
+    case SR_FEAT_MEL:
+    case SR_FEAT_LOGMEL: return h->n_mel;
+    default: return 0;
+    }
+}
+
+int sr_frame_features_batch_dev(sr_engine *h, int kind, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B,
+                                const sr_vad_rec *d_vad, uint32_t *d_feat, int16_t *d_mfcc, void *stream)
+{
+    if (!h || !d_pcm || !d_vad || !d_feat) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (!sr_frame_feature_width(h, kind)) return fail(SR_ERR_BAD_ARG, "unknown feature kind " + std::to_string(kind));
+    if (pcm_stride >= (1ull << 31)) return fail(SR_ERR_BAD_ARG, "pcm_stride must be below 2^31 samples");
+    if (int rcb = check_batch(h, B)) return rcb;
+    ENTER_DEVICE(h);
+    const hipStream_t s = (hipStream_t)stream;
+    const bool own_scratch = !d_mfcc;
+    if (own_scratch) {  // the kernels write MFCC rows anyway: into the engine's scratch
+        int rc;
+        if ((rc = order_after_scratch_users(h, s))) return rc;
+        if ((rc = h->s_mfcc.reserve((size_t)B * h->cfg.max_frames * h->nc))) return rc;
+        d_mfcc = h->s_mfcc.p;
+    }
+    launch_mfcc_features(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), kind, d_feat, s);
+    HIP_TRY(hipGetLastError());
+    if (own_scratch) return mark_scratch_user(h, s);
+    return SR_OK;
+}
+
 // EXTENSION (no reference counterpart): delta cepstra, see k_delta_mfcc
 int sr_delta_mfcc_batch_dev(sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_vad, const uint32_t *d_frames,
                             uint32_t B, int16_t *d_delta, void *stream)

@@ -17,6 +17,8 @@ TESTING_LIB_PATH = os.path.join(_HERE, "libsr_engine_testing.so")
 DIS_ERR = 0xFFFFFFFF
 ST_OK, ST_VAD_FAIL, ST_MFCC_FAIL, ST_SEG_OOB = 0, 1, 2, 3
 N_COEF = 12
+# per-frame intermediate values of the front end (sr_frame_features_batch*): packed FFT words, |X|*10, Mel energies, log*100
+FEAT_FFT, FEAT_MAG, FEAT_MEL, FEAT_LOGMEL = 1, 2, 3, 4
 
 RESULT_DTYPE = np.dtype([("best_tpl", "<u4"), ("min_dis", "<u4"), ("frm_num", "<u4"), ("status", "<u4")])
 VAD_DTYPE = np.dtype([("mid_val", "<u4"), ("n_thl", "<u2"), ("z_thl", "<u2"), ("s_thl", "<u4"),
@@ -294,6 +296,31 @@ class Engine:
                                                 _vp(end), _vp(mid), _vp(out), _vp(n), _vp(st)))
         return n, out, st
 
+    def frame_feature_width(self, kind):
+        """sr_frame_feature_width: u32 words per frame of a feature kind (0 for an unknown kind)"""
+        self.L.sr_frame_feature_width.restype = C.c_uint32
+        return int(self.L.sr_frame_feature_width(self.h, C.c_int(kind)))
+
+    def frame_features(self, pcm, start, end, mid, kind, want_mfcc=False):
+        """Per-frame intermediate values of get_mfcc for segment [start[b], end[b]) of row b (sr_frame_features_batch):
+        kind FEAT_FFT / FEAT_MAG (uint32 [B, max_frames, nfft/2]) or FEAT_MEL / FEAT_LOGMEL ([B, max_frames, n_mel]), rows
+        >= frm_num zero.  Returns (feat, frm_num, status), and the MFCC rows of the same launch as a fourth item when
+        want_mfcc.  Failed records as in mfcc_status()."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        width = self.frame_feature_width(kind)
+        feat = np.zeros((B, self.max_frames, max(width, 1)), dtype=np.uint32)
+        mf = np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16) if want_mfcc else None
+        n = np.zeros(B, dtype=np.uint32)
+        st = np.zeros(B, dtype=np.uint32)
+        self._check(self.L.sr_frame_features_batch(self.h, C.c_int(kind), _vp(pcm), C.c_uint64(S), C.c_uint32(S),
+                                                   C.c_uint32(B), _vp(start), _vp(end), _vp(mid), _vp(feat), _vp(mf),
+                                                   _vp(n), _vp(st)))
+        return (feat, n, st, mf) if want_mfcc else (feat, n, st)
+
     def dtw(self, in_mfcc, in_frames):
         """in_mfcc int16 [B, max_frames, 12] against the template store -> (scores [B,K], results [B])."""
         in_mfcc = np.ascontiguousarray(in_mfcc, dtype=np.int16)
@@ -408,6 +435,25 @@ class Engine:
         self._check(self.L.sr_mfcc_batch_dev(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(B), _vp(vad), _vp(mfcc),
                                              C.c_void_p(stream)))
         return vad, mfcc
+
+    def frame_features_dev(self, pcm, vad, kind, mfcc=None, stream=None):
+        """sr_frame_features_batch_dev on device tensors: pcm int16 [B, S] (u16 codes), vad [B, 12] int32 records (from
+        features_dev / recognize_dev); mfcc (optional) int16 [B, max_frames, n_coef] receives the MFCC rows of the same
+        launch.  Returns the feature tensor int32 [B, max_frames, width] (the u32 words; .view(torch.uint32) or numpy
+        .view(np.uint32) to read them unsigned).  Asynchronous on `stream` (a torch.cuda.Stream, or the current one)."""
+        import torch
+        assert pcm.is_cuda and pcm.dtype in (torch.int16, torch.uint16) and pcm.is_contiguous()
+        B, S = pcm.shape
+        width = self.frame_feature_width(kind)
+        if stream is None:
+            stream = torch.cuda.current_stream(pcm.device)
+        feat = torch.empty(B, self.max_frames, max(width, 1), dtype=torch.int32, device=pcm.device)
+        self._check(self.L.sr_frame_features_batch_dev(self.h, C.c_int(kind), _vp(pcm), C.c_uint64(S), C.c_uint32(B),
+                                                       _vp(vad), _vp(feat), _vp(mfcc),
+                                                       C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            feat.record_stream(stream)  # allocated on the current stream, written on `stream`
+        return feat
 
     def set_pipeline(self, streams=3, min_chunk=4096, max_chunks=12):
         """chunking of recognize_dev over the engine's internal streams (streams=1: one chunk, caller's stream)"""
