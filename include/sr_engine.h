@@ -184,6 +184,44 @@ int sr_recognize_segments_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_
                                     uint32_t B, sr_result *d_results, uint32_t *d_scores, sr_vad_rec *d_vad,
                                     void *stream);
 
+/* Stream recognition: every word of recordings of any length.  EXTENSION, NO REFERENCE COUNTERPART: the firmware's VAD
+ * stops after max_vc_con = 3 segments (VAD.H:4, VAD.C:203) of a buffer of at most 65 535 samples.  Per recording b the
+ * segmentation is exactly VAD() with max_vc_con unbounded over its len[b] samples (VAD.C:121-217; state carried from frame to
+ * frame as there, never reset between segments), thresholds from noise_atap over its first noise_len samples (VAD.C:22-71)
+ * unless given.  One record per segment start, stream-major, then by start; a segment the recording ended inside (state 2
+ * or 3) has end = -1 (what VAD.C leaves in valid_voice[n].end) and is never recognised; a recording that ends in the onset
+ * (state 1) reports nothing for that run.  frm_num and the recognition status follow segment selection to the letter:
+ * end < 0 -> SR_ST_VAD_FAIL, start < 1 -> SR_ST_SEG_OOB, else the u16-wrapping frame count of MFCC.C:102-107, more than
+ * max_frames -> SR_ST_MFCC_FAIL.  cfg.max_seg does not limit these calls.  Argument rules: those of sr_vad_batch, plus
+ * len[b] <= buf_len and, without atap_in, len[b] >= the noise head and > frame_len (the host form checks them; the device
+ * form clamps d_len[b] to buf_len and reads nothing beyond it). */
+typedef struct sr_stream_seg { /* 16 bytes */
+    uint32_t stream;           /* recording index b */
+    int32_t start;             /* sample offset in recording b (VAD.C:178) */
+    int32_t end;               /* sample offset (VAD.C:201); -1: the recording ended inside this segment */
+    uint32_t frm_num;          /* frames of the segment per MFCC.C:102-107, 0 on failure */
+} sr_stream_seg;
+/* DEVICE buffers, asynchronous on `stream`.  Recording b is d_pcm + b*pcm_stride, d_len[b] <= buf_len samples long
+ * (d_len NULL: every recording is buf_len long).  d_atap_in NULL: noise_atap on each recording's head.
+ * d_seg_offsets[B+1] (required): exclusive offsets of each recording's segments in the output, d_seg_offsets[B] = the
+ * TRUE total, which may exceed max_segs.  Only records with index < max_segs are written.  d_atap[B] optional. */
+int sr_stream_segments_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len,
+                           const uint32_t *d_len, uint32_t B, const sr_atap *d_atap_in, uint32_t max_segs,
+                           sr_stream_seg *d_segs, uint32_t *d_seg_offsets, sr_atap *d_atap, void *stream);
+/* The same, then every written segment recognised like segment 0 of sr_recognize_batch_dev:
+ * d_results[max_segs], d_scores[max_segs*K], d_mfcc[max_segs*max_frames*n_coef] (scores, mfcc optional).
+ * Result slots in [total, max_segs) are written as failed records (SR_ST_VAD_FAIL, SR_DIS_ERR, frm_num 0). */
+int sr_recognize_stream_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len,
+                            const uint32_t *d_len, uint32_t B, const sr_atap *d_atap_in, uint32_t max_segs,
+                            sr_stream_seg *d_segs, uint32_t *d_seg_offsets, sr_result *d_results, uint32_t *d_scores,
+                            int16_t *d_mfcc, void *stream);
+/* HOST buffers: copy in, run, copy out.  *n_segs = the true total; it syncs on the count, so the recognition launches cover
+ * exactly min(total, max_segs) records (outputs past them are not written).  len, atap_in, results, scores, mfcc may be
+ * NULL (results NULL: segmentation only). */
+int sr_recognize_stream(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, const uint32_t *len,
+                        uint32_t B, const sr_atap *atap_in, uint32_t max_segs, sr_stream_seg *segs, uint32_t *seg_offsets,
+                        sr_result *results, uint32_t *scores, int16_t *mfcc, uint32_t *n_segs);
+
 /* stage-level entry points on DEVICE buffers (same kernels the full path launches) */
 int sr_vad_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                      sr_vad_rec *d_vad, void *stream);
@@ -352,6 +390,7 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "dtw_debug"                      print the DTW geometry when a store is set
  *   "perturb_log_thr", "log_thr_from_host"   exercise / bypass the shipped log-step-table check (sr_log_table_mismatches)
  *   "mag_cheap_off"                  sr_create behaves as if its device sweep of the cheap magnitude form had failed
+ *   "stream_tile_frames"             frames per tile of the stream VAD scan (16..1024, a multiple of 16; default 512)
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

@@ -24,6 +24,7 @@ enum DevHook {
     kHookDtwDebug,        // "dtw_debug":   print the k_dtw_lds geometry when a store is set
     kHookCellsLiteral,    // "cells_literal": k_dtw_cells walks every pair literally (the fallback of walks that leave the band)
     kHookMagCheapOff,     // "mag_cheap_off": sr_create behaves as if the device sweep of the cheap magnitude form had failed (bound 0)
+    kHookStreamTile,      // "stream_tile_frames": frames per tile of the stream VAD scan (16..1024, a multiple of 16)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -68,6 +69,47 @@ struct VadArgs {
     uint32_t v_durmin;       // VAD.C:72-73: 80 ms / (frame_time - frame_mov_t) frames (8 at 20 / 10 ms)
     uint32_t s_durmax;       // VAD.C:74-75: 110 ms / (frame_time - frame_mov_t) frames (11)
     uint32_t wide;           // 1: a workgroup of four waves per capture (k_vad_wide.hip; small launches), 0: one wave per capture
+};
+
+// stream VAD (k_vad_stream.hip): B recordings scanned in tiles of tile_frames frames, nt tile slots per recording
+struct VadStreamArgs {
+    const uint16_t *pcm;      // [B][pcm_stride], 16-byte aligned rows
+    uint64_t pcm_stride;      // samples
+    uint32_t buf_len;         // samples per recording at most
+    const uint32_t *len;      // optional [B]: samples of each recording (clamped to buf_len)
+    uint32_t B;
+    const uint8_t *atap_src;  // thresholds of recording b at atap_src + b * atap_src_stride (sr_atap, or sr_vad_rec.atap)
+    uint32_t atap_src_stride;
+    uint32_t frame_len, hop, v_durmin, s_durmax;
+    uint32_t n_front;         // onset states: max(v_durmin - 1, 1); tail states likewise from s_durmax
+    uint32_t n_states;        // 2 + onset states + tail states
+    uint32_t tile_frames;     // T, a multiple of 16, <= kStreamTileMax
+    uint32_t nt;              // tile slots per recording: ceil(frames of buf_len / T)
+    uint32_t mask_words;      // ceil(T / 32)
+    uint32_t max_frames;
+    uint64_t *tab;            // [B * nt][3][n_states]: state out | carry out << 8 | starts << 10, last start frame << 32
+    uint32_t *masks;          // [B * nt][3][mask_words]: loud bits per carry in
+    uint4 *tile_in;           // [B * nt]: carry | state << 8, segments before the tile, start of the open segment
+    sr_atap *atap_res;        // [B] the thresholds used
+    sr_atap *atap_out;        // optional [B]
+    uint32_t *seg_offsets;    // [B + 1]
+    sr_stream_seg *segs;      // [max_segs]
+    uint32_t max_segs;
+};
+constexpr uint32_t kStreamTileMax = 1024, kStreamTileDefault = 512;  // frames per tile of the stream VAD scan
+constexpr uint32_t kStreamLead = 8;  // samples before a segment in its recognition row (the pre-emphasis predecessor)
+struct StreamRecArgs {
+    const uint16_t *pcm;
+    uint64_t pcm_stride;
+    const sr_stream_seg *segs;
+    const uint32_t *seg_offsets;  // [B + 1]
+    uint32_t B;
+    const sr_atap *atap;          // [B]
+    uint32_t r0;                  // first record of this launch
+    uint32_t frame_len, hop, max_frames;
+    uint16_t *rows;               // [n][row_stride]
+    uint64_t row_stride;
+    sr_vad_rec *recs;             // [n]
 };
 
 struct MfccArgs {
@@ -154,6 +196,8 @@ void launch_vad_wide(const VadArgs &a, hipStream_t s);  // k_vad_wide.hip
 bool vad_framing_supported(uint32_t frame_len, uint32_t hop);  // the VAD kernel is instantiated per framing
 void launch_select_segment(const sr_vad_rec *in, sr_vad_rec *out, uint32_t B, uint32_t seg_idx, uint32_t max_frames,
                            uint32_t frame_len, uint32_t hop, hipStream_t s);
+void launch_vad_stream(const VadStreamArgs &a, bool sad, hipStream_t s);  // the three passes (sad: 16-bit mid, see k_vad)
+void launch_stream_records(const StreamRecArgs &a, uint32_t n, hipStream_t s);
 void launch_mfcc(const MfccArgs &a, hipStream_t s);
 void launch_mfcc_gen(const MfccArgs &a, hipStream_t s);  // GENERIC front end (k_mfcc_gen.hip)
 // the same kernels' per-frame intermediate values (kind = SR_FEAT_*) into feat[B][max_frames][width], MFCC rows into a.mfcc

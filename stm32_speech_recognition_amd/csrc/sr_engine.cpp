@@ -21,7 +21,7 @@ static std::atomic<int64_t> g_hooks[kHookCount];
 int64_t dev_hook(DevHook h) { return g_hooks[h].load(std::memory_order_relaxed); }
 static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc", "mfcc_grid", "perturb_log_thr",
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
-                                                   "mag_cheap_off"};
+                                                   "mag_cheap_off", "stream_tile_frames"};
 #endif
 }  // namespace sr
 
@@ -368,6 +368,15 @@ void sr_destroy(sr_engine *h)
     h->tpl_frames_s.release();
     h->tpl_orig.release();
     h->s_pcm.release();
+    h->s_st_vad.release();
+    h->s_st_tab.release();
+    h->s_st_mask.release();
+    h->s_st_tin.release();
+    h->s_st_atap.release();
+    h->s_st_rows.release();
+    h->s_st_recs.release();
+    h->s_st_segs.release();
+    h->s_st_off.release();
     h->s_pack.release();
     h->s_vad.release();
     h->s_mfcc.release();

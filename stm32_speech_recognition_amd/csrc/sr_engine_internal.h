@@ -121,6 +121,17 @@ struct sr_engine {
     DevBuf<uint32_t> s_u32a, s_u32b;
     DevBuf<sr_atap> s_atap;
     DevBuf<sr_vad_rec> s_vad2;
+    // stream recognition (sr_stream.cpp): thresholds, tile tables, loud masks, tile entry states, per-chunk rows / records,
+    // and the host form's device copies of its outputs
+    DevBuf<sr_vad_rec> s_st_vad;
+    DevBuf<uint64_t> s_st_tab;
+    DevBuf<uint32_t> s_st_mask;
+    DevBuf<uint4> s_st_tin;
+    DevBuf<sr_atap> s_st_atap;
+    DevBuf<uint16_t> s_st_rows;
+    DevBuf<sr_vad_rec> s_st_recs;
+    DevBuf<sr_stream_seg> s_st_segs;
+    DevBuf<uint32_t> s_st_off;
     DevBuf<uint32_t> s_pcnt;  // k_dtw_cells: finished-pair counters per utterance of a call, zero between launches (kPairCounters)
     // The counters are hidden per-engine state shared by every launch: two small calls in flight on DIFFERENT caller streams
     // would both count in them.  They therefore belong to one caller stream at a time (internal chunk streams are forked from /

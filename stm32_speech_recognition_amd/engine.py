@@ -23,7 +23,10 @@ FEAT_FFT, FEAT_MAG, FEAT_MEL, FEAT_LOGMEL = 1, 2, 3, 4
 RESULT_DTYPE = np.dtype([("best_tpl", "<u4"), ("min_dis", "<u4"), ("frm_num", "<u4"), ("status", "<u4")])
 VAD_DTYPE = np.dtype([("mid_val", "<u4"), ("n_thl", "<u2"), ("z_thl", "<u2"), ("s_thl", "<u4"),
                       ("seg", "<i4", (6,)), ("frm_num", "<u4"), ("status", "<u4"), ("_pad", "<u4")])
+ATAP_DTYPE = np.dtype([("mid_val", "<u4"), ("n_thl", "<u2"), ("z_thl", "<u2"), ("s_thl", "<u4")])
+STREAM_SEG_DTYPE = np.dtype([("stream", "<u4"), ("start", "<i4"), ("end", "<i4"), ("frm_num", "<u4")])
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48
+assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16
 
 
 class Config(C.Structure):
@@ -260,6 +263,37 @@ class Engine:
                                                        _vp(res), _vp(sc), _vp(vd)))
         return res, sc, vd
 
+    def segment_stream(self, pcm, lengths=None, atap=None, max_segs=None):
+        """Stream VAD of recordings of any length (sr_recognize_stream without recognition): pcm uint16 [B, S],
+        lengths [B] (None: S each), atap (None: noise_atap on each head, else an ATAP_DTYPE array [B]).
+        Returns dict(segs [n] STREAM_SEG_DTYPE, seg_offsets [B+1], total); n = min(total, max_segs)."""
+        return self.recognize_stream(pcm, lengths, atap, max_segs, recognize=False)
+
+    def recognize_stream(self, pcm, lengths=None, atap=None, max_segs=None, want_scores=True, want_mfcc=True,
+                         recognize=True):
+        """Every segment of every recording recognised (sr_recognize_stream).  max_segs None: a first call counts the
+        segments.  Returns dict(segs, seg_offsets, total, results, scores, mfcc) of numpy arrays, the
+        per-segment outputs n = min(total, max_segs) long."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint32)
+        at = None if atap is None else np.ascontiguousarray(atap, dtype=ATAP_DTYPE)
+        if max_segs is None:
+            max_segs = int(self.recognize_stream(pcm, ln, at, 0, recognize=False)["total"])
+        K = self.n_templates if recognize else 0
+        segs = np.zeros(max_segs, dtype=STREAM_SEG_DTYPE)
+        off = np.zeros(B + 1, dtype=np.uint32)
+        res = np.zeros(max_segs, dtype=RESULT_DTYPE) if recognize else None
+        sc = np.zeros((max_segs, K), dtype=np.uint32) if recognize and want_scores else None
+        mf = np.zeros((max_segs, self.max_frames, self.n_coef), dtype=np.int16) if recognize and want_mfcc else None
+        total = C.c_uint32(0)
+        self._check(self.L.sr_recognize_stream(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S), _vp(ln), C.c_uint32(B), _vp(at),
+                                               C.c_uint32(max_segs), _vp(segs), _vp(off), _vp(res), _vp(sc), _vp(mf),
+                                               C.byref(total)))
+        n = min(total.value, max_segs)
+        cut = (lambda x: None if x is None else x[:n])
+        return dict(segs=segs[:n], seg_offsets=off, total=total.value, results=cut(res), scores=cut(sc), mfcc=cut(mf))
+
     def vad(self, pcm, buf_len=None):
         pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
         B, S = pcm.shape
@@ -454,6 +488,32 @@ class Engine:
         if isinstance(stream, torch.cuda.Stream):
             feat.record_stream(stream)  # allocated on the current stream, written on `stream`
         return feat
+
+    def recognize_stream_dev(self, pcm, max_segs, lengths=None, atap=None, scores=True, mfcc=True, stream=None):
+        """sr_recognize_stream_dev on device tensors: pcm int16 [B, S] (u16 codes), lengths int32 [B] (or None), atap
+        int32 [B, 3] sr_atap records (or None).  Asynchronous on `stream` (a torch.cuda.Stream, or the current one).
+        Returns dict of device tensors: segs int32 [max_segs, 4], seg_offsets int32 [B+1] (the last = the true total),
+        results int32 [max_segs, 4], scores [max_segs, K], mfcc [max_segs, max_frames, n_coef]."""
+        import torch
+        assert pcm.is_cuda and pcm.dtype in (torch.int16, torch.uint16) and pcm.is_contiguous()
+        B, S = pcm.shape
+        dev, K = pcm.device, self.n_templates
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        o = dict(segs=torch.empty(max(max_segs, 1), 4, dtype=torch.int32, device=dev)[:max_segs],
+                 seg_offsets=torch.empty(B + 1, dtype=torch.int32, device=dev),
+                 results=torch.empty(max(max_segs, 1), 4, dtype=torch.int32, device=dev)[:max_segs])
+        o["scores"] = torch.empty(max_segs, K, dtype=torch.int32, device=dev) if scores else None
+        o["mfcc"] = torch.empty(max_segs, self.max_frames, self.n_coef, dtype=torch.int16, device=dev) if mfcc else None
+        self._check(self.L.sr_recognize_stream_dev(
+            self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S), _vp(lengths), C.c_uint32(B), _vp(atap), C.c_uint32(max_segs),
+            _vp(o["segs"]), _vp(o["seg_offsets"]), _vp(o["results"]), _vp(o["scores"]), _vp(o["mfcc"]),
+            C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            for t in o.values():
+                if t is not None:
+                    t.record_stream(stream)  # allocated on the current stream, written on `stream`
+        return o
 
     def set_pipeline(self, streams=3, min_chunk=4096, max_chunks=12):
         """chunking of recognize_dev over the engine's internal streams (streams=1: one chunk, caller's stream)"""
