@@ -387,7 +387,8 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "dtw_u", "dtw_tie_g", "dtw_kc"   force the staged DTW kernel's workgroup geometry (read when a template store is set;
  *                                    a forced combination that does not fit the LDS / the grid is ignored)
  *   "mfcc_grid"                      workgroups of the frame kernel (read by sr_create)
- *   "dtw_debug"                      print the DTW geometry when a store is set
+ *   "dtw_debug"                      print the DTW plan (staged, per-pair and four-lane forms) when a store is set, and
+ *                                    the full-DP scorer's lanes per pair at each launch
  *   "perturb_log_thr", "log_thr_from_host"   exercise / bypass the shipped log-step-table check (sr_log_table_mismatches)
  *   "mag_cheap_off"                  sr_create behaves as if its device sweep of the cheap magnitude form had failed
  *   "stream_tile_frames"             frames per tile of the stream VAD scan (16..1024, a multiple of 16; default 512)

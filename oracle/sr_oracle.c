@@ -338,7 +338,9 @@ uint32_t sr_oracle_mfcc(const sr_oracle *o, const uint16_t *buf, int32_t start, 
     uint32_t cnt = 0;
     if (n > o->cfg.max_frames)
         return 0; /* MFCC.C:103-107 */
-    for (int32_t p = start; p <= end - (int32_t)fl; p += (int32_t)hop) {
+    /* A segment of 65 536 frames or more passes with n = its count mod 2^16.  MFCC.C:110-186 would then go on over every
+       frame of the segment, past mfcc_dat (undefined); this definition, like the engine, keeps the first n frames. */
+    for (int32_t p = start; p <= end - (int32_t)fl && cnt < n; p += (int32_t)hop) {
         mfcc_frame(o, buf + p, (int32_t)atap->mid_val, mfcc + (size_t)cnt * o->cfg.n_coef);
         cnt++;
     }

@@ -250,7 +250,9 @@ __global__ void __launch_bounds__(cells::kThreads) k_dtw_cells(const DtwArgs a, 
         // entry of the lane to its left (one DPP move across the wave).  A wave owns a contiguous range of rows and, block by
         // block of 64 columns (63 points wide: lane 0 only feeds lane 1), the columns their stored ranges span; the template
         // row of a lane's column stays in registers, the input row is one broadcast LDS read.
-        bool literal = a.cells_literal != 0 || npts > a.cells_points;  // (the second: never, dtw_cells_max_points bounds it)
+        // (the second: a pair whose band outgrows the points plan_dtw could give the workgroup beside the staged rows -- from
+        // about 300 frames on, the longest utterances against the longest templates)
+        bool literal = a.cells_literal != 0 || npts > a.cells_points;
         if (!literal) {
             const uint32_t rows_per = (MX + kThreads / 64 - 1) / (kThreads / 64);
             const uint32_t p0 = wv * rows_per, p1 = (p0 + rows_per < MX) ? p0 + rows_per : MX;

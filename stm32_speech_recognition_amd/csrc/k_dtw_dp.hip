@@ -1,6 +1,7 @@
 // k_dtw_dp.hip -- OPT-IN, NON-REFERENCE full dynamic-programming DTW scorer.
 // gfx950 (MI355X, CDNA4) only; wave = 64 lanes; no MFMA (the path has no dense contraction), integer VALU + LDS.
 // Every kernel reproduces the reference's integer arithmetic bit for bit; cited lines are relative to the reference tree.
+#include <cstdio>
 #include <type_traits>
 
 #include "sr_dtw_dev.h"
@@ -353,6 +354,8 @@ void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hi
         if (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > budget.stage_cap) G = 1;
     }
     const int W = dp_waves_for(G);
+    if (dev_hook(kHookDtwDebug))
+        std::fprintf(stderr, "sr_engine: full-DP scorer for %u template rows: %d lanes per pair\n", a.tpl_rows, G);
     const uint32_t per_wg = G == 1 ? 4u : (uint32_t)(W * (64 / G));  // utterances per workgroup (k_dtw_dp_wave64: one per wave)
     const size_t lds = G == 1 ? (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4 : dp_band_lds(a.tpl_rows, G, W, &rp);
     // the utterance blocks are the grid's second dimension (<= 65 535): larger batches go out in slices

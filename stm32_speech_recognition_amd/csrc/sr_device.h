@@ -21,7 +21,7 @@ enum DevHook {
     kHookPerturbLogThr,   // "perturb_log_thr": move host-built log step m by one (exercises the shipped-table check)
     kHookLogThrFromHost,  // "log_thr_from_host": keep the host's log step table even where it differs from the shipped one
     kHookMultiAllowDup,   // "multi_allow_dup": sr_multi_create accepts one device several times (1-GPU tests over the RCCL double)
-    kHookDtwDebug,        // "dtw_debug":   print the k_dtw_lds geometry when a store is set
+    kHookDtwDebug,        // "dtw_debug":   print the DTW plan when a store is set, and the full-DP scorer's form per launch
     kHookCellsLiteral,    // "cells_literal": k_dtw_cells walks every pair literally (the fallback of walks that leave the band)
     kHookMagCheapOff,     // "mag_cheap_off": sr_create behaves as if the device sweep of the cheap magnitude form had failed (bound 0)
     kHookStreamTile,      // "stream_tile_frames": frames per tile of the stream VAD scan (16..1024, a multiple of 16)

@@ -154,9 +154,6 @@ void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid)
     const uint32_t K = h->K, R = h->cfg.max_frames, rows = h->tpl_rows, nc = h->nc;
     // the batch kernel: k_dtw_lds where the store can be staged, else k_dtw_gen / k_dtw
     if (h->tpl_staged_ok) p.lds_u = dtw_lds_pick_u(K, R, lds, &p.lds_bytes, &p.lds_tie_g, &p.lds_kc, nc > (uint32_t)kCoef ? 8u : 6u);
-    if (dev_hook(kHookDtwDebug))
-        std::fprintf(stderr, "sr_engine: k_dtw_lds geometry for K = %u, %u rows: U = %u, Kc = %u, tie table %u, LDS %u bytes\n", K, R,
-                     p.lds_u, p.lds_kc, p.lds_tie_g, p.lds_bytes);
     // k_dtw_cells: the most band points any pair of this store can have (one word per point in LDS) -- capped at what a
     // workgroup's LDS holds beside the rows: a pair with more points than that (utterances near the frame cap against the
     // longest templates) is walked literally by its workgroup, which costs what the batch kernel costs
@@ -182,6 +179,12 @@ void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid)
     // time is flat up to ~400 000 pairs (126 us at the firmware's shapes), a round of the quad kernel takes a third of that, so
     // the automatic mode hands it launches of up to two rounds (profiles/r05_small_launch_sweep.json).
     if (p.quad_pu) p.quad_pairs = 2 * (uint64_t)h->n_cu * std::min(8u, lds.wgs_per_cu(p.quad_bytes)) * p.quad_pu * p.quad_pk;
+    if (dev_hook(kHookDtwDebug)) {
+        std::fprintf(stderr, "sr_engine: k_dtw_lds geometry for K = %u, %u rows: U = %u, Kc = %u, tie table %u, LDS %u bytes\n", K, R,
+                     p.lds_u, p.lds_kc, p.lds_tie_g, p.lds_bytes);
+        std::fprintf(stderr, "sr_engine: k_dtw_cells for %u template rows: %u band points, LDS %u bytes; k_dtw_quad: %u x %u, LDS %u bytes\n",
+                     rows, p.cells_points, p.cells_bytes, p.quad_pu, p.quad_pk, p.quad_bytes);
+    }
     h->plan = p;
 }
 

@@ -8,6 +8,7 @@ module.  The product package never does.
              MFCC.C / DTW.C compiled verbatim (+ C transcription of the asm FFT)
   RefLib320 -- the same objects built with vv_tim_max = 3210 ms (320 frames instead of
              119; oracle/Makefile), so the reference's own code runs the benchmark shape
+  RefLibLong -- the same with vv_tim_max = 163 840 ms: 16 383 frames, the engine's frame cap
 """
 import ctypes as C
 import os
@@ -20,6 +21,7 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 LIB_PATH = os.path.join(ORACLE_DIR, "liboracle.so")
 REF_PATH = os.path.join(ORACLE_DIR, "_ref", "libsr_ref.so")
 REF320_PATH = os.path.join(ORACLE_DIR, "_ref", "libsr_ref320.so")   # same objects, vv_tim_max patched to 320 frames
+REF_LONG_PATH = os.path.join(ORACLE_DIR, "_ref", "libsr_ref_long.so")  # ... patched to 16 383 frames
 
 DIS_ERR = 0xFFFFFFFF
 ST_OK, ST_VAD_FAIL, ST_MFCC_FAIL, ST_SEG_OOB = 0, 1, 2, 3
@@ -30,7 +32,8 @@ def build(force=False):
     srcs = [os.path.join(ORACLE_DIR, f) for f in ("sr_oracle.c", "sr_oracle.h", "q15_fft.c", "ref_glue.c", "Makefile")]
     stale = force or not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs if os.path.exists(s))
-    if os.path.isdir("/root/reference/Src/Speech_Recog") and not (os.path.exists(REF_PATH) and os.path.exists(REF320_PATH)):
+    if os.path.isdir("/root/reference/Src/Speech_Recog") and not all(
+            os.path.exists(p) for p in (REF_PATH, REF320_PATH, REF_LONG_PATH)):
         stale = True
     if stale:
         subprocess.check_call(["make", "-C", ORACLE_DIR, "all"], stdout=subprocess.DEVNULL)
@@ -368,6 +371,15 @@ class RefLib320(RefLib):
     FTR_BYTES = 4 + 320 * 12 * 2
     FRM_MAX = 320
     PATH = REF320_PATH
+
+
+class RefLibLong(RefLib):
+    """Tier (i) at vv_frm_max = 16 383, the engine's frame cap: vv_tim_max 1200 -> 163 840 ms (oracle/Makefile, same recipe
+    as RefLib320).  Its VAD still takes a u16 buffer length; get_mfcc is called with the segment directly.  A segment of
+    65 536 frames or more must never reach it: get_mfcc would write every frame past mfcc_dat (MFCC.C:102-186)."""
+    FTR_BYTES = 4 + 16383 * 12 * 2
+    FRM_MAX = 16383
+    PATH = REF_LONG_PATH
 
 
 def ref320_store(tm, tfr, valid=None, stride=8192):

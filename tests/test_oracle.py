@@ -726,3 +726,47 @@ def test_extension_fft512_is_a_dft_within_its_truncation_bound(oracle):
         assert np.sqrt((err ** 2).mean()) <= 5.0 + 3e-4 * scale, (np.sqrt((err ** 2).mean()), scale)
         worst = max(worst, err.max() - 6e-4 * scale)
     assert worst > 0.3                                                    # the bound is not vacuous: truncation is visible
+
+
+@needs_ref_objects
+@pytest.mark.skipif(not os.path.exists(ol.REF_LONG_PATH), reason="16 383-frame reference objects not built (reference tree absent)")
+def test_tier2_equals_reference_objects_at_the_frame_cap():
+    """the reference's own get_mfcc and dtw built with vv_frm_max = 16 383 (the engine's frame cap) against the restatement
+    at max_frames = 16 383: segments of 1, 641, 4 097 and 16 383 frames, and 16 384 (refused by both, MFCC.C:103-107);
+    random, full-scale and constant feature pairs up to 16 383 frames, at and just across the 2:1 length gates"""
+    r = ol.RefLibLong()
+    assert r.FTR_BYTES == 4 + 16383 * 24
+    R = 16383
+    o = ol.Oracle(max_frames=R)
+    rng = np.random.default_rng(163)
+    S = 2400 + 800 + (R + 2) * 80 + 4000
+    t = np.arange(S)
+    x = np.clip(np.round(2048 + 600 * np.sin(2 * np.pi * 440 * t / 8000) * (t >= 3200) + rng.normal(0, 6, S)), 0, 4095)
+    x = x.astype(np.uint16)
+    rc, a = o.noise_atap(x)
+    assert rc == 0
+    for n in (1, 641, 4097, R, R + 1):
+        st = 3200 + 17
+        en = st + (n - 1) * 80 + 160
+        n1, m1, _ = r.mfcc(x, st, en, a)
+        n2, m2 = o.mfcc(x, st, en, a)
+        if n > R:
+            assert n1 == n2 == 0
+        else:
+            assert n1 == n2 == n and np.array_equal(m1, m2), n
+            assert m2.any()
+    pad = np.zeros((1, 12), np.int16)
+    pairs = [(R, R), (R, R // 2 + 1), (R // 2 + 1, R), (R, R // 2), (R // 2 - 1, R), (R, 8191), (8192, R), (R - 1, 2),
+             (1, 1), (1, 2), (2, 1), (3000, 6000), (3000, 6001), (6001, 3000), (641, 1282), (4097, 8194)]
+    n_err = 0
+    for i, (na, nb) in enumerate(pairs):
+        amp = [3000, 32767, 16383][i % 3]
+        a_ = rng.integers(-amp, amp + 1, (R + 1, 12)).astype(np.int16)
+        b_ = rng.integers(-amp, amp + 1, (R + 1, 12)).astype(np.int16)
+        if i % 4 == 3:
+            b_[:] = a_[0]  # one repeated row: ties
+        d1 = r.dtw(ol.RefLibLong.make_ftr(a_, na), ol.RefLibLong.make_ftr(b_, nb))
+        d2 = o.dtw(np.concatenate([a_[:na + 1], pad]), na, np.concatenate([b_[:nb + 1], pad]), nb)
+        assert d1 == d2, (na, nb)
+        n_err += int(d1 == ol.DIS_ERR)
+    assert 0 < n_err < len(pairs)
