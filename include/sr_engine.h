@@ -86,7 +86,7 @@ typedef struct sr_vad_rec {
     int32_t seg[2 * SR_MAX_SEG]; /* start/end sample offsets of up to 3 segments, -1 = NULL (VAD.H:18-22) */
     uint32_t frm_num;            /* frames of segment 0 per MFCC.C:102-107 (0 on any failure) */
     uint32_t status;             /* SR_ST_* */
-    uint32_t _pad;
+    uint32_t _pad;               /* written as 0 by every call that writes the record */
 } sr_vad_rec;
 
 /* recognition record, 16 bytes: the argmin of main.c:276-295 */
@@ -158,7 +158,9 @@ int sr_train_store(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint3
  *   results[B], scores[B*K] (cur_dis of every slot, main.c:283), mfcc[B*max_frames*n_coef]
  *   (frame-major, rows >= frm_num zeroed), vad[B].
  *
- * sr_recognize_batch:      HOST buffers; stages them through HBM (PCIe-inclusive).
+ * sr_recognize_batch:      HOST buffers; stages them through HBM (PCIe-inclusive).  HOST capture buffers of every
+ *                          entry point need only the 2-byte alignment of their samples and take any
+ *                          pcm_stride >= buf_len, odd ones included; nothing outside [0, buf_len) of a row is read.
  * sr_recognize_batch_dev:  DEVICE buffers already resident in HBM, enqueued on `stream`
  *                          (a hipStream_t; NULL = default stream), asynchronous.
  *                          pcm must be 16-byte aligned and pcm_stride a multiple of 8.
@@ -222,7 +224,10 @@ int sr_recognize_stream(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, 
                         uint32_t B, const sr_atap *atap_in, uint32_t max_segs, sr_stream_seg *segs, uint32_t *seg_offsets,
                         sr_result *results, uint32_t *scores, int16_t *mfcc, uint32_t *n_segs);
 
-/* stage-level entry points on DEVICE buffers (same kernels the full path launches) */
+/* stage-level entry points on DEVICE buffers (same kernels the full path launches).  d_vad records a caller writes itself
+ * follow the rules of those sr_vad_batch_dev writes: a failed record (status != 0) has frm_num 0.  The frame kernels
+ * (sr_mfcc_batch_dev, sr_frame_features_batch_dev) take seg[0] and frm_num as given and read frm_num frames from seg[0] - 1
+ * on; the DTW, full-DP and delta forms treat a record with status != 0 as failed whatever frm_num it carries. */
 int sr_vad_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                      sr_vad_rec *d_vad, void *stream);
 int sr_mfcc_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B, const sr_vad_rec *d_vad,

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import oracle_lib as ol
+from guarded import _dtw_all_modes  # every DTW form on one input (shared with test_buffer_contracts.py)
 from stm32_speech_recognition_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -33,34 +34,6 @@ def eng119():
 @pytest.fixture(scope="module")
 def oracle():
     return ol.Oracle(max_frames=119)
-
-
-def _dtw_all_modes(eng, im, inf):
-    """sr_dtw_batch with the batch kernels (small-launch mode 1), with one workgroup per pair wherever the band fits
-    (mode 2, k_dtw_cells), with four lanes per pair (mode 3, k_dtw_quad), in the automatic mode and with k_dtw_cells' literal
-    fallback forced: scores and results must be the same bytes; returns the first"""
-    from stm32_speech_recognition_amd.engine import dev_hook
-    eng.set_small_launch(1)
-    sc, res = eng.dtw(im, inf)
-    for mode in (2, 3, 0):
-        eng.set_small_launch(mode)
-        sc2, res2 = eng.dtw(im, inf)
-        assert np.array_equal(sc, sc2), mode
-        assert res.tobytes() == res2.tobytes(), mode
-    # k_dtw_cells' fallback for walks that leave dtw_limit's band (a step with all three candidates outside): the literal
-    # walk on the staged rows, forced for every pair by the development hook -- which exists only in the -DSR_TESTING build
-    # of the library, so an engine with the same configuration and store is opened there
-    et = eng.clone(testing=True)
-    dev_hook("cells_literal", 1)
-    try:
-        et.set_small_launch(2)
-        sc3, res3 = et.dtw(im, inf)
-    finally:
-        dev_hook("cells_literal", 0)
-        et.close()
-        eng.set_small_launch(0)
-    assert np.array_equal(sc, sc3) and res.tobytes() == res3.tobytes()
-    return sc, res
 
 
 def test_library_loaded_is_in_tree():
