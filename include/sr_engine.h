@@ -135,6 +135,10 @@ int sr_log_table_mismatches(void);
  * in use for this engine: 70171 after a clean sweep, 0 (every frame takes the exactly corrected root; sr_last_error()
  * holds a warning from sr_create) otherwise, and for front ends whose kernels do not use the form. */
 uint32_t sr_mag_cheap_bound(const sr_engine *h);
+/* Host-only (touches no device): frames whose largest re^2+im^2 is at most 26 843 (the QUIET tier) take their magnitudes from
+ * a table, t[n] = (u32)(sqrtf((float)n) * 10) << 2 -- MFCC.C:58 evaluated on the host, shifted so that t*t is the operand of
+ * the fused filterbank term.  Copies the first min(n, length) entries to out (may be NULL) and returns the length, 26 844. */
+uint32_t sr_mag_table(uint16_t *out, uint32_t n);
 
 /* ------------------------------------------------------------------ template store
  * The firmware keeps templates as v_ftr_tag images in MCU flash at a 4 KiB stride
@@ -396,6 +400,8 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    the full-DP scorer's lanes per pair at each launch
  *   "perturb_log_thr", "log_thr_from_host"   exercise / bypass the shipped log-step-table check (sr_log_table_mismatches)
  *   "mag_cheap_off"                  sr_create behaves as if its device sweep of the cheap magnitude form had failed
+ *   "mag_table_off"                  the frame kernel sends QUIET frames down the MID tier (v_sqrt_f32 root, literal filterbank
+ *                                    term -- exact over the QUIET range too) instead of the magnitude table; read per launch
  *   "stream_tile_frames"             frames per tile of the stream VAD scan (16..1024, a multiple of 16; default 512)
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)

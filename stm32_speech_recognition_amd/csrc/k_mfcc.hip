@@ -18,6 +18,14 @@ constexpr int kMfccWaves = 4;       // waves per workgroup
 // serial chain of ~1.5 us each: one capture = 110 frames is 28 workgroups of 4 frames instead of 2 of 64 -- 7 us instead of
 // 28-33 -- and 256 captures are 2 048 workgroups of 16 frames instead of 512 of 64)
 constexpr int kFramesPerWave = 16, kFramesPerWaveMid = 4, kFramesPerWaveSmall = 1;
+// bins per lane whose QUIET-tier magnitude comes from the table mag_q (sr_tables.h) instead of v_sqrt_f32: 8 = all of them,
+// 4 = the `+ 256` half only, 0 = none.  A knob per form: the batch form hides the gathers behind the other waves' arithmetic;
+// a one-frame launch would wait for a cold table, so the underfilled-launch forms keep the root (RESULTS.md, round 7).
+#ifndef SR_MAG_TAB_BINS
+#define SR_MAG_TAB_BINS 8
+#endif
+constexpr int mfcc_tab_bins(int fpw) { return fpw == kFramesPerWave ? SR_MAG_TAB_BINS : 0; }
+static_assert(SR_MAG_TAB_BINS == 0 || SR_MAG_TAB_BINS == 4 || SR_MAG_TAB_BINS == 8, "table bins per lane");
 // per-wave LDS: exchange/scratch words + windowed frame + filterbank outputs of the wave's frames
 // rows of the filterbank outputs and of the DCT tables are kMelPad = 25 words apart: in the DCT the lanes of a wave read
 // 6 different frames x 12 different coefficients rows at the same column, and a stride of 24 folds those onto 4 banks
@@ -31,15 +39,34 @@ constexpr int kMelPad = kMel + 1;
 __device__ __forceinline__ constexpr int mel_chunk_word(int j) { return 256 * ((j >> 2) & 1) + 4 * ((j >> 3) ^ (4 * ((j >> 2) & 1))) + (j & 3); }
 constexpr int mfcc_wave_lds_words(int fpw) { return kXchgWords + fpw * kMelPad + 64; }
 
-// Args = MfccArgs: the frame kernel.  Args = MfccFeatArgs<kind>: the same kernel, which also stores one intermediate value
-// per frame into a.feat[b][max_frames][width] at the point where it exists (sr_frame_features_batch_dev).  Every feature
-// store sits under `if constexpr`, so k_mfcc<kFPW, MfccArgs> compiles to the instructions it had before the parameter existed.
-template <int kFPW, typename Args = MfccArgs>
+// the kernel's argument block: the block every frame kernel takes (MfccArgs, or MfccFeatArgs<kind>) + the magnitude table
+template <typename Base>
+struct MfccTabArgs : Base {
+    const uint16_t *mag_q;
+    uint32_t mag_table_off;
+};
+template <typename Base>
+constexpr int mfcc_feat_kind<MfccTabArgs<Base>> = mfcc_feat_kind<Base>;
+template <typename Base>
+static MfccTabArgs<Base> mfcc_tab_args(const Base &b, const MfccMagTab &tab)
+{
+    MfccTabArgs<Base> r;
+    static_cast<Base &>(r) = b;
+    r.mag_q = tab.mag_q;
+    r.mag_table_off = tab.mag_table_off;
+    return r;
+}
+
+// Args = MfccTabArgs<MfccArgs>: the frame kernel.  Args = MfccTabArgs<MfccFeatArgs<kind>>: the same kernel, which also stores
+// one intermediate value per frame into a.feat[b][max_frames][width] at the point where it exists
+// (sr_frame_features_batch_dev).  Every feature store sits under `if constexpr`: the frame kernel carries none of them.
+template <int kFPW, typename Args = MfccTabArgs<MfccArgs>>
 __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 {
     constexpr int kFeat = mfcc_feat_kind<Args>;
     constexpr uint32_t kFeatW = (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) ? kBins : kMel;  // feature words per frame
     constexpr int kWaveLdsWords = mfcc_wave_lds_words(kFPW);
+    constexpr int kTabBins = mfcc_tab_bins(kFPW);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_dctM[kCoef * kMelPad];
     __shared__ int s_dctS[kCoef * kMelPad];  // 32-bit: read with the wide LDS loads, no byte extraction
@@ -123,6 +150,12 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
         p_lo = half + il, x_lo = (il >> 3) > 0 ? (il >> 3) - 1 : 0;
 #endif
     }
+    // The magnitude table as a structured buffer of exactly its size (stride 2, num_records in elements): the gathers index
+    // it with n itself (idxen) -- no address arithmetic on the VALU -- and an n past the end could only load 0, never fault
+    // (none occurs: only QUIET frames, every n <= kMagSmallMax, gather).  No builtin emits the indexed form, so the loads are
+    // inline assembly.
+    const uint64_t mag_p = (uint64_t)a.mag_q;
+    const u32x4 mag_rs = {(uint32_t)mag_p, (uint32_t)(mag_p >> 32) | (2u << 16), kMagTabEntries, 0x00027000u};
     const uint32_t tw_off = 32u * (uint32_t)lane;  // byte offset of the lane's eight raw filterbank weights (LOUD / MID tiers)
     // bin lane + 64 e3 (+ 256) of the magnitude stage in the same order: word e_base + 32 e3 (+ 128)
 #if SR_MEL_CHUNKED
@@ -219,7 +252,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             }
             // ---- |X|*10 and energy (MFCC.C:49-60, 128-133), three tiers by the largest re^2 + im^2 of the frame, decided for the whole
             // wave so that every branch is uniform:
-            //   QUIET  (<= kMagSmallMax = 26 843, i.e. |X|*10 <= 1638 and E <= kMelFusedMaxE): cheap magnitude + fused filterbank term
+            //   QUIET  (<= kMagSmallMax = 26 843, i.e. |X|*10 <= 1638 and E <= kMelFusedMaxE): magnitude from the table mag_q (batch form;
+            //                                     cheap magnitude in the forms without it, mfcc_tab_bins) + fused filterbank term
             //   MID    (<= a.mag_cheap_max = 70 171 on gfx950, |X|*10 <= 2648):              cheap magnitude + literal filterbank term
             //   LOUD   (anything else):                                                     exact magnitude + literal filterbank term
             // cheap magnitude = (u32)(v_sqrt_f32 * 10): equal to the exact form for every n <= 70 171 on gfx950 -- a property of this
@@ -228,7 +262,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             // certified, sr_dev.h sqrt_rn_int).  At the benchmark's amplitudes 97-99 % of the frames are QUIET; at SURVEY 8(d)'s
             // (gain 2.4) 29 % QUIET / 47 % MID / 24 % LOUD; near-clipping captures are LOUD (profiles/experiments/RESULTS.md).
             const uint32_t nmax = max(max(max(max(nn[0], nn[1]), nn[2]), max(max(nn[3], nn[4]), nn[5])), max(nn[6], nn[7]));
+#ifdef SR_TESTING  // development hook "mag_table_off": QUIET frames take the MID tier, independent arithmetic that is exact there too
+            const bool quiet = __builtin_expect(__builtin_amdgcn_ballot_w64(nmax > kMagSmallMax) == 0 && !a.mag_table_off, 1);
+#else
             const bool quiet = __builtin_expect(__builtin_amdgcn_ballot_w64(nmax > kMagSmallMax) == 0, 1);
+#endif
             // the literal filterbank form multiplies by the weights themselves: requested from the (cache-resident) table now, they
             // arrive behind the magnitude stage.  Kept out of LDS (the workgroup's share is full at four workgroups per CU) and out
             // of the quiet path's registers.
@@ -247,13 +285,50 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             }
             // energies go to the wave's scratch in the chunked order the filterbank reads them in (mel_chunk_word)
             uint32_t *eb = buf + e_base;
-            if (cheap) {
+            if (kTabBins > 0 && quiet) {
+                // QUIET-tier magnitudes << 2 from the table: eight gathers on the vector-memory path, which take no VALU issue
+                // slot -- the SIMD's other waves issue under them.  Requested only once the frame is known to be QUIET: gathered
+                // inside pass 5, before the decision, they cost the frames of the other tiers (scattered indices, nothing saved)
+                // more than the earlier start bought here (RESULTS.md, round 7).  (nn come from v_dot2; the nmax reduction and
+                // the branch between them and this point are more than the wait states a vector-memory read of them needs.)
+                uint32_t tq[8];
+#pragma unroll
+                for (int e3 = 0; e3 < 4; e3++) {
+                    if constexpr (kTabBins == 8)
+                        asm volatile("buffer_load_ushort %0, %1, %2, 0 idxen" : "=v"(tq[2 * e3]) : "v"(nn[2 * e3]), "s"(mag_rs));
+                    asm volatile("buffer_load_ushort %0, %1, %2, 0 idxen" : "=v"(tq[2 * e3 + 1]) : "v"(nn[2 * e3 + 1]), "s"(mag_rs));
+                }
+                uint32_t q0s[4];  // kTabBins = 4: the bins the table does not serve keep the root, shifted to match, under the gathers
+                if constexpr (kTabBins == 4) {
+#pragma unroll
+                    for (int e3 = 0; e3 < 4; e3++) q0s[e3] = cvt_u32(__builtin_amdgcn_sqrtf((float)(int)nn[2 * e3]) * 10.0f) << 2;
+                }
+                // the compiler does not count loads issued from inline assembly: the wait is written out, with the values tied in
+                if constexpr (kTabBins == 8)
+                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3]), "+v"(tq[4]), "+v"(tq[5]), "+v"(tq[6]), "+v"(tq[7]));
+                else
+                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(tq[1]), "+v"(tq[3]), "+v"(tq[5]), "+v"(tq[7]));
+                // the entries are |X|*10 << 2: their squares are E << 4, the operand of the fused filterbank term
+#pragma unroll
+                for (int e3 = 0; e3 < 4; e3++) {
+                    uint32_t q0, q1 = tq[2 * e3 + 1];
+                    if constexpr (kTabBins == 8) q0 = tq[2 * e3];
+                    else q0 = q0s[e3];
+                    if constexpr (kFeat == SR_FEAT_MAG) {  // the QUIET tier's magnitudes
+                        uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
+                        fr[0] = q0 >> 2;
+                        fr[256] = q1 >> 2;
+                    }
+                    eb[kEs * e3] = umul24(q0, q0);
+                    eb[kEs * e3 + kEh] = umul24(q1, q1);
+                }
+            } else if (cheap) {
 #pragma unroll
                 for (int e3 = 0; e3 < 4; e3++) {
                     const f32x2 m = f32x2{__builtin_amdgcn_sqrtf((float)(int)nn[2 * e3]), __builtin_amdgcn_sqrtf((float)(int)nn[2 * e3 + 1])} *
                                     f32x2{10.0f, 10.0f};
                     const uint32_t m0 = cvt_u32(m.x), m1 = cvt_u32(m.y);
-                    if constexpr (kFeat == SR_FEAT_MAG) {  // the QUIET / MID tiers' magnitudes
+                    if constexpr (kFeat == SR_FEAT_MAG) {  // the MID tier's magnitudes (and the QUIET tier's in a form without the table)
                         uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
                         fr[0] = m0;
                         fr[256] = m1;
@@ -292,7 +367,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                         const u32x4 me = s_tm[64 * c + lane], mo = s_tm[64 * (c + 2) + lane];
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
-                            const uint32_t es = e[4 * c + k] << 4;
+                            const uint32_t es = kTabBins > 0 ? e[4 * c + k] : e[4 * c + k] << 4;  // (the table's squares are shifted already)
                             se += mel_term_fused(es, me[k]);
                             so += mel_term_fused(es, mo[k]);
                             pe[4 * c + k] = se;
@@ -424,7 +499,7 @@ uint32_t mfcc_resident_workgroups(uint32_t frame_len)
     return (uint32_t)(per_cu * n_cu);
 }
 
-void launch_mfcc(const MfccArgs &a, hipStream_t s)
+void launch_mfcc(const MfccArgs &a, const MfccMagTab &tab, hipStream_t s)
 {
     if (a.generic) {
         launch_mfcc_gen(a, s);
@@ -440,38 +515,39 @@ void launch_mfcc(const MfccArgs &a, hipStream_t s)
     }
     if (a.small_tiles == 2) {  // a.tiles counts tiles of mfcc_frames_per_tile_small(frame_len, 1) frames
         const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWaveSmall) * sizeof(uint32_t);
-        hipLaunchKernelGGL(k_mfcc<kFramesPerWaveSmall>, dim3(grid), dim3(64 * kMfccWaves), lds, s, a);
+        hipLaunchKernelGGL(k_mfcc<kFramesPerWaveSmall>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
         return;
     }
     if (a.small_tiles == 1) {  // ... of mfcc_frames_per_tile_small(frame_len, 0) frames
         const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWaveMid) * sizeof(uint32_t);
-        hipLaunchKernelGGL(k_mfcc<kFramesPerWaveMid>, dim3(grid), dim3(64 * kMfccWaves), lds, s, a);
+        hipLaunchKernelGGL(k_mfcc<kFramesPerWaveMid>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
         return;
     }
     const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWave) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_mfcc<kFramesPerWave>, dim3(grid), dim3(64 * kMfccWaves), lds, s, a);
+    hipLaunchKernelGGL(k_mfcc<kFramesPerWave>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
 }
 
 template <int kFPW, int kKind>
-static void launch_mfcc_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
+static void launch_mfcc_feat_kind(const MfccArgs &a, const MfccMagTab &tab, uint32_t *feat, uint32_t grid, hipStream_t s)
 {
     const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFPW) * sizeof(uint32_t);
-    hipLaunchKernelGGL((k_mfcc<kFPW, MfccFeatArgs<kKind>>), dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_feat_args<kKind>(a, feat));
+    hipLaunchKernelGGL((k_mfcc<kFPW, MfccTabArgs<MfccFeatArgs<kKind>>>), dim3(grid), dim3(64 * kMfccWaves), lds, s,
+                       mfcc_tab_args(mfcc_feat_args<kKind>(a, feat), tab));
 }
 template <int kFPW>
-static void launch_mfcc_feat_form(const MfccArgs &a, int kind, uint32_t *feat, uint32_t grid, hipStream_t s)
+static void launch_mfcc_feat_form(const MfccArgs &a, const MfccMagTab &tab, int kind, uint32_t *feat, uint32_t grid, hipStream_t s)
 {
     switch (kind) {
-    case SR_FEAT_FFT: launch_mfcc_feat_kind<kFPW, SR_FEAT_FFT>(a, feat, grid, s); break;
-    case SR_FEAT_MAG: launch_mfcc_feat_kind<kFPW, SR_FEAT_MAG>(a, feat, grid, s); break;
-    case SR_FEAT_MEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_MEL>(a, feat, grid, s); break;
-    case SR_FEAT_LOGMEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_LOGMEL>(a, feat, grid, s); break;
+    case SR_FEAT_FFT: launch_mfcc_feat_kind<kFPW, SR_FEAT_FFT>(a, tab, feat, grid, s); break;
+    case SR_FEAT_MAG: launch_mfcc_feat_kind<kFPW, SR_FEAT_MAG>(a, tab, feat, grid, s); break;
+    case SR_FEAT_MEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_MEL>(a, tab, feat, grid, s); break;
+    case SR_FEAT_LOGMEL: launch_mfcc_feat_kind<kFPW, SR_FEAT_LOGMEL>(a, tab, feat, grid, s); break;
     default: break;  // (kinds are checked by the entry point)
     }
 }
 
 // the feature kernels in the form and grid launch_mfcc would pick for the same arguments
-void launch_mfcc_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s)
+void launch_mfcc_features(const MfccArgs &a, const MfccMagTab &tab, int kind, uint32_t *feat, hipStream_t s)
 {
     if (a.generic) {
         launch_mfcc_gen_features(a, kind, feat, s);
@@ -483,11 +559,11 @@ void launch_mfcc_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream
     if (a.frame_len == 320)
         launch_mfcc_ext_features(a, kind, feat, grid, s);
     else if (a.small_tiles == 2)
-        launch_mfcc_feat_form<kFramesPerWaveSmall>(a, kind, feat, grid, s);
+        launch_mfcc_feat_form<kFramesPerWaveSmall>(a, tab, kind, feat, grid, s);
     else if (a.small_tiles == 1)
-        launch_mfcc_feat_form<kFramesPerWaveMid>(a, kind, feat, grid, s);
+        launch_mfcc_feat_form<kFramesPerWaveMid>(a, tab, kind, feat, grid, s);
     else
-        launch_mfcc_feat_form<kFramesPerWave>(a, kind, feat, grid, s);
+        launch_mfcc_feat_form<kFramesPerWave>(a, tab, kind, feat, grid, s);
 }
 
 }  // namespace sr

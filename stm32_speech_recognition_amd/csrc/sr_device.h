@@ -24,6 +24,7 @@ enum DevHook {
     kHookDtwDebug,        // "dtw_debug":   print the DTW plan when a store is set, and the full-DP scorer's form per launch
     kHookCellsLiteral,    // "cells_literal": k_dtw_cells walks every pair literally (the fallback of walks that leave the band)
     kHookMagCheapOff,     // "mag_cheap_off": sr_create behaves as if the device sweep of the cheap magnitude form had failed (bound 0)
+    kHookMagTableOff,     // "mag_table_off": k_mfcc sends QUIET frames down the MID tier (cheap root, literal filterbank term) instead of the table
     kHookStreamTile,      // "stream_tile_frames": frames per tile of the stream VAD scan (16..1024, a multiple of 16)
     kHookCount
 };
@@ -129,6 +130,13 @@ struct MfccArgs {
     uint32_t hop, n_mel, n_coef;
     DevTables t;
 };
+// k_mfcc alone also takes the QUIET-tier magnitude table.  A block of its own, appended to the kernel's arguments by the
+// launcher (k_mfcc.hip MfccTabArgs): MfccArgs and DevTables are shared with k_mfcc_ext / k_mfcc_gen, whose argument layout --
+// and with it their code -- stays as it is.
+struct MfccMagTab {
+    const uint16_t *mag_q;   // [kMagTabEntries] magnitudes << 2 (sr_tables.h), read through a buffer resource of exactly that size
+    uint32_t mag_table_off;  // -DSR_TESTING build only: development hook "mag_table_off"
+};
 
 // launch arguments of the feature kernels (sr_frame_features_batch_dev): the frame kernel's block + the feature output
 // feat[B][max_frames][width], kind = SR_FEAT_*.  A separate type, so that the frame kernels' own argument block stays as it is;
@@ -198,10 +206,10 @@ void launch_select_segment(const sr_vad_rec *in, sr_vad_rec *out, uint32_t B, ui
                            uint32_t frame_len, uint32_t hop, hipStream_t s);
 void launch_vad_stream(const VadStreamArgs &a, bool sad, hipStream_t s);  // the three passes (sad: 16-bit mid, see k_vad)
 void launch_stream_records(const StreamRecArgs &a, uint32_t n, hipStream_t s);
-void launch_mfcc(const MfccArgs &a, hipStream_t s);
+void launch_mfcc(const MfccArgs &a, const MfccMagTab &tab, hipStream_t s);
 void launch_mfcc_gen(const MfccArgs &a, hipStream_t s);  // GENERIC front end (k_mfcc_gen.hip)
 // the same kernels' per-frame intermediate values (kind = SR_FEAT_*) into feat[B][max_frames][width], MFCC rows into a.mfcc
-void launch_mfcc_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s);
+void launch_mfcc_features(const MfccArgs &a, const MfccMagTab &tab, int kind, uint32_t *feat, hipStream_t s);
 void launch_mfcc_gen_features(const MfccArgs &a, int kind, uint32_t *feat, hipStream_t s);
 uint32_t mfcc_frames_per_tile(uint32_t frame_len);        // frames one work item of the frame kernel covers
 uint32_t mfcc_frames_per_tile_small(uint32_t frame_len, uint32_t which);  // ... of its forms for underfilled launches (MfccArgs::small_tiles - 1)

@@ -21,7 +21,7 @@ static std::atomic<int64_t> g_hooks[kHookCount];
 int64_t dev_hook(DevHook h) { return g_hooks[h].load(std::memory_order_relaxed); }
 static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc", "mfcc_grid", "perturb_log_thr",
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
-                                                   "mag_cheap_off", "stream_tile_frames"};
+                                                   "mag_cheap_off", "mag_table_off", "stream_tile_frames"};
 #endif
 }  // namespace sr
 
@@ -93,6 +93,15 @@ static int front_end_of(const sr_config *cfg, FrontEnd *fe)
 
 int sr_log_table_mismatches(void) { return log_table_mismatches(); }
 uint32_t sr_mag_cheap_bound(const sr_engine *h) { return h ? h->mag_cheap_max : 0u; }
+
+// Host-only: the first n entries of the QUIET-tier magnitude table sr_create uploads; returns the table's length
+uint32_t sr_mag_table(uint16_t *out, uint32_t n)
+{
+    std::vector<uint16_t> t;
+    gen_mag_q(t);
+    if (out) std::memcpy(out, t.data(), std::min<size_t>(n, t.size()) * 2);
+    return (uint32_t)t.size();
+}
 
 // 1 in the -DSR_TESTING build (development hooks compiled in), 0 in the product library
 int sr_testing_build(void)
@@ -270,14 +279,15 @@ int sr_create(const sr_config *cfg, sr_engine **out)
         const void *src;
         size_t bytes;
         size_t off;
-    } parts[16] = {{t.hamm.data(), t.hamm.size() * 2, 0},       {t.tri_even.data(), t.tri_even.size() * 2, 0},
+    } parts[17] = {{t.hamm.data(), t.hamm.size() * 2, 0},       {t.tri_even.data(), t.tri_even.size() * 2, 0},
                   {t.tri_odd.data(), t.tri_odd.size() * 2, 0}, {t.tri_cen.data(), t.tri_cen.size() * 2, 0},
                   {t.dct.data(), t.dct.size(), 0},             {t.tw_a.data(), t.tw_a.size() * 4, 0},
                   {t.tw_b.data(), t.tw_b.size() * 4, 0},       {t.log_thr.data(), t.log_thr.size() * 4, 0},
                   {t.w512_a.data(), t.w512_a.size() * 4, 0},   {t.w512_b.data(), t.w512_b.size() * 4, 0},
                   {te32.data(), te32.size() * 4, 0},           {to32.data(), to32.size() * 4, 0},
                   {t.tie_delta.data(), t.tie_delta.size(), 0}, {hpk.data(), hpk.size() * 4, 0},
-                  {tem.data(), tem.size() * 4, 0},             {tom.data(), tom.size() * 4, 0}};
+                  {tem.data(), tem.size() * 4, 0},             {tom.data(), tom.size() * 4, 0},
+                  {t.mag_q.data(), t.mag_q.size() * 2, 0}};
     if (t.tie_delta.size() != (size_t)kTieMax) {
         delete h;
         return fail(SR_ERR_BAD_CONFIG, "internal: DTW tie-threshold table does not fit 8 bits");
@@ -312,6 +322,7 @@ int sr_create(const sr_config *cfg, sr_engine **out)
     h->dev.hamm_pk = (const uint32_t *)(base + parts[13].off);
     h->dev.tri_even_m = (const uint32_t *)(base + parts[14].off);
     h->dev.tri_odd_m = (const uint32_t *)(base + parts[15].off);
+    h->dev_mag_q = (const uint16_t *)(base + parts[16].off);
     // The cheap magnitude form of k_mfcc's QUIET / MID tiers rests on a property of this chip's v_sqrt_f32, so it is checked
     // here, on the device the engine will run on, over the WHOLE range it is used on (70 172 values, microseconds): any
     // difference from the exactly corrected root and every frame takes the exact form (bound 0) -- parity never depends on a

@@ -90,6 +90,7 @@ struct sr_engine {
     uint32_t noise_len = 0, atap_frm = 0;
     uint32_t n_cu = 256;  // compute units of the engine's device (sr_create)
     LdsBudget lds;        // its LDS (sr_create): every DTW launch shape is planned from these figures, not MI355X's
+    const uint16_t *dev_mag_q = nullptr;  // QUIET-tier magnitude table inside table_blob (kMagTabEntries x u16, its own 256-byte-aligned part)
     uint32_t mag_cheap_max = 0;  // kMagCheapMax once the device sweep at sr_create has confirmed the cheap magnitude form on this chip, else 0
     uint32_t mfcc_tile = 64, mfcc_tile_mid = 64, mfcc_tile_small = 64, mfcc_grid_cap = 0;  // frames per k_mfcc work item (batch form / the two forms for underfilled launches), resident workgroups
     uint32_t frame_len = 160, hop = 80;          // 160/80 reference, 320/160 extension, or the generic front end's framing
@@ -182,6 +183,7 @@ int order_after_scratch_users(sr_engine *h, hipStream_t s);
 VadArgs vad_args(const sr_engine *h, const uint16_t *pcm, uint64_t stride, uint32_t buf_len, uint32_t noise_len, uint32_t B,
                      sr_vad_rec *vad, const sr_atap *atap_in = nullptr, uint64_t *dbg = nullptr);
 MfccArgs mfcc_args(const sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B, const sr_vad_rec *d_vad, int16_t *d_mfcc);
+MfccMagTab mfcc_mag_tab(const sr_engine *h);  // what launch_mfcc / launch_mfcc_features take next to it
 DtwArgs dtw_args(const sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_vad, const uint32_t *d_in_frames, uint32_t B,
                      uint32_t *d_scores, sr_result *d_results);
 void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid);

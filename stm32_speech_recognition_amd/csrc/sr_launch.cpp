@@ -106,6 +106,8 @@ MfccArgs mfcc_args(const sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_strid
     return a;
 }
 
+MfccMagTab mfcc_mag_tab(const sr_engine *h) { return MfccMagTab{h->dev_mag_q, dev_hook(kHookMagTableOff) ? 1u : 0u}; }
+
 int sr_mfcc_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t B, const sr_vad_rec *d_vad,
                       int16_t *d_mfcc, void *stream)
 {
@@ -113,7 +115,7 @@ int sr_mfcc_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, 
     if (pcm_stride >= (1ull << 31)) return fail(SR_ERR_BAD_ARG, "pcm_stride must be below 2^31 samples");
     if (int rcb = check_batch(h, B)) return rcb;
     ENTER_DEVICE(h);
-    launch_mfcc(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), (hipStream_t)stream);
+    launch_mfcc(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), mfcc_mag_tab(h), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SR_OK;
 }
@@ -294,7 +296,7 @@ int sr_recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_str
         if (prof) HIP_TRY(hipEventRecord(ev[0], sc));
         launch_vad(va, sc);
         if (prof) HIP_TRY(hipEventRecord(ev[1], sc));
-        launch_mfcc(mfcc_args(h, pc, pcm_stride, n, vc, mc), sc);
+        launch_mfcc(mfcc_args(h, pc, pcm_stride, n, vc, mc), mfcc_mag_tab(h), sc);
         if (prof) HIP_TRY(hipEventRecord(ev[2], sc));
         DtwArgs da = dtw_args(h, mc, vc, nullptr, n, d_scores + (size_t)b0 * h->K, d_results + b0);
         const bool scanned = launch_dtw_auto(h, da, b0, sc, s);
@@ -350,7 +352,7 @@ int sr_recognize_segments_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_
     bool counted = false;
     for (uint32_t sg = 0; sg < h->cfg.max_seg; sg++) {
         launch_select_segment(d_vad, h->s_vad2.p, B, sg, h->cfg.max_frames, h->frame_len, h->hop, s);
-        launch_mfcc(mfcc_args(h, d_pcm, pcm_stride, B, h->s_vad2.p, h->s_mfcc.p), s);
+        launch_mfcc(mfcc_args(h, d_pcm, pcm_stride, B, h->s_vad2.p, h->s_mfcc.p), mfcc_mag_tab(h), s);
         DtwArgs da = dtw_args(h, h->s_mfcc.p, h->s_vad2.p, nullptr, B, d_scores + (size_t)sg * B * h->K,
                               d_results + (size_t)sg * B);
         if (launch_dtw_auto(h, da, 0, s, s)) counted = true;
@@ -409,7 +411,7 @@ int sr_frame_features_batch_dev(sr_engine *h, int kind, const uint16_t *d_pcm, u
         if ((rc = h->s_mfcc.reserve((size_t)B * h->cfg.max_frames * h->nc))) return rc;
         d_mfcc = h->s_mfcc.p;
     }
-    launch_mfcc_features(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), kind, d_feat, s);
+    launch_mfcc_features(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), mfcc_mag_tab(h), kind, d_feat, s);
     HIP_TRY(hipGetLastError());
     if (own_scratch) return mark_scratch_user(h, s);
     return SR_OK;

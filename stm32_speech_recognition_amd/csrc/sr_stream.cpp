@@ -98,7 +98,7 @@ int stream_recognize(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, u
                          h->s_st_rows.p, row, h->s_st_recs.p};
         launch_stream_records(ra, m, s);
         int16_t *mc = d_mfcc ? d_mfcc + (size_t)r0 * R * nc : h->s_mfcc.p;
-        launch_mfcc(mfcc_args(h, h->s_st_rows.p, row, m, h->s_st_recs.p, mc), s);
+        launch_mfcc(mfcc_args(h, h->s_st_rows.p, row, m, h->s_st_recs.p, mc), mfcc_mag_tab(h), s);
         DtwArgs da = dtw_args(h, mc, h->s_st_recs.p, nullptr, m, d_scores ? d_scores + (size_t)r0 * K : h->s_scores.p, d_results + r0);
         if (launch_dtw_auto(h, da, 0, s, s)) counted = true;
         else launch_argmin(da, s);

@@ -182,8 +182,18 @@ static void gen_tie_delta(HostTables &t)
     }
 }
 
+// MFCC.C:58 takes (u32)(sqrtf(re^2 + im^2) * 10) of every bin.  For the QUIET tier's range the frame kernel reads it from this
+// table instead of evaluating it: the very expression, on the host (sqrtf is an IEEE-exact operation and the multiply stays a
+// separate IEEE multiply -- the build is -ffp-contract=off -- so the table does not depend on the libm), pre-shifted by 2.
+void gen_mag_q(std::vector<uint16_t> &out)
+{
+    out.resize(kMagTabEntries);
+    for (uint32_t n = 0; n < kMagTabEntries; n++) out[n] = (uint16_t)(((uint32_t)(sqrtf((float)n) * 10.0f)) << 2);
+}
+
 void build_tables(HostTables &t, const FrontEnd &fe)
 {
+    gen_mag_q(t.mag_q);
     gen_tie_delta(t);
     gen_hamm(t, fe);
     gen_tri(t, fe);

@@ -50,6 +50,11 @@ static_assert(1638u * 1638u <= kMelFusedMaxE && 100ull * (kMagSmallMax + 1) < 16
 // hands the kernel a bound of 0 -- every frame then takes the exactly corrected root -- if the sweep finds a difference.
 constexpr uint32_t kMagCheapMax = 70171;
 static_assert(kMagSmallMax <= kMagCheapMax, "the quiet tier lies inside the cheap-magnitude range");
+// QUIET-tier magnitudes from a table (round 7): mag_q[n] = (u32)(sqrtf((float)n) * 10) << 2 for n = 0..kMagSmallMax, the
+// reference expression of MFCC.C:58 evaluated on the host (IEEE sqrtf, then a separate IEEE multiply).  The << 2 makes the
+// square E << 4, the operand the fused filterbank term wants; 1638 << 2 = 6552 fits 16 bits.  52.4 KB, L2-resident.
+constexpr uint32_t kMagTabEntries = kMagSmallMax + 1;
+static_assert((1638u << 2) <= 0xFFFFu && 2 * kMagTabEntries < (1u << 17), "table entries fit u16, table fits a raw buffer's range");
 constexpr uint32_t kMelTriMax = 1599;                  // largest weight whose multiplier fits 32 bits
 constexpr uint32_t mel_fused_multiplier(uint32_t tri) { return (uint32_t)((((uint64_t)tri << 28) + 99u) / 100u); }
 
@@ -83,9 +88,11 @@ struct HostTables {
     // T(g) = g*(g + 2) + tie_delta[g] (one 24-bit multiply-add on the device).  Exact squares up to 2^24 convert to
     // float exactly, so the entry is 1 for g < 4096; above, (float)d rounds d and T(g) falls a little short of (g + 1)^2.
     std::vector<int8_t> tie_delta;
+    std::vector<uint16_t> mag_q;     // [kMagTabEntries] QUIET-tier magnitudes << 2 (see kMagTabEntries)
 };
 
 void build_tables(HostTables &t, const FrontEnd &fe);
+void gen_mag_q(std::vector<uint16_t> &out);  // the QUIET-tier magnitude table alone (independent of the front end)
 // entries of the log step table where this host's libm disagreed with the shipped positions at the last build_tables
 int log_table_mismatches();
 
