@@ -1,6 +1,7 @@
 // Shared by the host translation units of the library (sr_engine.cpp: lifecycle, template store, settings;
-// sr_launch.cpp: the device-resident entry points and kernel sequencing; sr_host.cpp: host-buffer entry points, staging,
-// diagnostics): the engine handle, device-memory / device-selection helpers and the launch-argument builders.
+// sr_launch.cpp: the device-resident entry points and kernel sequencing; sr_host.cpp: host-buffer entry points and
+// diagnostics, whose transport is sr_host_call.h): the engine handle, device-memory / device-selection helpers and the
+// launch-argument builders.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,14 @@ struct DevBuf {
     }
 };
 
+// a DevBuf that lives for one call: freed on every return path
+template <typename T>
+struct TmpDevBuf : DevBuf<T> {
+    TmpDevBuf() = default;
+    TmpDevBuf(const TmpDevBuf &) = delete;
+    ~TmpDevBuf() { this->release(); }
+};
+
 }  // namespace sr
 
 using namespace sr;  // internal header of three host units of one library: the handle below is a global C type built from sr:: parts
@@ -95,6 +104,7 @@ struct sr_engine {
     uint32_t mfcc_tile = 64, mfcc_tile_mid = 64, mfcc_tile_small = 64, mfcc_grid_cap = 0;  // frames per k_mfcc work item (batch form / the two forms for underfilled launches), resident workgroups
     uint32_t frame_len = 160, hop = 80;          // 160/80 reference, 320/160 extension, or the generic front end's framing
     uint32_t nc = 12, n_mel = 24;                // s16 per feature row (n_coef), Mel filters
+    size_t mfcc_elems(size_t B) const { return B * cfg.max_frames * nc; }  // s16 in the feature records of B utterances
     bool generic = false;                        // GENERIC front end (k_mfcc_gen; k_dtw_lds's 16-wide form when nc > 12)
     uint32_t v_durmin = 8, s_durmax = 11;        // VAD.C:72-75 in frames
     HostTables host;
@@ -149,8 +159,10 @@ struct sr_engine {
     bool scratch_pending = false;
     // host-buffer pipeline (sr_recognize_batch): upload of chunk c+1 overlaps the kernels of chunk c
     hipStream_t st_copy = nullptr, st_comp = nullptr;
-    // small host-buffer calls (spch_recg: one capture): pinned staging area for the upload, results written by the kernel
-    // straight into pinned host memory -- one stream synchronisation per call instead of a blocking copy each way
+    // small host-buffer calls (spch_recg: one capture), HostCall's pinned mode in sr_host_call.h: one mapped pinned area of
+    // kPinTotal bytes -- staging for what goes up, then the part results land in (written by the kernel itself or by
+    // asynchronous copies), all on st_comp: one stream synchronisation per call instead of a blocking copy each way.
+    // Allocated on the first small call (ensure_pin); pin_failed = the host refused it, every call stays blocking
     void *pin_buf = nullptr;
     size_t pin_cap = 0;
     bool pin_failed = false;

@@ -253,7 +253,7 @@ static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm
         d_vad = h->s_vad.p;
     }
     if (!d_mfcc) {
-        if ((rc = h->s_mfcc.reserve((size_t)B * h->cfg.max_frames * h->nc))) return rc;
+        if ((rc = h->s_mfcc.reserve(h->mfcc_elems(B)))) return rc;
         d_mfcc = h->s_mfcc.p;
     }
     if (!d_scores) {
@@ -296,7 +296,7 @@ static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm
         hipEvent_t *ev = prof ? &h->ev[5 * (h->ev_used + c)] : nullptr;
         const uint16_t *pc = d_pcm + (size_t)b0 * pcm_stride;
         sr_vad_rec *vc = d_vad + b0;
-        int16_t *mc = d_mfcc + (size_t)b0 * h->cfg.max_frames * h->nc;
+        int16_t *mc = d_mfcc + h->mfcc_elems(b0);
         VadArgs va = vad_args(h, pc, pcm_stride, buf_len, h->noise_len, n, vc);
         if (prof) HIP_TRY(hipEventRecord(ev[0], sc));
         launch_vad(va, sc);
@@ -363,7 +363,7 @@ int sr_recognize_segments_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_
     }
     if ((rc = order_after_scratch_users(h, s))) return rc;  // s_vad2 / s_mfcc are always the engine's
     if ((rc = h->s_vad2.reserve(B))) return rc;
-    if ((rc = h->s_mfcc.reserve((size_t)B * h->cfg.max_frames * h->nc))) return rc;
+    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(B)))) return rc;
     if (!d_scores) {
         if ((rc = h->s_scores.reserve((size_t)B * h->K * h->cfg.max_seg))) return rc;
         d_scores = h->s_scores.p;
@@ -429,7 +429,7 @@ int sr_frame_features_batch_dev(sr_engine *h, int kind, const uint16_t *d_pcm, u
     if (own_scratch) {  // the kernels write MFCC rows anyway: into the engine's scratch
         int rc;
         if ((rc = order_after_scratch_users(h, s))) return rc;
-        if ((rc = h->s_mfcc.reserve((size_t)B * h->cfg.max_frames * h->nc))) return rc;
+        if ((rc = h->s_mfcc.reserve(h->mfcc_elems(B)))) return rc;
         d_mfcc = h->s_mfcc.p;
     }
     launch_mfcc_features(mfcc_args(h, d_pcm, pcm_stride, B, d_vad, d_mfcc), mfcc_mag_tab(h), kind, d_feat, s);

@@ -1,7 +1,7 @@
 // Word-level N-best (include/sr_engine.h, "words instead of slots"): the slot -> word map of an engine, the grouping of the
 // store's slots under it that k_nbest.hip reads, and the stage-level entry points.  The whole-path and stream forms launch the
 // same kernel from sr_launch.cpp / sr_host.cpp / sr_stream.cpp.
-#include "sr_engine_internal.h"
+#include "sr_host_call.h"
 
 #include <unordered_map>
 
@@ -137,17 +137,16 @@ int sr_nbest_batch(sr_engine *h, const uint32_t *scores, uint32_t n_rows, uint32
     if (int rc = check_nbest(h, n_best, nbest)) return rc;
     if (n_rows > 0xFFFFFFF0u) return fail(SR_ERR_BAD_ARG, "too many rows");
     if (!n_rows) return SR_OK;
-    ENTER_DEVICE(h);
+    ENTER_HOST_CALL(h);
     int rc;
-    if ((rc = order_after_scratch_users(h, nullptr))) return rc;  // the null stream reuses the scratch buffers
     if ((rc = h->s_scores.reserve((size_t)n_rows * h->K))) return rc;
     if ((rc = h->s_nbest.reserve((size_t)n_rows * n_best))) return rc;
     if ((rc = h->s_nmatched.reserve(n_rows))) return rc;
-    HIP_TRY(hipMemcpy(h->s_scores.p, scores, (size_t)n_rows * h->K * 4, hipMemcpyHostToDevice));
+    COPY_UP(h->s_scores.p, scores, (size_t)n_rows * h->K * 4);
     launch_nbest(nbest_args(h, h->s_scores.p, n_rows, NbestOut{n_best, h->s_nbest.p, h->s_nmatched.p}, 0), nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(nbest, h->s_nbest.p, (size_t)n_rows * n_best * sizeof(sr_nbest_entry), hipMemcpyDeviceToHost));
-    if (n_matched) HIP_TRY(hipMemcpy(n_matched, h->s_nmatched.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+    COPY_DOWN(nbest, h->s_nbest.p, (size_t)n_rows * n_best * sizeof(sr_nbest_entry));
+    if (n_matched) COPY_DOWN(n_matched, h->s_nmatched.p, (size_t)n_rows * 4);
     return SR_OK;
 }
 

@@ -1,7 +1,7 @@
 // Stream recognition (include/sr_engine.h, "Stream recognition"): every segment of recordings of any length -- the stream VAD
 // of k_vad_stream.hip (three launches), then each segment recognised by the frame kernel, DTW and the slot scan exactly as
 // segment 0 of sr_recognize_batch_dev.  EXTENSION, NO REFERENCE COUNTERPART (the firmware stops at 3 segments, VAD.C:203).
-#include "sr_engine_internal.h"
+#include "sr_host_call.h"
 
 using namespace sr;
 
@@ -193,38 +193,36 @@ static int recognize_stream_host(sr_engine *h, const uint16_t *pcm, uint64_t pcm
         if (!atap_in && (len[b] < h->noise_len || len[b] <= h->frame_len))
             return fail(SR_ERR_BAD_ARG, "len[" + std::to_string(b) + "] shorter than the noise head and a frame");
     }
-    ENTER_DEVICE(h);
+    ENTER_HOST_CALL(h);
     int rc;
-    if ((rc = order_after_scratch_users(h, nullptr))) return rc;  // the null stream reuses the scratch buffers
     if (B == 0) {
         seg_offsets[0] = 0;
         if (n_segs) *n_segs = 0;
         return SR_OK;
     }
-    const uint64_t ds = ((uint64_t)buf_len + 7) & ~7ull;
-    if ((rc = h->s_pcm.reserve((size_t)B * ds))) return rc;
-    HIP_TRY(hipMemcpy2D(h->s_pcm.p, ds * 2, pcm, pcm_stride * 2, (size_t)buf_len * 2, B, hipMemcpyHostToDevice));
+    uint64_t ds = 0;
+    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
     uint32_t *d_len = nullptr;
     sr_atap *d_atap_in = nullptr;
     if (len) {
         if ((rc = h->s_u32a.reserve(B))) return rc;
         d_len = h->s_u32a.p;
-        HIP_TRY(hipMemcpy(d_len, len, (size_t)B * 4, hipMemcpyHostToDevice));
+        COPY_UP(d_len, len, (size_t)B * 4);
     }
     if (atap_in) {
         if ((rc = h->s_atap.reserve(B))) return rc;
         d_atap_in = h->s_atap.p;
-        HIP_TRY(hipMemcpy(d_atap_in, atap_in, (size_t)B * sizeof(sr_atap), hipMemcpyHostToDevice));
+        COPY_UP(d_atap_in, atap_in, (size_t)B * sizeof(sr_atap));
     }
     if ((rc = h->s_st_segs.reserve(std::max(1u, max_segs)))) return rc;
     if ((rc = h->s_st_off.reserve((size_t)B + 1))) return rc;
     if ((rc = stream_segment(h, h->s_pcm.p, ds, buf_len, d_len, B, d_atap_in, max_segs, h->s_st_segs.p, h->s_st_off.p, nullptr,
                              nullptr)))
         return rc;
-    HIP_TRY(hipMemcpy(seg_offsets, h->s_st_off.p, ((size_t)B + 1) * 4, hipMemcpyDeviceToHost));  // syncs on the count
+    COPY_DOWN(seg_offsets, h->s_st_off.p, ((size_t)B + 1) * 4);  // syncs on the count
     const uint32_t total = seg_offsets[B], n = std::min(total, max_segs);
     if (n_segs) *n_segs = total;
-    if (n) HIP_TRY(hipMemcpy(segs, h->s_st_segs.p, (size_t)n * sizeof(sr_stream_seg), hipMemcpyDeviceToHost));
+    if (n) COPY_DOWN(segs, h->s_st_segs.p, (size_t)n * sizeof(sr_stream_seg));
     if ((!results && !nb) || !n) return SR_OK;
     const uint32_t R = h->cfg.max_frames, nc = h->nc, K = h->K;
     NbestOut d_nb{};
@@ -240,12 +238,12 @@ static int recognize_stream_host(sr_engine *h, const uint16_t *pcm, uint64_t pcm
                                scores ? h->s_scores.p : nullptr, mfcc ? h->s_mfcc.p : nullptr, nullptr, nb ? &d_nb : nullptr)))
         return rc;
     if (nb) {
-        HIP_TRY(hipMemcpy(nb->out, h->s_nbest.p, (size_t)n * nb->n_best * sizeof(sr_nbest_entry), hipMemcpyDeviceToHost));
-        if (nb->n_matched) HIP_TRY(hipMemcpy(nb->n_matched, h->s_nmatched.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        COPY_DOWN(nb->out, h->s_nbest.p, (size_t)n * nb->n_best * sizeof(sr_nbest_entry));
+        if (nb->n_matched) COPY_DOWN(nb->n_matched, h->s_nmatched.p, (size_t)n * 4);
     }
-    if (results) HIP_TRY(hipMemcpy(results, h->s_results.p, (size_t)n * sizeof(sr_result), hipMemcpyDeviceToHost));
-    if (scores) HIP_TRY(hipMemcpy(scores, h->s_scores.p, (size_t)n * K * 4, hipMemcpyDeviceToHost));
-    if (mfcc) HIP_TRY(hipMemcpy(mfcc, h->s_mfcc.p, (size_t)n * R * nc * 2, hipMemcpyDeviceToHost));
+    if (results) COPY_DOWN(results, h->s_results.p, (size_t)n * sizeof(sr_result));
+    if (scores) COPY_DOWN(scores, h->s_scores.p, (size_t)n * K * 4);
+    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, (size_t)n * R * nc * 2);
     return SR_OK;
 }
 

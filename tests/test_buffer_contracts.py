@@ -31,7 +31,8 @@ hop, so "starts at sample 1" exists only for the entry points that take explicit
 sr_frame_features_batch), where it is the first record of every call.
 
 Wall time on one MI355X, measured in one session: this module 18 s (58 tests, 17 s inside pytest); the -m gpu suite without
-it 170 s (220 tests), at the parent commit and with this change alike.
+it 170 s (220 tests), at the parent commit and with this change alike.  With the four cases at the capacity edge of the pinned
+staging area (16 / 17 capture rows, 283 / 284 feature records): 62 tests, 15 to 17 s.
 """
 import ctypes as C
 import itertools
@@ -65,8 +66,11 @@ P, U32, U64, I32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 # offset, stride, lead, mode, poison and stream at least once per front end
 DEV_CASES = [(1, 0, 0, 0, 0, "adc", False), (5, -1, 8, 8, 1, "ffff", True), (63, -3, 4104, 4104, 2, "adc", True),
              (65, -7, 0, 8, 3, "ffff", False), (1023, 5, 8, 4104, 0, "adc", False), (1025, -1, 4104, 0, 1, "ffff", True)]
-# host forms: (B, buf_len - base, pcm_stride - buf_len, lead, mode, poison); odd strides, 2-byte aligned bases
-HOST_CASES = {"ref": [(5, -1, 1, 1, 0, "adc"), (65, 5, 4105, 1, 1, "ffff"), (1025, -7, 3, 0, 0, "adc")],
+# host forms: (B, buf_len - base, pcm_stride - buf_len, lead, mode, poison); odd strides, 2-byte aligned bases.  B = 16 / 17 at
+# buf_len = base = 9 680: rows of 19 360 bytes, the most that fit the 327 680 bytes of the pinned staging area's upload part
+# (sr_mfcc_batch_status adds a 48-byte record per row: 16 x 19 408 + 128 = 310 656) and the first batch that does not
+HOST_CASES = {"ref": [(5, -1, 1, 1, 0, "adc"), (65, 5, 4105, 1, 1, "ffff"), (1025, -7, 3, 0, 0, "adc"),
+                      (16, 0, 1, 1, 0, "adc"), (17, 0, 1, 1, 0, "ffff")],
               "ext": [(5, -3, 9, 1, 1, "ffff"), (63, 0, 1, 3, 0, "adc")],
               "gen": [(1, -7, 0, 1, 0, "adc"), (65, -1, 7, 5, 2, "ffff")],
               "gen32": [(5, 5, 3, 1, 1, "adc"), (63, -3, 1, 0, 0, "ffff")]}
@@ -804,6 +808,27 @@ def test_dtw_device_forms_on_records_with_poison_rows(fronts, front):
                 g.check()
     finally:
         eng.set_small_launch(0)
+
+
+@pytest.mark.parametrize("B", [283, 284])
+def test_dtw_host_form_on_poisoned_records_at_the_edge_of_the_staging_area(fronts, B):
+    """sr_dtw_batch in every small-launch mode on the largest batch of records that fits the upload part of the pinned
+    staging area and on the first that does not: a record of R = 48 frames x 12 coefficients is 1 152 bytes + 4 of its frame
+    count, + 128 for the two blocks, against 327 680 bytes -- 283 records are 327 276, 284 are 328 432.  Frame counts 1..48
+    (1, 2 and R among them), poison rows at and after frames[b]; every score and every result record equals the oracle's"""
+    c = fronts("ref")
+    assert c.nc == 12 and 283 * (R * 12 * 2 + 4) + 128 <= 327680 < 284 * (R * 12 * 2 + 4) + 128
+    rng = np.random.default_rng(B)
+    frames = rng.integers(1, R + 1, B).astype(np.uint32)
+    frames[:3], frames[-1] = (1, 2, R), R
+    im = poison_feature_rows(rng.integers(-900, 900, (B, R, c.nc)).astype(np.int16), frames)
+    vd = np.zeros(B, VAD_DTYPE)
+    vd["frm_num"] = frames
+    want_sc, want_res = dtw_expected(c, im, frames, vd)
+    assert (want_sc[:, c.valid != 0] != DIS_ERR).sum() >= B and (want_sc[:, c.valid == 0] == DIS_ERR).all()
+    sc, res = _dtw_all_modes(c.eng, im, frames)
+    assert np.array_equal(sc, want_sc), np.argwhere(sc != want_sc)[:4].tolist()
+    assert res.tobytes() == want_res.tobytes()
 
 
 def test_get_mdl_batch_on_records_with_poison_rows(fronts):
