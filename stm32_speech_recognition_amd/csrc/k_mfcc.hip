@@ -3,6 +3,8 @@
 // Every kernel reproduces the reference's integer arithmetic bit for bit; cited lines are relative to the reference tree.
 #include "sr_fft_dev.h"
 
+#include <type_traits>
+
 #ifndef SR_MEL_CHUNKED
 #define SR_MEL_CHUNKED 1  // experiment switch (profiles/experiments/RESULTS.md, round 6): 0 = bin-major scratch order of round 5
 #endif
@@ -26,6 +28,21 @@ constexpr int kFramesPerWave = 16, kFramesPerWaveMid = 4, kFramesPerWaveSmall = 
 #endif
 constexpr int mfcc_tab_bins(int fpw) { return fpw == kFramesPerWave ? SR_MAG_TAB_BINS : 0; }
 static_assert(SR_MAG_TAB_BINS == 0 || SR_MAG_TAB_BINS == 4 || SR_MAG_TAB_BINS == 8, "table bins per lane");
+// switches of the batch form's two-frame loop (RESULTS.md, round 8; the defaults are the variant that was kept): SR_MFCC_PIPE 0 =
+// the serial loop of round 7; SR_MFCC_PIPE_PEEL 0 = one loop with its first / last-frame tests as scalar branches;
+// SR_MFCC_PIPE_VMCNT 0 = every wait drains the counter, 3 = the steady-state wait leaves the three younger sample loads in
+// flight (peeled form only: elsewhere they are not behind the gathers on every path)
+#ifndef SR_MFCC_PIPE
+#define SR_MFCC_PIPE 1
+#endif
+#ifndef SR_MFCC_PIPE_PEEL
+#define SR_MFCC_PIPE_PEEL 1
+#endif
+#ifndef SR_MFCC_PIPE_VMCNT
+#define SR_MFCC_PIPE_VMCNT (SR_MFCC_PIPE_PEEL ? 3 : 0)
+#endif
+static_assert(SR_MFCC_PIPE_VMCNT == 0 || (SR_MFCC_PIPE_VMCNT == 3 && SR_MFCC_PIPE_PEEL), "younger loads counted by the wait");
+constexpr bool mfcc_pipelined(int fpw) { return SR_MFCC_PIPE && mfcc_tab_bins(fpw) == 8; }
 // per-wave LDS: exchange/scratch words + windowed frame + filterbank outputs of the wave's frames
 // rows of the filterbank outputs and of the DCT tables are kMelPad = 25 words apart: in the DCT the lanes of a wave read
 // 6 different frames x 12 different coefficients rows at the same column, and a stride of 24 folds those onto 4 banks
@@ -67,6 +84,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     constexpr uint32_t kFeatW = (kFeat == SR_FEAT_FFT || kFeat == SR_FEAT_MAG) ? kBins : kMel;  // feature words per frame
     constexpr int kWaveLdsWords = mfcc_wave_lds_words(kFPW);
     constexpr int kTabBins = mfcc_tab_bins(kFPW);
+    constexpr bool kPipe = mfcc_pipelined(kFPW);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_dctM[kCoef * kMelPad];
     __shared__ int s_dctS[kCoef * kMelPad];  // 32-bit: read with the wide LDS loads, no byte extraction
@@ -207,6 +225,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 if (i < kFrameLen) s_pp[k] = *(const u32_align2 *)(x + i - 1);
             }
         }
+        if constexpr (!kPipe)  // the forms without the table (and the feature variants of those): one frame at a time
         for (uint32_t fi = 0; fi < nf; fi++) {
             // ---- pre-emphasis + Hamming (MFCC.C:115-124); x[-1] is the sample before the frame
 #pragma unroll
@@ -407,6 +426,214 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 if constexpr (kFeat == SR_FEAT_MEL) frow[(f0 + fi) * kFeatW + lane] = hi - lo;
             }
             wave_sync();
+        } else {
+            // ---- the batch form: two frames in flight per wave (round 8).  Frame fi's BACK END (energies, filterbank, look-up)
+            // runs after frame fi+1's FFT front, so that a QUIET frame's eight gathers have a whole FFT front -- window, ten LDS
+            // reads, passes 2-3 -- to come back under, instead of stopping the wave once per frame.  Order of one iteration:
+            //   front(fi): xw -> v[][] in registers (buf is free from here) ; back end of fi-1 through buf -> powb[fi-1] ;
+            //   exchange, passes 4-5, nn[] of fi ; window(fi+1) -> xw (u[][] is in registers: buf is free again) ;
+            //   tier of fi: QUIET issues the gathers, MID / LOUD compute ; request the samples of fi+2.
+            // Carried over the iteration boundary: mq[8] (|X|*10 of the lane's bins; << 2 from the table in a QUIET frame, plain
+            // otherwise -- umul24(q, q) serves both, as in the serial loop) and the wave-uniform flag pq (that frame was QUIET).
+            // vmcnt is ONE in-order counter and the compiler does not count the gathers: any wait it writes for an OLDER load
+            // between the gathers and the back end's explicit wait would drain them there.  Hence window(fi+1), the consumer of the
+            // prefetched samples, sits BEFORE the gathers and the next request AFTER them; a feature store never sits in between.
+            // Found in the disassembly of k_mfcc<16> (gfx950, -O3): on the QUIET path from the last gather to the explicit wait
+            // there are the three sample loads, the loop branch and the whole FFT front -- no s_waitcnt that names vmcnt, and no
+            // instruction that reads one of the eight gather registers (the compiler keeps mq[] in the same VGPRs on all paths;
+            // a copy there would read a register still in flight: look again after any change to this loop).
+            uint32_t mq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            bool pq = true;
+            auto window = [&]() {  // pre-emphasis + Hamming (MFCC.C:115-124) of the requested samples, as in the serial loop below
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const int i = lane + 64 * k;
+                    if (i < kFrameLen) xw[i] = k == 0 ? window_sample<4>(s_pp[k], mid, hamm_m[k]) : window_sample<2>(s_pp[k], mid, hamm_m[k]);
+                }
+            };
+            auto request = [&](uint32_t f) {
+                const uint16_t *x = row + seg0 + (int)kHop * (int)(f0 + f);
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const int i = lane + 64 * k;
+                    if (i < kFrameLen) s_pp[k] = *(const u32_align2 *)(x + i - 1);
+                }
+            };
+            // exchange .. tier decision of frame fi (`more`: frame fi+1 exists); comments of the stages: the serial loop below
+            auto middle = [&](uint32_t fi, uint32_t (&v)[4][4], bool more) {
+                uint32_t u[4][4];
+                fft_exchange(buf, lane, v, u);
+#pragma unroll
+                for (int e4 = 0; e4 < 4; e4++)
+                    bfly_pk<false>(u[0][e4], u[1][e4], u[2][e4], u[3][e4], tw.s4[0][0], tw.s4[0][1], tw.s4[1][0], tw.s4[1][1],
+                                   tw.s4[2][0], tw.s4[2][1], tw.s4[3][0], tw.s4[3][1]);
+                wave_sync();
+                uint32_t k5[4][4][2];
+                load_tw32(s_tw5, lane, k5);
+                uint32_t nn[8];
+#pragma unroll
+                for (int e3 = 0; e3 < 4; e3++) {
+                    bfly_pk<true>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
+                                  k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
+                    if constexpr (kFeat == SR_FEAT_FFT) {
+                        uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
+                        fr[0] = u[e3][0];
+                        fr[256] = u[e3][1];
+                    }
+                    nn[2 * e3] = (uint32_t)sdot2z(u[e3][0], u[e3][0]);
+                    nn[2 * e3 + 1] = (uint32_t)sdot2z(u[e3][1], u[e3][1]);
+                }
+                const uint32_t nmax = max(max(max(max(nn[0], nn[1]), nn[2]), max(max(nn[3], nn[4]), nn[5])), max(nn[6], nn[7]));
+                if (more) {  // every exchange word has been read: the next frame's window goes over them
+                    wave_sync();
+                    window();
+                }
+#ifdef SR_TESTING
+                const bool quiet = __builtin_expect(__builtin_amdgcn_ballot_w64(nmax > kMagSmallMax) == 0 && !a.mag_table_off, 1);
+#else
+                const bool quiet = __builtin_expect(__builtin_amdgcn_ballot_w64(nmax > kMagSmallMax) == 0, 1);
+#endif
+                if (quiet) {
+#pragma unroll
+                    for (int k = 0; k < 8; k++) asm volatile("buffer_load_ushort %0, %1, %2, 0 idxen" : "=v"(mq[k]) : "v"(nn[k]), "s"(mag_rs));
+                } else if (__builtin_amdgcn_ballot_w64(nmax > a.mag_cheap_max) == 0) {
+#pragma unroll
+                    for (int e3 = 0; e3 < 4; e3++) {
+                        const f32x2 m = f32x2{__builtin_amdgcn_sqrtf((float)(int)nn[2 * e3]), __builtin_amdgcn_sqrtf((float)(int)nn[2 * e3 + 1])} *
+                                        f32x2{10.0f, 10.0f};
+                        mq[2 * e3] = cvt_u32(m.x);
+                        mq[2 * e3 + 1] = cvt_u32(m.y);
+                    }
+                } else {
+#pragma unroll
+                    for (int e3 = 0; e3 < 4; e3++) {
+                        const f32x2 m = sqrt_rn_int2(f32x2{(float)(int)nn[2 * e3], (float)(int)nn[2 * e3 + 1]}) * f32x2{10.0f, 10.0f};
+                        mq[2 * e3] = cvt_u32(m.x);
+                        mq[2 * e3 + 1] = cvt_u32(m.y);
+                    }
+                }
+                pq = quiet;
+                if (fi + 2 < nf) request(fi + 2);
+            };
+            // energies .. powb[r] of the carried frame, row r of the wave.  `young`: the three sample loads of request() were issued
+            // behind the gathers on every path that leads here, so the wait may leave them in flight.
+            auto back_end = [&](uint32_t r, auto young) {
+                wave_sync();  // (the front's reads of xw are done: buf takes the energies)
+                auto energies = [&]() {  // squares of the carried magnitudes, in the chunked order the filterbank reads them in
+                    uint32_t *eb = buf + e_base;
+#pragma unroll
+                    for (int e3 = 0; e3 < 4; e3++) {
+                        const uint32_t q0 = mq[2 * e3], q1 = mq[2 * e3 + 1];
+                        if constexpr (kFeat == SR_FEAT_MAG) {  // the carried frame's row
+                            uint32_t *fr = frow + (f0 + r) * kFeatW + lane + 64 * e3;
+                            const uint32_t sh = pq ? 2u : 0u;
+                            fr[0] = q0 >> sh;
+                            fr[256] = q1 >> sh;
+                        }
+                        eb[kEs * e3] = umul24(q0, q0);
+                        eb[kEs * e3 + kEh] = umul24(q1, q1);
+                    }
+                    wave_sync();
+                };
+                // the two tiers' back ends are two whole branches: the literal form's sixteen raw weights are live in its own only
+                uint32_t pe[8], po[8], se = 0, so = 0;
+                if (pq) {
+                    if constexpr (decltype(young)::value)
+                        asm volatile("s_waitcnt vmcnt(3)" : "+v"(mq[0]), "+v"(mq[1]), "+v"(mq[2]), "+v"(mq[3]), "+v"(mq[4]), "+v"(mq[5]), "+v"(mq[6]), "+v"(mq[7]));
+                    else
+                        asm volatile("s_waitcnt vmcnt(0)" : "+v"(mq[0]), "+v"(mq[1]), "+v"(mq[2]), "+v"(mq[3]), "+v"(mq[4]), "+v"(mq[5]), "+v"(mq[6]), "+v"(mq[7]));
+                    energies();
+                    const uint4 q0 = *(const uint4 *)(buf + c0), q1 = *(const uint4 *)(buf + c1);
+                    const uint32_t e[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const u32x4 me = s_tm[64 * c + lane], mo = s_tm[64 * (c + 2) + lane];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            se += mel_term_fused(e[4 * c + k], me[k]);  // (the table's squares are E << 4 already)
+                            so += mel_term_fused(e[4 * c + k], mo[k]);
+                            pe[4 * c + k] = se;
+                            po[4 * c + k] = so;
+                        }
+                    }
+                } else {
+                    u32x4 tw_e[2], tw_o[2];  // requested from the (cache-resident) table first: they arrive behind the energies
+                    uint32_t off = tw_off;   // (opaque: hoisted out of the loop, the two 64-bit lane addresses cost the QUIET path four VGPRs)
+                    asm("" : "+v"(off));
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        tw_e[c] = *(const u32x4 *)((const char *)a.t.tri_even32 + off + 16 * c);
+                        tw_o[c] = *(const u32x4 *)((const char *)a.t.tri_odd32 + off + 16 * c);
+                    }
+                    energies();
+                    const uint4 q0 = *(const uint4 *)(buf + c0), q1 = *(const uint4 *)(buf + c1);
+                    const uint32_t e[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            se += e[4 * c + k] * tw_e[c][k] / 100u;
+                            so += e[4 * c + k] * tw_o[c][k] / 100u;
+                            pe[4 * c + k] = se;
+                            po[4 * c + k] = so;
+                        }
+                    }
+                }
+                const uint32_t xe = wave_scan_incl(se), xo = wave_scan_incl(so);
+                *(uint4 *)(buf + c0) = make_uint4(pe[0], pe[1], pe[2], pe[3]);
+                *(uint4 *)(buf + c1) = make_uint4(pe[4], pe[5], pe[6], pe[7]);
+                *(uint4 *)(buf + kBins + c0) = make_uint4(po[0], po[1], po[2], po[3]);
+                *(uint4 *)(buf + kBins + c1) = make_uint4(po[4], po[5], po[6], po[7]);
+                buf[2 * kBins + lane] = xe;
+                moff[lane] = xo;
+                wave_sync();
+                if (lane < kMel) {
+                    const uint32_t *X = (lane & 1) ? moff : buf + 2 * kBins;
+                    const uint32_t hi = buf[p_hi] + X[x_hi], lo = f_lo ? buf[p_lo] + X[x_lo] : 0u;
+                    powb[r * kMelPad + lane] = hi - lo;
+                    if constexpr (kFeat == SR_FEAT_MEL) frow[(f0 + r) * kFeatW + lane] = hi - lo;
+                }
+                wave_sync();  // (the exchange of the frame in flight overwrites the prefixes)
+            };
+            constexpr std::false_type kDrain{};
+            if (nf) {
+                window();
+                if (nf > 1) request(1);
+#if SR_MFCC_PIPE_PEEL
+                // first and last frame peeled: the steady-state body is one straight-line block, and on every path into its back end
+                // the next request follows the gathers
+                constexpr std::integral_constant<bool, SR_MFCC_PIPE_VMCNT != 0> kSteady{};
+                {
+                    wave_sync();
+                    uint32_t v[4][4];
+                    fft_front_real160(xw, lane, tw, s_tw3, v);
+                    middle(0, v, nf > 1);
+                }
+                for (uint32_t fi = 1; fi + 1 < nf; fi++) {
+                    wave_sync();
+                    uint32_t v[4][4];
+                    fft_front_real160(xw, lane, tw, s_tw3, v);
+                    back_end(fi - 1, kSteady);
+                    middle(fi, v, true);
+                }
+                if (nf > 1) {
+                    wave_sync();
+                    uint32_t v[4][4];
+                    fft_front_real160(xw, lane, tw, s_tw3, v);
+                    back_end(nf - 2, kDrain);
+                    middle(nf - 1, v, false);
+                }
+#else
+                for (uint32_t fi = 0; fi < nf; fi++) {
+                    wave_sync();
+                    uint32_t v[4][4];
+                    fft_front_real160(xw, lane, tw, s_tw3, v);
+                    if (fi > 0) back_end(fi - 1, kDrain);
+                    middle(fi, v, fi + 1 < nf);
+                }
+#endif
+                back_end(nf - 1, kDrain);
+            }
         }
 
         // ---- log (MFCC.C:165-170) and DCT (MFCC.C:173-183) for the wave's nf frames, all lanes busy
@@ -445,7 +672,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
         {
             int16_t *out_w = out + (size_t)f0 * kCoef;
 #pragma unroll
-            for (uint32_t t = lane; t < (uint32_t)(kFPW * kCoef); t += 64) {
+            for (uint32_t tl = lane; tl < (uint32_t)(kFPW * kCoef); tl += 64) {
+                uint32_t t = tl;
+                // (two-frame loop: a round's row and table addresses are functions of the lane alone; hoisted out of the work-item
+                // loop they sat in VGPRs through the frame loop, which has none to spare -- opaque, they are recomputed per 16 frames)
+                if constexpr (kPipe) asm volatile("" : "+v"(t));
                 if (t < nf * kCoef) {
                     const uint32_t fi = umul24(t, 10923u) >> 17, h = t - umul24(fi, (uint32_t)kCoef);
                     const uint32_t *pw = powb + umul24(fi, (uint32_t)kMelPad), *dm = s_dctM + umul24(h, (uint32_t)kMelPad);
