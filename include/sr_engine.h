@@ -295,6 +295,60 @@ int sr_recognize_stream_nbest(sr_engine *h, const uint16_t *pcm, uint64_t pcm_st
                               uint32_t *seg_offsets, uint32_t n_best, sr_nbest_entry *nbest, uint32_t *n_matched,
                               sr_result *results, uint32_t *scores, int16_t *mfcc, uint32_t *n_segs);
 
+/* ------------------------------------------------------------------ live sessions: chunked audio, VAD state carried
+ * EXTENSION, NO REFERENCE COUNTERPART, like stream recognition.  A session owns n_channels channels; audio arrives in pushes
+ * of at most chunk_max samples per channel, and the session keeps each channel's VAD state and a ring of its recent samples
+ * on the device between calls.  THE RULE: let X_c be everything pushed to channel c since it was opened or last ended.  After
+ * pushing it in ANY chunking and ending the channel, the records the session emitted for c equal what sr_recognize_stream
+ * returns for X_c as one recording with len = |X_c| -- thresholds by the same rule (noise_atap over the first noise_len
+ * samples, or those given at open), same order, start, end, frm_num, sr_result, score row, MFCC rows and N-best entries,
+ * byte for byte -- except for the record type (64-bit offsets) and ONE DEVIATION: a segment of 65 536 frames or more always
+ * fails with SR_ST_MFCC_FAIL (frm_num 0).  The u16-wrapped count of MFCC.C:102 would pass the max_frames cap there and read
+ * samples the ring no longer holds (sr_mfcc_batch_status documents a deviation of the same kind).
+ *
+ * Frame j of a channel is consumed as soon as MORE than j*hop + frame_len samples have arrived (the loop bound of VAD.C:121).
+ * Without given thresholds a channel consumes nothing until noise_len samples have arrived; they are then computed once over
+ * that head and frames are taken from 0 on.  A push emits the segments whose END event (VAD.C:198-207) falls into the frames
+ * it consumed, by ascending channel, then ascending start (deterministic).  Records are never dropped: a push whose max_segs
+ * is below sr_live_event_bound() returns SR_ERR_BAD_ARG, writes nothing and changes no state; so does every other failed
+ * call.  Templates and the word map may change between pushes.  The session uses its engine's scratch buffers: the engine's
+ * one-caller-at-a-time rule covers its sessions. */
+typedef struct sr_live sr_live;
+typedef struct sr_live_seg {   /* 24 bytes */
+    uint32_t channel;
+    uint32_t frm_num;          /* as sr_stream_seg.frm_num (0 on failure; see the deviation above) */
+    int64_t start;             /* sample offset since the channel's recording began (VAD.C:178) */
+    int64_t end;               /* VAD.C:201; -1: the recording was ended inside this segment */
+} sr_live_seg;
+/* host-only, no device (like sr_dtw_geometry): out[0] = ring samples per channel -- whole hop-sized blocks covering
+ * max((max_frames + s_durmax + 4)*hop + 8 + chunk_max, noise_len + frame_len + chunk_max); out[1] = most records one channel
+ * can emit in one push of chunk_max samples; out[2] = device bytes per channel.  chunk_max 1..2^24. */
+int sr_live_geometry(const sr_config *cfg, uint32_t chunk_max, uint32_t out[3]);
+/* host-only: most END events of the VAD's endpoint state machine in `frames` consecutive frames, from any entering state:
+ * 0 for no frame, else 1 + (frames - 1) / (max(v_durmin, 2) + max(s_durmax, 2)) -- what the two bounds are made of */
+uint32_t sr_live_events_in_frames(uint32_t v_durmin, uint32_t s_durmax, uint64_t frames);
+/* atap_in: HOST [n_channels] thresholds, or NULL (noise_atap over each channel's head, again after every sr_live_end) */
+int sr_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, const sr_atap *atap_in, sr_live **out);
+void sr_live_close(sr_live *l); /* before sr_destroy of its engine; waits for the session's last push */
+/* host-only: upper bound on the records THIS push can emit, from the counts alone (n NULL: n_all each) */
+uint32_t sr_live_event_bound(const sr_live *l, const uint32_t *n, uint32_t n_all);
+/* One push.  n: HOST array [n_channels] in both forms, 0 <= n[c] <= chunk_max (any number, 0 = silent in this push); NULL:
+ * n_all each.  Channel c's samples are d_pcm + c*pcm_stride.  DEVICE form: d_pcm 16-byte aligned, pcm_stride a multiple of 8;
+ * one asynchronous operation on `stream`.  d_segs[max_segs], d_count[1] (the true total, <= max_segs) are required;
+ * d_results NULL and n_best 0: segmentation only.  Recognition is launched over all max_segs slots, those in
+ * [*d_count, max_segs) padded as failed records as sr_recognize_stream[_nbest]_dev pads them.  n_best 0 or 1..SR_NBEST_MAX
+ * with d_nbest[max_segs*n_best] (required then) and d_n_matched[max_segs] (optional); d_scores, d_mfcc optional.
+ * HOST form: the same with host buffers; syncs on the count and writes exactly *n_segs rows of every output. */
+int sr_live_push_dev(sr_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                     uint32_t max_segs, sr_live_seg *d_segs, uint32_t *d_count, uint32_t n_best, sr_nbest_entry *d_nbest,
+                     uint32_t *d_n_matched, sr_result *d_results, uint32_t *d_scores, int16_t *d_mfcc, void *stream);
+int sr_live_push(sr_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all, uint32_t max_segs,
+                 sr_live_seg *segs, uint32_t n_best, sr_nbest_entry *nbest, uint32_t *n_matched, sr_result *results,
+                 uint32_t *scores, int16_t *mfcc, uint32_t *n_segs);
+/* The listed channels' recordings end here: a channel inside a segment (state speech or tail) reports {start, -1}, in the
+ * order listed; then the channel is as freshly opened.  segs[n_ch], *n_segs = records written.  Waits for the device. */
+int sr_live_end(sr_live *l, const uint32_t *channels, uint32_t n_ch, sr_live_seg *segs, uint32_t *n_segs);
+
 /* stage-level entry points on DEVICE buffers (same kernels the full path launches).  d_vad records a caller writes itself
  * follow the rules of those sr_vad_batch_dev writes: a failed record (status != 0) has frm_num 0.  The frame kernels
  * (sr_mfcc_batch_dev, sr_frame_features_batch_dev) take seg[0] and frm_num as given and read frm_num frames from seg[0] - 1

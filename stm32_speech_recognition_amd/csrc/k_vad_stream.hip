@@ -14,37 +14,10 @@
 //   pass 3  k_stream_emit    one lane per tile: the tile's frames replayed from its entering state; every END event writes
 //                            the whole record (start from the replay or from the scan), as does the end of a recording that
 //                            ends inside a segment (end = -1).  Each record is written by exactly one lane.
-#include "sr_vad_dev.h"
+#include "sr_stream_dev.h"  // StreamSm, stream_frm_num (shared with k_live.hip)
 
 namespace sr {
 
-// the endpoint state machine (VAD.C:164-216) with the counters folded into one state number:
-//   0 silence | 1..nF onset, front = s | sp = nF + 1 speech | sp + 1 .. sp + nB tail, back = s - sp
-struct StreamSm {
-    uint32_t nF, sp, v_durmin, s_durmax;
-    // one frame; ev: 1 = a segment starts at this frame (VAD.C:175-180), 2 = one ends (VAD.C:198-207)
-    __device__ __forceinline__ uint32_t step(uint32_t s, bool loud, uint32_t &ev) const
-    {
-        ev = 0;
-        if (s == 0) return loud ? 1u : 0u;
-        if (s <= nF) {  // front++ is checked on loud frames only, after the increment (VAD.C:173-181)
-            if (!loud) return 0u;
-            if (s + 1 >= v_durmin) {
-                ev = 1;
-                return sp;
-            }
-            return s + 1;
-        }
-        if (s == sp) return loud ? sp : sp + 1;
-        if (loud) return sp;  // a loud frame returns to speech (VAD.C:186-190)
-        const uint32_t back = s - sp + 1;
-        if (back >= s_durmax) {
-            ev = 2;
-            return 0u;
-        }
-        return sp + back;
-    }
-};
 __device__ __forceinline__ StreamSm stream_sm(const VadStreamArgs &a)
 {
     return StreamSm{a.n_front, a.n_front + 1, a.v_durmin, a.s_durmax};
@@ -205,13 +178,6 @@ __global__ void __launch_bounds__(kScanThreads) k_stream_scan(const VadStreamArg
 }
 
 // ---- pass 3 ------------------------------------------------------------------------------------------------------------
-// frm_num per k_select_segment (k_vad.hip) / MFCC.C:102-107: 0 for an open end or a start < 1
-__device__ __forceinline__ uint32_t stream_frm_num(int st, int en, uint32_t frame_len, uint32_t hop, uint32_t max_frames)
-{
-    if (en < 0 || st < 1) return 0;
-    const uint32_t n = ((((uint32_t)(en - st) - frame_len) / hop) + 1) & 0xFFFF;
-    return n > max_frames ? 0u : n;
-}
 __global__ void __launch_bounds__(256) k_stream_emit(const VadStreamArgs a)
 {
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

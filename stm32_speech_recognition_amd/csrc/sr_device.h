@@ -113,6 +113,57 @@ struct StreamRecArgs {
     sr_vad_rec *recs;             // [n]
 };
 
+// live sessions (k_live.hip): chunked audio, VAD state carried from push to push.  One record per channel; the host mirrors
+// received / next_frame / atap_set (it knows every count), carry, state and open_start live on the device alone.
+struct LiveChan {  // 48 bytes
+    sr_atap atap;         // the thresholds, once atap_set
+    uint32_t atap_set;    // 1: given at open, or computed when the noise head was complete
+    uint32_t carry;       // class of the last out-of-band sample in blocks < next_frame (last_sig, VAD.C:99: never reset)
+    uint32_t state;       // StreamSm state number
+    uint64_t next_frame;  // frames consumed so far = absolute index of the next one
+    int64_t open_start;   // start of the segment open in state speech / tail (VAD.C:178)
+    uint64_t received;    // samples since the channel's recording began
+};
+struct LiveEvent {  // an END event (VAD.C:198-207) of one push, in the channel's bounded slots
+    int64_t start, end;
+};
+struct LiveArgs {
+    LiveChan *chan;             // [C]
+    uint16_t *ring;             // [C][ring_stride]: whole blocks of hop samples, by absolute block number modulo ring_blocks
+    uint64_t ring_stride;       // samples = ring_blocks * hop
+    uint32_t ring_blocks;
+    uint32_t C;
+    const uint16_t *pcm;        // the chunks of this push: [C][pcm_stride], 16-byte aligned rows
+    uint64_t pcm_stride;
+    const uint32_t *n;          // [C] samples of each chunk; NULL: n_all each
+    uint32_t n_all;
+    const sr_vad_rec *head_vad; // k_vad records of channels head_c0 ..: thresholds of the noise heads completed by this push
+    uint32_t head_c0;
+    uint32_t noise_len;
+    uint32_t frame_len, hop, v_durmin, s_durmax, max_frames;
+    LiveEvent *events;          // [C][ev_slots]
+    uint32_t *ev_count;         // [C]
+    uint32_t ev_slots;
+    sr_live_seg *segs;          // [max_segs] compacted: ascending channel, then ascending start
+    uint32_t max_segs;
+    uint32_t *count;            // [1] the total
+};
+struct LiveRecArgs {
+    const LiveChan *chan;
+    const uint16_t *ring;
+    uint64_t ring_stride;
+    const sr_live_seg *segs;
+    const uint32_t *count;        // [1]
+    uint32_t r0;                  // first record of this launch
+    uint32_t frame_len, hop, max_frames;
+    uint16_t *rows;               // [n][row_stride]
+    uint64_t row_stride;
+    sr_vad_rec *recs;             // [n]
+};
+void launch_live_append(const LiveArgs &a, hipStream_t s);
+void launch_live_scan(const LiveArgs &a, bool sad, hipStream_t s);  // scan + count / offsets / compaction
+void launch_live_records(const LiveRecArgs &a, uint32_t n, hipStream_t s);
+
 struct MfccArgs {
     const uint16_t *pcm;
     uint64_t pcm_stride;

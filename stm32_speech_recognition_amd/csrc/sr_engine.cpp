@@ -91,6 +91,22 @@ static int front_end_of(const sr_config *cfg, FrontEnd *fe)
     return SR_OK;
 }
 
+// Host-only: the framing figures sr_create derives from cfg, for entry points that need them without an engine
+// (sr_live_geometry); the same checks as sr_create, no device touched
+extern "C++" int sr::config_framing(const sr_config *cfg, ConfigFraming *out)
+{
+    FrontEnd fe;
+    if (int rc = front_end_of(cfg, &fe)) return rc;
+    if (cfg->max_frames < 2 || cfg->max_frames > 16383) return fail(SR_ERR_BAD_CONFIG, "max_frames must be 2..16383");
+    const uint32_t noise_len = (cfg->fs / 1000) * cfg->noise_len_ms, atap_frm = (cfg->fs / 1000) * 30;
+    if (noise_len == 0 || noise_len % atap_frm != 0 || noise_len % (uint32_t)fe.frame_len != 0)
+        return fail(SR_ERR_BAD_CONFIG, "noise_len_ms: the noise head must be a non-zero multiple of the 30 ms block of noise_atap and of the frame length");
+    const uint32_t step = cfg->frame_time_ms - cfg->frame_mov_ms;
+    if (80 / step < 1 || 110 / step < 1) return fail(SR_ERR_BAD_CONFIG, "frame_time_ms - frame_mov_ms must not exceed 80 ms (VAD.C:72-75)");
+    *out = ConfigFraming{(uint32_t)fe.frame_len, (uint32_t)fe.hop, 80 / step, 110 / step, noise_len, cfg->max_frames};
+    return SR_OK;
+}
+
 int sr_log_table_mismatches(void) { return log_table_mismatches(); }
 uint32_t sr_mag_cheap_bound(const sr_engine *h) { return h ? h->mag_cheap_max : 0u; }
 

@@ -215,6 +215,13 @@ DtwArgs dtw_args(const sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_
                      uint32_t *d_scores, sr_result *d_results);
 void plan_dtw(sr_engine *h, const uint32_t *frames, const uint8_t *valid);
 bool launch_dtw_auto(sr_engine *h, DtwArgs &a, uint32_t b0, hipStream_t s, hipStream_t owner);
+// ---- live sessions (sr_live.cpp) -------------------------------------------------------------------------------------------
+namespace sr {
+struct ConfigFraming {
+    uint32_t frame_len, hop, v_durmin, s_durmax, noise_len, max_frames;
+};
+int config_framing(const sr_config *cfg, ConfigFraming *out);  // sr_engine.cpp: host-only, sr_create's checks and figures
+}  // namespace sr
 // ---- word-level N-best (sr_nbest.cpp) -----------------------------------------------------------------------------------
 // (re)build and upload the grouping for the current store and map; waits for the device unless the caller has (`drained`)
 int regroup_words(sr_engine *h, bool drained);

@@ -28,8 +28,11 @@ STREAM_SEG_DTYPE = np.dtype([("stream", "<u4"), ("start", "<i4"), ("end", "<i4")
 # word-level N-best (sr_nbest_entry): a candidate word, its best slot, that slot's distance, its slots that matched at all
 NBEST_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("dis", "<u4"), ("count", "<u4")])
 NO_WORD, NBEST_MAX = 0xFFFFFFFF, 16
+# live sessions (sr_live_seg): a segment of a channel, 64-bit sample offsets since the channel's recording began
+LIVE_SEG_DTYPE = np.dtype([("channel", "<u4"), ("frm_num", "<u4"), ("start", "<i8"), ("end", "<i8")])
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48
 assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16 and NBEST_DTYPE.itemsize == 16
+assert LIVE_SEG_DTYPE.itemsize == 24
 
 
 class Config(C.Structure):
@@ -620,6 +623,11 @@ class Engine:
                     t.record_stream(stream)  # allocated on the current stream, written on `stream`
         return o
 
+    def live(self, n_channels, chunk_max, atap=None):
+        """sr_live_open: a LiveSession of n_channels channels taking pushes of at most chunk_max samples per channel; atap
+        None (noise_atap over each channel's head) or an ATAP_DTYPE array [n_channels].  Close it before the engine."""
+        return LiveSession(self, n_channels, chunk_max, atap)
+
     def set_pipeline(self, streams=3, min_chunk=4096, max_chunks=12):
         """chunking of recognize_dev over the engine's internal streams (streams=1: one chunk, caller's stream)"""
         self._check(self.L.sr_set_pipeline(self.h, C.c_uint32(streams), C.c_uint32(min_chunk), C.c_uint32(max_chunks)))
@@ -633,6 +641,145 @@ class Engine:
         n = C.c_uint32(0)
         self._check(self.L.sr_get_stage_launches(self.h, C.byref(n)))
         return dict(vad=ms[0], mfcc=ms[1], dtw=ms[2], argmin=ms[3], total=ms[4], launches_per_call=n.value)
+
+
+def live_geometry(chunk_max, max_frames=119, **kw):
+    """Host-only sr_live_geometry for a configuration (keywords as Engine's): (ring samples per channel, most records one
+    channel can emit in one push of chunk_max samples, device bytes per channel)"""
+    L = load_library()
+    cfg = Config()
+    L.sr_default_config(C.byref(cfg))
+    cfg.max_frames = max_frames
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    out = (C.c_uint32 * 3)()
+    rc = L.sr_live_geometry(C.byref(cfg), C.c_uint32(chunk_max), out)
+    if rc != 0:
+        raise SrError(f"sr_live_geometry error {rc}: {L.sr_last_error().decode()}")
+    return tuple(out)
+
+
+class LiveSession:
+    """One sr_live handle (Engine.live): chunked audio on n_channels channels, VAD state carried between pushes.  The records
+    of a channel, over any chunking, are those of Engine.recognize_stream on everything pushed to it (include/sr_engine.h)."""
+
+    def __init__(self, eng, n_channels, chunk_max, atap=None):
+        self.eng, self.L, self.n_channels, self.chunk_max = eng, eng.L, n_channels, chunk_max
+        self.L.sr_live_event_bound.restype = C.c_uint32
+        self.L.sr_live_close.restype = None
+        self.L.sr_live_close.argtypes = [C.c_void_p]
+        at = None if atap is None else np.ascontiguousarray(atap, dtype=ATAP_DTYPE)
+        assert at is None or len(at) == n_channels
+        l = C.c_void_p()
+        eng._check(self.L.sr_live_open(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), _vp(at), C.byref(l)))
+        self.l = l
+
+    def close(self):
+        if getattr(self, "l", None):
+            self.L.sr_live_close(self.l)
+            self.l = None
+
+    def __del__(self):
+        try:
+            if getattr(self.eng, "h", None):  # a session never outlives its engine's handle
+                self.close()
+        except Exception:
+            pass
+
+    def _counts(self, counts, width):
+        """(host uint32 array or None, n_all)"""
+        if counts is None:
+            return None, width
+        ct = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert ct.shape == (self.n_channels,)
+        return ct, 0
+
+    def event_bound(self, counts):
+        """sr_live_event_bound: most records a push with these counts (an int: that many on every channel) can emit"""
+        if np.isscalar(counts):
+            return int(self.L.sr_live_event_bound(self.l, None, C.c_uint32(int(counts))))
+        ct, _ = self._counts(counts, 0)
+        return int(self.L.sr_live_event_bound(self.l, _vp(ct), C.c_uint32(0)))
+
+    def push(self, chunks, counts=None, n_best=None, want_scores=True, want_mfcc=True, recognize=True, max_segs=None):
+        """sr_live_push: chunks uint16 [n_channels, W], counts [n_channels] (None: W each).  Returns dict(segs
+        LIVE_SEG_DTYPE [n], total = n, results, scores, mfcc[, nbest, n_matched]) of numpy arrays."""
+        pcm = np.ascontiguousarray(chunks, dtype=np.uint16)
+        assert pcm.ndim == 2 and pcm.shape[0] == self.n_channels
+        W = pcm.shape[1]
+        ct, n_all = self._counts(counts, W)
+        if max_segs is None:
+            max_segs = self.event_bound(W if ct is None else ct)
+        eng = self.eng
+        K = eng.n_templates if recognize else 0
+        segs = np.zeros(max_segs, dtype=LIVE_SEG_DTYPE)
+        res = np.zeros(max_segs, dtype=RESULT_DTYPE) if recognize else None
+        sc = np.zeros((max_segs, K), dtype=np.uint32) if recognize and want_scores else None
+        mf = np.zeros((max_segs, eng.max_frames, eng.n_coef), dtype=np.int16) if recognize and want_mfcc else None
+        nb = nm = None
+        if recognize and n_best is not None:
+            nb = np.zeros((max_segs, max(n_best, 0)), dtype=NBEST_DTYPE)
+            nm = np.zeros(max_segs, dtype=np.uint32)
+        total = C.c_uint32(0)
+        eng._check(self.L.sr_live_push(self.l, _vp(pcm), C.c_uint64(max(W, 1)), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_segs),
+                                       _vp(segs), C.c_uint32(n_best if nb is not None else 0), _vp(nb), _vp(nm), _vp(res), _vp(sc),
+                                       _vp(mf), C.byref(total)))
+        cut = (lambda x: None if x is None else x[:total.value])
+        out = dict(segs=cut(segs), total=total.value, results=cut(res), scores=cut(sc), mfcc=cut(mf))
+        if nb is not None:
+            out.update(nbest=cut(nb), n_matched=cut(nm))
+        return out
+
+    def push_dev(self, chunks, counts=None, n_best=None, scores=True, mfcc=True, recognize=True, max_segs=None, stream=None):
+        """sr_live_push_dev on a device tensor: chunks int16 [n_channels, W] (u16 codes, W a multiple of 8), counts a HOST
+        array [n_channels] (None: W each).  Asynchronous on `stream` (a torch.cuda.Stream, or the current one).  Returns a
+        dict of device tensors max_segs long: segs int32 [max_segs, 6] (sr_live_seg records), count int32 [1], results,
+        scores, mfcc[, nbest, n_matched]; rows at and past count are padding."""
+        import torch
+        assert chunks.is_cuda and chunks.dtype in (torch.int16, torch.uint16) and chunks.is_contiguous()
+        assert chunks.shape[0] == self.n_channels
+        W = chunks.shape[1]
+        ct, n_all = self._counts(counts, W)
+        if max_segs is None:
+            max_segs = self.event_bound(W if ct is None else ct)
+        eng, dev = self.eng, chunks.device
+        K = eng.n_templates if recognize else 0
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        rows = max(max_segs, 1)
+        o = dict(segs=torch.empty(rows, 6, dtype=torch.int32, device=dev)[:max_segs],
+                 count=torch.empty(1, dtype=torch.int32, device=dev))
+        o["results"] = torch.empty(rows, 4, dtype=torch.int32, device=dev)[:max_segs] if recognize else None
+        o["scores"] = torch.empty(max_segs, K, dtype=torch.int32, device=dev) if recognize and scores else None
+        o["mfcc"] = torch.empty(max_segs, eng.max_frames, eng.n_coef, dtype=torch.int16, device=dev) if recognize and mfcc else None
+        nb = nm = None
+        if recognize and n_best is not None:
+            nb = o["nbest"] = torch.empty(rows, max(n_best, 0), 4, dtype=torch.int32, device=dev)[:max_segs]
+            nm = o["n_matched"] = torch.empty(rows, dtype=torch.int32, device=dev)[:max_segs]
+        eng._check(self.L.sr_live_push_dev(self.l, _vp(chunks), C.c_uint64(W), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_segs),
+                                           _vp(o["segs"]), _vp(o["count"]), C.c_uint32(n_best if nb is not None else 0), _vp(nb),
+                                           _vp(nm), _vp(o["results"]), _vp(o["scores"]), _vp(o["mfcc"]),
+                                           C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            chunks.record_stream(stream)
+            for t in o.values():
+                if t is not None:
+                    t.record_stream(stream)  # allocated on the current stream, written on `stream`
+        return o
+
+    def end(self, channels):
+        """sr_live_end: the listed channels' recordings end here.  Returns the LIVE_SEG_DTYPE records {start, -1} of those
+        that were inside a segment; afterwards the channels are as freshly opened."""
+        ch = np.ascontiguousarray(np.atleast_1d(channels), dtype=np.uint32)
+        segs = np.zeros(max(len(ch), 1), dtype=LIVE_SEG_DTYPE)
+        n = C.c_uint32(0)
+        self.eng._check(self.L.sr_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(segs), C.byref(n)))
+        return segs[:n.value]
+
+
+def live_segs_from_torch(t):
+    """[n, 6] int32 device tensor of sr_live_seg records -> numpy LIVE_SEG_DTYPE array [n]"""
+    return t.cpu().numpy().view(np.uint8).reshape(-1, 24).copy().view(LIVE_SEG_DTYPE).reshape(-1)
 
 
 def pack12(pcm):
