@@ -295,6 +295,50 @@ int sr_recognize_stream_nbest(sr_engine *h, const uint16_t *pcm, uint64_t pcm_st
                               uint32_t *seg_offsets, uint32_t n_best, sr_nbest_entry *nbest, uint32_t *n_matched,
                               sr_result *results, uint32_t *scores, int16_t *mfcc, uint32_t *n_segs);
 
+/* ------------------------------------------------------------------ second pass: full-DP rescoring of the N-best words
+ * EXTENSION, NO REFERENCE COUNTERPART: the classic two-pass recogniser built from the two extensions above and below.  The
+ * first pass (the firmware's greedy dtw() walk) names n_best candidate words per row; the second pass gives EVERY slot of
+ * every candidate word its full-DP score -- exactly the value sr_dtw_dp_batch_dev writes for that (row, slot), SR_DIS_ERR
+ * included -- and ranks the words again, all on the device.  No existing call, record or score changes.
+ *
+ * Per row, from its feature record, its frame count and an input list of n_best sr_nbest_entry:
+ *   candidates  for every input entry with word != SR_NO_WORD and slot < K: the word group that SLOT belongs to under the
+ *               engine's current word map (the entry's word field is not trusted any further).  A word named twice counts
+ *               once; entries with slot >= K are ignored and nothing is read out of range.
+ *   output      what sr_nbest_batch returns, with the same n_best, for a score row that holds the full-DP scores at the
+ *               candidate words' slots and SR_DIS_ERR everywhere else: first minimum in slot order inside a word, ranking by
+ *               (dis, slot), count = the word's slots with a full-DP score, the tail filled with
+ *               {SR_NO_WORD, 0xFFFFFFFF, SR_DIS_ERR, 0}; a word none of whose slots gets a score drops out.
+ *               n_rescored[row] = the candidates that survived.
+ * Stage level: d_mfcc[n_rows][max_frames][12] (frames[row] <= max_frames, as for sr_dtw_dp_batch_dev); d_in_frames points at
+ * the FIRST row's u32 frame count and frames_stride (u32 words, >= 1) leads to the next row's, so one argument serves every
+ * record the library emits: 1 for a plain array, 4 for &d_results[0].frm_num and &d_segs[0].frm_num (sr_stream_seg), 6 for
+ * sr_live_seg, 12 for &d_vad[0].frm_num (sr_vad_rec).  Stream and live callers rescore with this call on the d_mfcc and
+ * d_nbest they already hold.  d_nbest_out[n_rows*n_best] (required) must not be d_nbest_in, which is never written;
+ * d_n_rescored[n_rows] is optional; n_rows <= 16 776 960.  DEVICE form: asynchronous on `stream`, no host synchronisation,
+ * no read-back; the pair marks and the second-pass score rows live in the engine's scratch.  sr_set_dp_lanes applies, with
+ * the same fallbacks and the same values in every form.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_BAD_ARG for a null required
+ * pointer, n_best outside 1..SR_NBEST_MAX, a word map that does not fit the store, frames_stride 0, d_nbest_out ==
+ * d_nbest_in, templates too long for the LDS-staged DP kernel; SR_ERR_NO_TEMPLATES. */
+int sr_rescore_nbest_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride,
+                            uint32_t n_rows, uint32_t n_best, const sr_nbest_entry *d_nbest_in, sr_nbest_entry *d_nbest_out,
+                            uint32_t *d_n_rescored, void *stream);
+int sr_rescore_nbest_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                        uint32_t n_best, const sr_nbest_entry *nbest_in, sr_nbest_entry *nbest_out, uint32_t *n_rescored);
+/* Whole path: sr_recognize_nbest_batch[_dev] (same arguments, the same bytes in every output) plus rescored[B*n_best]
+ * (required) and n_rescored[B] (optional) = the stage-level call on that call's mfcc, vad[].frm_num and nbest.  The
+ * first-pass list stays an output but may be NULL here (it then lives in the engine's scratch).  The device form stays ONE
+ * asynchronous operation: the second pass runs per chunk, on that chunk's stream, behind its first-pass reduction.  The
+ * host form is sr_recognize_nbest_batch followed by ONE second pass over all B rows in the engine's scratch. */
+int sr_recognize_rescored_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                                    uint32_t n_best, sr_nbest_entry *d_nbest, uint32_t *d_n_matched, sr_nbest_entry *d_rescored,
+                                    uint32_t *d_n_rescored, sr_result *d_results, uint32_t *d_scores, int16_t *d_mfcc,
+                                    sr_vad_rec *d_vad, void *stream);
+int sr_recognize_rescored_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                                uint32_t n_best, sr_nbest_entry *nbest, uint32_t *n_matched, sr_nbest_entry *rescored,
+                                uint32_t *n_rescored, sr_result *results, uint32_t *scores, int16_t *mfcc, sr_vad_rec *vad);
+
 /* ------------------------------------------------------------------ live sessions: chunked audio, VAD state carried
  * EXTENSION, NO REFERENCE COUNTERPART, like stream recognition.  A session owns n_channels channels; audio arrives in pushes
  * of at most chunk_max samples per channel, and the session keeps each channel's VAD state and a ring of its recent samples

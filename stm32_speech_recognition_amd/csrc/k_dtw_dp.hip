@@ -21,14 +21,23 @@ namespace sr {
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kDpInf = 0xFFFFFFFFu;
 
-__global__ void __launch_bounds__(256) k_dtw_dp_wave64(const DtwArgs a)
+// The sparse form of both kernels (two-pass rescoring, k_rescore.hip): the pairs of a launch are not every (row, slot) but
+// the ones the mark pass chose, one byte per pair in marks[template rank][row].  A sparse workgroup serves one template
+// and a RANGE of rows: it looks at its template's marks for the range first, leaves at once when none is set, and otherwise
+// stages the template and walks the marked rows exactly as the dense kernel walks its block of rows -- the walk itself
+// (dp_wave64_pair / dp_band_walk) is the same code, only the row index of a pair comes from the marks.
+struct DpSparseArgs {
+    const uint8_t *marks;      // [K ranks][mark_stride], != 0: score this pair; rows past the launch's are 0
+    uint32_t mark_stride;      // bytes per template, a multiple of 16
+    uint32_t frames_stride;    // u32 words between the frame counts of consecutive rows (in_frames[row * frames_stride])
+    const uint32_t *tpl_rank;  // [K] rank of each slot in the length order (the inverse of tpl_orig)
+};
+constexpr uint32_t kDpSparseRowsWave = 256;   // rows of one k_dtw_dp_wave64_sparse workgroup: one mark byte per thread
+constexpr uint32_t kDpSparseRowsBand = 1024;  // rows of one k_dtw_dp_band_sparse workgroup: four mark bytes per thread
+
+// stage the template (24-byte rows + squared norm) once per workgroup
+__device__ __forceinline__ void dp_wave64_stage(const DtwArgs &a, u32x4 *dp_smem, uint32_t k)
 {
-    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];  // template rows: [tpl_rows][2] u32x4
-    const uint32_t k = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t b = blockIdx.y * 4 + w;
-    const uint32_t mdl_n = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
-    uint32_t *s_col = (uint32_t *)(dp_smem + (size_t)a.tpl_rows * 2) + (size_t)w * a.tpl_rows;  // boundary column per wave
-    // stage the template (24-byte rows + squared norm) once per workgroup
     for (uint32_t r = threadIdx.x; r < a.tpl_rows; r += blockDim.x) {
         const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
         const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
@@ -41,10 +50,13 @@ __global__ void __launch_bounds__(256) k_dtw_dp_wave64(const DtwArgs a)
         dp_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
         dp_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)nr, 0u};
     }
-    __syncthreads();
-    if (b >= a.B) return;
+}
+// one (utterance b, template k) pair on one wave; s_col = the wave's boundary column
+__device__ __forceinline__ void dp_wave64_pair(const DtwArgs &a, const u32x4 *dp_smem, uint32_t *s_col, uint32_t k, uint32_t mdl_n,
+                                               uint32_t b, uint32_t lane, uint32_t frames_stride)
+{
     uint32_t in_n;
-    if (a.in_frames) in_n = a.in_frames[b];
+    if (a.in_frames) in_n = a.in_frames[(size_t)b * frames_stride];
     else in_n = (a.vad[b].status == SR_ST_OK) ? a.vad[b].frm_num : 0u;
     uint32_t score = SR_DIS_ERR;
     if (in_n && mdl_n && !(in_n > mdl_n * 2 || 2 * in_n < mdl_n)) {
@@ -99,6 +111,45 @@ __global__ void __launch_bounds__(256) k_dtw_dp_wave64(const DtwArgs a)
         if (d_end != kDpInf) score = d_end / (in_n + mdl_n);
     }
     if (lane == 0) a.scores[(size_t)b * a.K + k] = score;
+}
+
+__global__ void __launch_bounds__(256) k_dtw_dp_wave64(const DtwArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];  // template rows: [tpl_rows][2] u32x4
+    const uint32_t k = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t b = blockIdx.y * 4 + w;
+    const uint32_t mdl_n = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
+    uint32_t *s_col = (uint32_t *)(dp_smem + (size_t)a.tpl_rows * 2) + (size_t)w * a.tpl_rows;  // boundary column per wave
+    dp_wave64_stage(a, dp_smem, k);
+    __syncthreads();
+    if (b >= a.B) return;
+    dp_wave64_pair(a, dp_smem, s_col, k, mdl_n, b, lane, 1u);
+}
+
+// sparse form: grid (slot, range of kDpSparseRowsWave rows); wave w owns the 64 rows [row0 + 64 w, + 64) of the range and
+// walks the marked ones one after the other (the generic kernel gives a pair a whole wave)
+__global__ void __launch_bounds__(256) k_dtw_dp_wave64_sparse(const DtwArgs a, const DpSparseArgs sp)
+{
+    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];
+    const uint32_t k = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t row0 = blockIdx.y * kDpSparseRowsWave + w * 64, row = row0 + lane;
+    uint32_t *s_flag = (uint32_t *)(dp_smem + (size_t)a.tpl_rows * 2);  // word 0 of each wave's boundary column, until the walk starts
+    uint32_t *s_col = s_flag + (size_t)w * a.tpl_rows;
+    const bool marked = row < a.B && sp.marks[(size_t)sp.tpl_rank[k] * sp.mark_stride + row] != 0;
+    uint64_t todo = __builtin_amdgcn_ballot_w64(marked);
+    if (lane == 0) *s_col = todo != 0ull;
+    __syncthreads();
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < 4; i++) any |= s_flag[(size_t)i * a.tpl_rows];
+    if (!any) return;  // (workgroup-uniform) nothing to score here: nothing staged
+    const uint32_t mdl_n = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
+    dp_wave64_stage(a, dp_smem, k);
+    __syncthreads();  // (every wave has read the flags before it arrives here)
+    while (todo) {    // (wave-uniform)
+        const uint32_t i = (uint32_t)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        dp_wave64_pair(a, dp_smem, s_col, k, mdl_n, row0 + i, lane, sp.frames_stride);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -170,36 +221,34 @@ __device__ __forceinline__ int wave_reduce_i32(int v)
 __device__ __forceinline__ int wave_min_i32(int v) { return wave_reduce_i32<false>(v); }
 __device__ __forceinline__ int wave_max_i32(int v) { return wave_reduce_i32<true>(v); }
 
-template <int G, int kDpWaves>  // lanes per pair, waves per workgroup
-__global__ void __launch_bounds__(64 * kDpWaves) k_dtw_dp_band(const DpBandArgs a)
+// LDS of a band workgroup: template image [RP] rows of 32 bytes, row r at index r + G (G pad rows in front: lanes j > 0 start
+// above the band), then one boundary column of RP words per group, entry r at index r + G
+template <int G>
+__device__ __forceinline__ void dp_band_stage(const DpBandArgs &a, u32x4 *s_tpl, uint32_t ks)
 {
-    constexpr int NG = 64 / G;  // pairs per wave
-    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];
-    const uint32_t K = a.d.K, ks = blockIdx.x;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j = (int)(lane % G);
-    const uint32_t grp = w * NG + lane / G;
-    const uint32_t RP = a.rows_pad;
-    // LDS: template image [RP] rows of 32 bytes, row r at index r + G (G pad rows in front: lanes j > 0 start above the
-    // band), then one boundary column of RP words per group, entry r at index r + G
-    u32x4 *s_tpl = dp_smem;
-    uint32_t *s_col = (uint32_t *)(dp_smem + 2 * (size_t)RP) + (size_t)grp * RP;
-    const int mdl_n = (int)a.tpl_frames_s[ks];
-    {
-        const uint32_t rows = a.d.tpl_rows;
-        for (uint32_t r = tid; r < rows; r += blockDim.x) {
-            const u32x4 *q = a.tplR + ((size_t)r * K + ks) * 2;
-            s_tpl[2 * (r + G)] = q[0];
-            s_tpl[2 * (r + G) + 1] = q[1];
-        }
-        // D(0,0) = 0 is the virtual predecessor of cell (1,1): entry -1 of the boundary column; everything else unreachable
-        for (uint32_t i = (uint32_t)j; i < RP; i += G) s_col[i] = (i == (uint32_t)(G - 1)) ? 0u : kDpInf;
+    const uint32_t rows = a.d.tpl_rows, K = a.d.K;
+    for (uint32_t r = threadIdx.x; r < rows; r += blockDim.x) {
+        const u32x4 *q = a.tplR + ((size_t)r * K + ks) * 2;
+        s_tpl[2 * (r + G)] = q[0];
+        s_tpl[2 * (r + G) + 1] = q[1];
     }
-    __syncthreads();
-    const uint32_t b = (blockIdx.y * kDpWaves + w) * NG + lane / G;
+}
+// D(0,0) = 0 is the virtual predecessor of cell (1,1): entry -1 of the boundary column; everything else unreachable
+template <int G>
+__device__ __forceinline__ void dp_band_reset_col(uint32_t *s_col, uint32_t RP, int j)
+{
+    for (uint32_t i = (uint32_t)j; i < RP; i += G) s_col[i] = (i == (uint32_t)(G - 1)) ? 0u : kDpInf;
+}
+
+// The pairs of one wave against the staged template ks: lane j of a group walks utterance b (b >= B: no pair in this group)
+template <int G>
+__device__ __forceinline__ void dp_band_walk(const DpBandArgs &a, const u32x4 *s_tpl, uint32_t *s_col, uint32_t ks, int mdl_n,
+                                             uint32_t b, int j, uint32_t frames_stride)
+{
+    const uint32_t K = a.d.K;
     int in_n = 0;
     if (b < a.d.B) {
-        if (a.d.in_frames) in_n = (int)a.d.in_frames[b];
+        if (a.d.in_frames) in_n = (int)a.d.in_frames[(size_t)b * frames_stride];
         else in_n = (a.d.vad[b].status == SR_ST_OK) ? (int)a.d.vad[b].frm_num : 0;
     }
     const bool pair_ok = in_n > 0 && mdl_n > 0 && !(in_n > 2 * mdl_n || 2 * in_n < mdl_n);  // main.c:283, DTW.C:133-137
@@ -324,6 +373,84 @@ __global__ void __launch_bounds__(64 * kDpWaves) k_dtw_dp_band(const DpBandArgs 
     }
 }
 
+template <int G, int kDpWaves>  // lanes per pair, waves per workgroup
+__global__ void __launch_bounds__(64 * kDpWaves) k_dtw_dp_band(const DpBandArgs a)
+{
+    constexpr int NG = 64 / G;  // pairs per wave
+    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];
+    const uint32_t ks = blockIdx.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j = (int)(lane % G);
+    const uint32_t grp = w * NG + lane / G;
+    const uint32_t RP = a.rows_pad;
+    u32x4 *s_tpl = dp_smem;
+    uint32_t *s_col = (uint32_t *)(dp_smem + 2 * (size_t)RP) + (size_t)grp * RP;
+    const int mdl_n = (int)a.tpl_frames_s[ks];
+    dp_band_stage<G>(a, s_tpl, ks);
+    dp_band_reset_col<G>(s_col, RP, j);
+    __syncthreads();
+    const uint32_t b = (blockIdx.y * kDpWaves + w) * NG + lane / G;
+    dp_band_walk<G>(a, s_tpl, s_col, ks, mdl_n, b, j, 1u);
+}
+
+// sparse form: grid (template rank, range of kDpSparseRowsBand rows).  Thread t holds the marks of rows row0 + 4 t .. + 3 as
+// one word; four ballots per wave and the waves' counts in LDS give every marked row its place in the list s_list (the place
+// decides which group walks the row, nothing else: a score is written by (row, slot)), then the list is walked in rounds of
+// kDpWaves * 64 / G pairs against the template staged once.
+template <int G, int kDpWaves>
+__global__ void __launch_bounds__(64 * kDpWaves) k_dtw_dp_band_sparse(const DpBandArgs a, const DpSparseArgs sp)
+{
+    static_assert(64 * kDpWaves * 4 == kDpSparseRowsBand, "four mark bytes per thread");
+    constexpr int NG = 64 / G, PER = NG * kDpWaves;
+    extern __shared__ __attribute__((aligned(16))) u32x4 dp_smem[];
+    const uint32_t ks = blockIdx.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j = (int)(lane % G);
+    const uint32_t grp = w * NG + lane / G;
+    const uint32_t RP = a.rows_pad;
+    u32x4 *s_tpl = dp_smem;
+    uint32_t *s_col = (uint32_t *)(dp_smem + 2 * (size_t)RP) + (size_t)grp * RP;
+    // behind the dense layout and its 32 spare bytes (dp_band_lds): the row list, then the waves' counts
+    uint32_t *s_list = (uint32_t *)(dp_smem + 2 * (size_t)RP) + (size_t)PER * RP + 8;
+    uint32_t *s_cnt = s_list + kDpSparseRowsBand;
+    const uint32_t r4 = blockIdx.y * kDpSparseRowsBand + 4 * tid;
+    uint32_t m4 = 0;
+    if (r4 < sp.mark_stride) m4 = *(const uint32_t *)(sp.marks + (size_t)ks * sp.mark_stride + r4);  // (stride % 16 == 0: whole words)
+    uint64_t bm[4];
+    uint32_t n_wave = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        bm[i] = __builtin_amdgcn_ballot_w64(((m4 >> (8 * i)) & 0xFFu) != 0);
+        n_wave += (uint32_t)__builtin_popcountll(bm[i]);
+    }
+    if (lane == 0) s_cnt[w] = n_wave;
+    __syncthreads();
+    uint32_t total = 0, at = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < (uint32_t)kDpWaves; i++) {
+        const uint32_t c = s_cnt[i];
+        at += i < w ? c : 0u;
+        total += c;
+    }
+    if (!total) return;  // (workgroup-uniform) no pair of this template in this row range: nothing staged
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm[i] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm[i], 0u));
+        if ((m4 >> (8 * i)) & 0xFFu) s_list[at + below] = r4 + (uint32_t)i;
+        at += (uint32_t)__builtin_popcountll(bm[i]);
+    }
+    const int mdl_n = (int)a.tpl_frames_s[ks];
+    dp_band_stage<G>(a, s_tpl, ks);
+    __syncthreads();
+    for (uint32_t p0 = w * NG; p0 < total; p0 += PER) {  // (wave-uniform) this wave's NG pairs of every round
+        dp_band_reset_col<G>(s_col, RP, j);
+        wave_sync();
+        const uint32_t p = p0 + lane / G;
+        const uint32_t b = p < total ? s_list[p] : 0xFFFFFFFFu;
+        dp_band_walk<G>(a, s_tpl, s_col, ks, mdl_n, b, j, sp.frames_stride);
+    }
+}
+
 // LDS of a band-kernel workgroup: the template image + one boundary column per group, both rows_pad long.  Reads may
 // run up to five rows / entries past the last step (the rounded-up step and the rows requested ahead): they land in the
 // next region of the image (values never used) and, for the last group, in the 32 spare bytes at the end.
@@ -337,25 +464,36 @@ static uint32_t dp_band_lds(uint32_t tpl_rows, int G, int waves, uint32_t *rows_
 // three of them fit a CU instead of one: their waves pile up on two of the four SIMDs)
 static int dp_waves_for(int G) { (void)G; return 4; }
 
-void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hipStream_t s)
+// LDS a sparse workgroup takes on top of the dense layout: the row list and the waves' counts (band form only)
+static constexpr uint32_t kDpSparseLds = kDpSparseRowsBand * 4u + 16u;
+
+// lanes per pair of a launch: 4 / 8 / 16 = the band kernel, 1 = k_dtw_dp_wave64; `lanes` is sr_set_dp_lanes' value (0 =
+// choose), `extra` the LDS a workgroup needs beside the dense layout
+static int dp_pick_lanes(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, uint32_t extra, uint32_t *rows_pad)
 {
-    if (!a.B || !a.K) return;
-    int G = (int)lanes;  // 4 / 8 / 16 lanes per pair of the band kernel, 1 = k_dtw_dp_wave64, 0 = choose
-    uint32_t rp = 0;
+    int G = (int)lanes;
     if (G != 1 && G != 4 && G != 8 && G != 16) {
         // 8 lanes per pair while three of its workgroups fit a CU (MI355X: 160 KiB in granules of 1 280 bytes): 111 ms per
         // 65 536 x 100 pairs at a 320-frame cap; one granule more and only two fit (153 ms) -- then 16 lanes per pair (half
         // the boundary columns, 120 ms with three or four workgroups per CU) is the better shape
-        auto wgs = [&](int g) { return budget.wgs_per_cu(dp_band_lds(a.tpl_rows, g, dp_waves_for(g), nullptr)); };
+        auto wgs = [&](int g) { return budget.wgs_per_cu(dp_band_lds(a.tpl_rows, g, dp_waves_for(g), nullptr) + extra); };
         G = (wgs(8) >= 3 || wgs(16) < 3) ? 8 : 16;
     }
-    if (G != 1 && (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > budget.stage_cap)) {
+    if (G != 1 && (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), rows_pad) + extra > budget.stage_cap)) {
         G = 16;  // fewer pairs per wave: fewer boundary columns
-        if (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), &rp) > budget.stage_cap) G = 1;
+        if (!a.tplR || dp_band_lds(a.tpl_rows, G, dp_waves_for(G), rows_pad) + extra > budget.stage_cap) G = 1;
     }
-    const int W = dp_waves_for(G);
     if (dev_hook(kHookDtwDebug))
-        std::fprintf(stderr, "sr_engine: full-DP scorer for %u template rows: %d lanes per pair\n", a.tpl_rows, G);
+        std::fprintf(stderr, "sr_engine: full-DP scorer for %u template rows%s: %d lanes per pair\n", a.tpl_rows, extra ? ", sparse" : "", G);
+    return G;
+}
+
+void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hipStream_t s)
+{
+    if (!a.B || !a.K) return;
+    uint32_t rp = 0;
+    const int G = dp_pick_lanes(a, lanes, budget, 0u, &rp);
+    const int W = dp_waves_for(G);
     const uint32_t per_wg = G == 1 ? 4u : (uint32_t)(W * (64 / G));  // utterances per workgroup (k_dtw_dp_wave64: one per wave)
     const size_t lds = G == 1 ? (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4 : dp_band_lds(a.tpl_rows, G, W, &rp);
     // the utterance blocks are the grid's second dimension (<= 65 535): larger batches go out in slices
@@ -375,10 +513,38 @@ void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hi
         else hipLaunchKernelGGL((k_dtw_dp_band<16, 4>), grid, block, lds, s, ba);
     }
 }
+
+// The marked pairs of a.B <= kDpSparseMaxRows rows (a.in_frames at frames_stride words; a.vad unused), scores by (row, slot)
+// into a.scores; pairs without a mark are not touched.  Same forms and fallbacks as launch_dtw_dp.
+void launch_dtw_dp_sparse(const DtwArgs &a, const uint8_t *marks, uint32_t mark_stride, uint32_t frames_stride, const uint32_t *tpl_rank,
+                          uint32_t lanes, const LdsBudget &budget, hipStream_t s)
+{
+    if (!a.B || !a.K) return;
+    uint32_t rp = 0;
+    const int G = dp_pick_lanes(a, lanes, budget, kDpSparseLds, &rp);
+    const int W = dp_waves_for(G);
+    const DpSparseArgs sp{marks, mark_stride, frames_stride, tpl_rank};
+    const dim3 block(64 * W);
+    if (G == 1) {  // (the flags of the mark check live in the boundary columns: the dense kernel's LDS)
+        const dim3 grid(a.K, (a.B + kDpSparseRowsWave - 1) / kDpSparseRowsWave);
+        hipLaunchKernelGGL(k_dtw_dp_wave64_sparse, grid, block, (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4, s, a, sp);
+        return;
+    }
+    const size_t lds = dp_band_lds(a.tpl_rows, G, W, &rp) + kDpSparseLds;
+    const dim3 grid(a.K, (a.B + kDpSparseRowsBand - 1) / kDpSparseRowsBand);
+    const DpBandArgs ba{a, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, rp};
+    if (G == 4) hipLaunchKernelGGL((k_dtw_dp_band_sparse<4, 4>), grid, block, lds, s, ba, sp);
+    else if (G == 8) hipLaunchKernelGGL((k_dtw_dp_band_sparse<8, 4>), grid, block, lds, s, ba, sp);
+    else hipLaunchKernelGGL((k_dtw_dp_band_sparse<16, 4>), grid, block, lds, s, ba, sp);
+}
 const char *dtw_dp_allow_lds(uint32_t bytes)
 {
     return allow_dynamic_lds({{(const void *)k_dtw_dp_wave64, "k_dtw_dp_wave64"}, {(const void *)k_dtw_dp_band<4, 4>, "k_dtw_dp_band<4, 4>"},
-                              {(const void *)k_dtw_dp_band<8, 4>, "k_dtw_dp_band<8, 4>"}, {(const void *)k_dtw_dp_band<16, 4>, "k_dtw_dp_band<16, 4>"}}, bytes);
+                              {(const void *)k_dtw_dp_band<8, 4>, "k_dtw_dp_band<8, 4>"}, {(const void *)k_dtw_dp_band<16, 4>, "k_dtw_dp_band<16, 4>"},
+                              {(const void *)k_dtw_dp_wave64_sparse, "k_dtw_dp_wave64_sparse"},
+                              {(const void *)k_dtw_dp_band_sparse<4, 4>, "k_dtw_dp_band_sparse<4, 4>"},
+                              {(const void *)k_dtw_dp_band_sparse<8, 4>, "k_dtw_dp_band_sparse<8, 4>"},
+                              {(const void *)k_dtw_dp_band_sparse<16, 4>, "k_dtw_dp_band_sparse<16, 4>"}}, bytes);
 }
 
 }  // namespace sr

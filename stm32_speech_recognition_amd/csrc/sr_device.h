@@ -249,6 +249,21 @@ struct NbestArgs {
 };
 void launch_nbest(const NbestArgs &a, hipStream_t s);
 
+// two-pass rescoring, the mark pass (k_rescore.hip): the slots of the candidate words of every row's input list
+struct RescoreMarkArgs {
+    const sr_nbest_entry *in;       // [n_rows][n_best] first-pass lists (read only)
+    uint32_t n_rows;
+    uint32_t n_best;
+    uint32_t K;
+    const uint32_t *order;          // the engine's word grouping, as NbestArgs
+    const uint32_t *group_start;
+    const uint32_t *group_of_slot;  // [K] index of the word group a slot belongs to
+    const uint32_t *tpl_rank;       // [K] rank of a slot in the store's length order
+    uint8_t *marks;                 // [K ranks][mark_stride] zeroed; 1 = score this (row, slot)
+    uint32_t mark_stride;
+};
+void launch_rescore_mark(const RescoreMarkArgs &a, hipStream_t s);
+
 // get_mdl (DTW.C:217-296): P independent pairs
 struct GetMdlArgs {
     const int16_t *in1;     // [P][rows1][12]

@@ -52,6 +52,10 @@ void launch_dtw(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
 void launch_dtw_cells(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
 void launch_dtw_quad(const DtwArgs &a, const DtwPlan &p, hipStream_t s);
 void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &lds, hipStream_t s);  // opt-in full-DP scorer (sr_set_dp_lanes)
+// two-pass rescoring: the full-DP score of the pairs marked in marks[template rank][row] (one byte per pair, mark_stride bytes
+// per template, a multiple of 16, rows past a.B zero), frame counts at a.in_frames[row * frames_stride]; unmarked pairs untouched
+void launch_dtw_dp_sparse(const DtwArgs &a, const uint8_t *marks, uint32_t mark_stride, uint32_t frames_stride, const uint32_t *tpl_rank,
+                          uint32_t lanes, const LdsBudget &lds, hipStream_t s);
 
 // sr_create: let every instance of the file's kernels take up to `bytes` of dynamic LDS (the default limit is 64 KiB);
 // returns the name of an instance that was refused, or nullptr

@@ -394,6 +394,7 @@ void sr_destroy(sr_engine *h)
     h->tplR.release();
     h->tpl_frames_s.release();
     h->tpl_orig.release();
+    h->tpl_rank.release();
     h->s_pcm.release();
     h->s_st_vad.release();
     h->s_st_tab.release();
@@ -417,6 +418,11 @@ void sr_destroy(sr_engine *h)
     h->wg_tab.release();
     h->s_nbest.release();
     h->s_nmatched.release();
+    h->s_rs_marks.release();
+    h->s_rs_scores.release();
+    h->s_rs_first.release();
+    h->s_rs_out.release();
+    h->s_rs_n.release();
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     for (auto &e : h->ev_call) (void)hipEventDestroy(e);
     for (auto &e : h->ev_chunk) (void)hipEventDestroy(e);
@@ -445,7 +451,7 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
     const uint32_t nc = h->nc;  // s16 per feature row; the staged kernels (k_dtw_lds, k_dtw_dp_band) are built for 12
     HIP_TRY(hipDeviceSynchronize());
     DevBuf<int16_t> n_tpl;
-    DevBuf<uint32_t> n_frames, n_tplR, n_frames_s, n_orig;
+    DevBuf<uint32_t> n_frames, n_tplR, n_frames_s, n_orig, n_rank;
     DevBuf<uint8_t> n_valid;
     bool fits = true;
     auto build = [&]() -> int {
@@ -495,6 +501,10 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
         HIP_TRY(hipMemcpy(n_tplR.p, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(n_frames_s.p, fs.data(), K * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(n_orig.p, order.data(), K * 4, hipMemcpyHostToDevice));
+        std::vector<uint32_t> rank(K);  // the inverse: where a slot stands in the length order
+        for (uint32_t ks = 0; ks < K; ks++) rank[order[ks]] = ks;
+        if ((rc = n_rank.reserve(K))) return rc;
+        HIP_TRY(hipMemcpy(n_rank.p, rank.data(), K * 4, hipMemcpyHostToDevice));
         return SR_OK;
     };
     const int rc = build();
@@ -505,6 +515,7 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
         n_tplR.release();
         n_frames_s.release();
         n_orig.release();
+        n_rank.release();
         return rc;
     }
     std::swap(h->tpl, n_tpl);
@@ -513,12 +524,14 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
     std::swap(h->tplR, n_tplR);
     std::swap(h->tpl_frames_s, n_frames_s);
     std::swap(h->tpl_orig, n_orig);
+    std::swap(h->tpl_rank, n_rank);
     n_tpl.release();  // the old store (nothing in flight: synchronised above)
     n_frames.release();
     n_valid.release();
     n_tplR.release();
     n_frames_s.release();
     n_orig.release();
+    n_rank.release();
     h->tpl_staged_ok = fits;
     h->K = K;
     h->tpl_rows = rows;

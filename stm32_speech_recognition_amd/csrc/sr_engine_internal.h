@@ -117,6 +117,7 @@ struct sr_engine {
     bool tpl_staged_ok = true;     // every coefficient of the store fits the -2*coef rows of tplR
     DevBuf<uint32_t> tplR;         // [rows][K] 32-byte rows (12 x s16 | norm | pad), templates ordered by length
     DevBuf<uint32_t> tpl_frames_s, tpl_orig;
+    DevBuf<uint32_t> tpl_rank;     // [K] rank of each slot in that order (the inverse of tpl_orig): the sparse full-DP scorer's marks
     uint32_t K = 0, tpl_rows = 0, tpl_stride = 0;
     DtwPlan plan;                  // which DTW kernel serves this store, in what shape (plan_dtw, when the store is set)
     uint32_t dp_lanes = 0;         // sr_set_dp_lanes: lanes per pair of the opt-in full-DP scorer (0 = default)
@@ -189,10 +190,17 @@ struct sr_engine {
     std::vector<uint32_t> word_labels;  // sr_set_word_map with labels (word_explicit); else word = slot / word_spw
     bool word_explicit = false;
     uint32_t word_spw = 1;
-    DevBuf<uint32_t> wg_tab;            // order[K] | group_start[n_words + 1] | word_id[n_words] (sr_word_groups)
+    DevBuf<uint32_t> wg_tab;            // order[K] | group_start[n_words + 1] | word_id[n_words] (sr_word_groups) | group_of_slot[K]
     uint32_t wg_K = 0, wg_words = 0;    // the store size the grouping was built for (0: none, or a map of another length)
     DevBuf<sr_nbest_entry> s_nbest;     // host-buffer forms: device copies of their N-best outputs
     DevBuf<uint32_t> s_nmatched;
+    // two-pass rescoring (sr_rescore.cpp): the pair marks [chunk][K ranks][mark stride] and the second-pass score rows [rows][K]
+    // of a call (its own matrix: s_scores may hold the first pass), the first-pass lists of a whole-path call that was handed no
+    // buffer for them, and the host-buffer forms' device copies of their outputs
+    DevBuf<uint8_t> s_rs_marks;
+    DevBuf<uint32_t> s_rs_scores;
+    DevBuf<sr_nbest_entry> s_rs_first, s_rs_out;
+    DevBuf<uint32_t> s_rs_n;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant
@@ -227,3 +235,19 @@ int config_framing(const sr_config *cfg, ConfigFraming *out);  // sr_engine.cpp:
 int regroup_words(sr_engine *h, bool drained);
 int check_nbest(const sr_engine *h, uint32_t n_best, const void *nbest);  // n_best range, non-null output, a grouping for this store
 NbestArgs nbest_args(const sr_engine *h, const uint32_t *d_scores, uint32_t n_rows, const NbestOut &nb, size_t row0);
+// ---- two-pass rescoring (sr_rescore.cpp) ----------------------------------------------------------------------------------
+// what a rescoring form adds to the N-best call it extends (device pointers)
+struct RescoreOut {
+    sr_nbest_entry *out;   // [rows][n_best]
+    uint32_t *n_rescored;  // optional
+};
+static constexpr uint32_t kRescoreMaxRows = 65535u * 256u;  // rows of one rescoring: the sparse scorer's grid (256 rows per workgroup at least)
+static inline uint32_t rescore_mark_stride(uint32_t n_rows) { return (n_rows + 15u) & ~15u; }  // bytes of marks per template
+// check_nbest's rules for `out` + the conditions of sr_dtw_dp_batch_dev
+int check_rescore(const sr_engine *h, uint32_t n_best, const void *out);
+// room for `n_chunks` concurrent rescorings of at most `per` rows each, n_rows rows in all
+int reserve_rescore(sr_engine *h, uint32_t n_chunks, uint32_t per, size_t n_rows);
+// the second pass of rows [row0, row0 + n) of a call as chunk `chunk` of reserve_rescore's layout, enqueued on s: d_mfcc /
+// d_frames / in / out / n_rescored point at the CALL's first row
+int launch_rescore(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride, uint32_t n_best,
+                   const sr_nbest_entry *in, const RescoreOut &out, uint32_t chunk, uint32_t per, size_t row0, uint32_t n, hipStream_t s);

@@ -113,22 +113,55 @@ int sr_recognize_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, u
 
 // sr_recognize_batch, then the N-best of the score rows it left in the engine's scratch (all of them, whichever way the
 // captures went up), on the null stream the plain call's copies ran on
-int sr_recognize_nbest_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, uint32_t n_best,
-                             sr_nbest_entry *nbest, uint32_t *n_matched, sr_result *results, uint32_t *scores, int16_t *mfcc,
-                             sr_vad_rec *vad)
+// (nbest == NULL: the rescored form that does not want the first-pass list back; the checks are the caller's then)
+static int recognize_nbest_host(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, uint32_t n_best,
+                                sr_nbest_entry *nbest, uint32_t *n_matched, sr_result *results, uint32_t *scores, int16_t *mfcc,
+                                sr_vad_rec *vad)
 {
-    if (!h || !pcm || !results) return fail(SR_ERR_BAD_ARG, "null argument");
-    if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
-    int rc = check_nbest(h, n_best, nbest);
-    if (rc) return rc;
+    int rc;
     if ((rc = recognize_host(h, pcm, pcm_stride, false, buf_len, B, results, scores, mfcc, vad)) || B == 0) return rc;
     ENTER_DEVICE(h);
     if ((rc = h->s_nbest.reserve((size_t)B * n_best))) return rc;
     if ((rc = h->s_nmatched.reserve(B))) return rc;
     launch_nbest(nbest_args(h, h->s_scores.p, B, NbestOut{n_best, h->s_nbest.p, h->s_nmatched.p}, 0), nullptr);
     HIP_TRY(hipGetLastError());
-    COPY_DOWN(nbest, h->s_nbest.p, (size_t)B * n_best * sizeof(sr_nbest_entry));
+    if (nbest) COPY_DOWN(nbest, h->s_nbest.p, (size_t)B * n_best * sizeof(sr_nbest_entry));
     if (n_matched) COPY_DOWN(n_matched, h->s_nmatched.p, (size_t)B * 4);
+    return SR_OK;
+}
+
+int sr_recognize_nbest_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, uint32_t n_best,
+                             sr_nbest_entry *nbest, uint32_t *n_matched, sr_result *results, uint32_t *scores, int16_t *mfcc,
+                             sr_vad_rec *vad)
+{
+    if (!h || !pcm || !results) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
+    if (int rc = check_nbest(h, n_best, nbest)) return rc;
+    return recognize_nbest_host(h, pcm, pcm_stride, buf_len, B, n_best, nbest, n_matched, results, scores, mfcc, vad);
+}
+
+// sr_recognize_nbest_batch, then ONE second pass over all B rows where that call left them in the engine's scratch: feature
+// records, the frame counts inside the VAD records, the first-pass lists
+int sr_recognize_rescored_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, uint32_t n_best,
+                                sr_nbest_entry *nbest, uint32_t *n_matched, sr_nbest_entry *rescored, uint32_t *n_rescored,
+                                sr_result *results, uint32_t *scores, int16_t *mfcc, sr_vad_rec *vad)
+{
+    if (!h || !pcm || !results) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
+    int rc = check_rescore(h, n_best, rescored);
+    if (rc) return rc;
+    if (rescored == nbest) return fail(SR_ERR_BAD_ARG, "the rescored list must not be the first-pass list");
+    if (B > kRescoreMaxRows) return fail(SR_ERR_BAD_ARG, "batch too large");
+    if ((rc = recognize_nbest_host(h, pcm, pcm_stride, buf_len, B, n_best, nbest, n_matched, results, scores, mfcc, vad)) || B == 0) return rc;
+    ENTER_DEVICE(h);
+    if ((rc = h->s_rs_out.reserve((size_t)B * n_best))) return rc;
+    if ((rc = h->s_rs_n.reserve(B))) return rc;
+    if ((rc = reserve_rescore(h, 1, B, B))) return rc;
+    if ((rc = launch_rescore(h, h->s_mfcc.p, &h->s_vad.p->frm_num, sizeof(sr_vad_rec) / 4, n_best, h->s_nbest.p,
+                             RescoreOut{h->s_rs_out.p, h->s_rs_n.p}, 0, B, 0, B, nullptr)))
+        return rc;
+    COPY_DOWN(rescored, h->s_rs_out.p, (size_t)B * n_best * sizeof(sr_nbest_entry));
+    if (n_rescored) COPY_DOWN(n_rescored, h->s_rs_n.p, (size_t)B * 4);
     return SR_OK;
 }
 

@@ -230,14 +230,21 @@ int sr_dtw_batch_dev(sr_engine *h, const int16_t *d_mfcc, const sr_vad_rec *d_va
     return SR_OK;
 }
 
-// sr_recognize_batch_dev, and with nb the N-best form: k_nbest per chunk on the chunk's stream, behind its slot scan
+// sr_recognize_batch_dev, and with nb the N-best form: k_nbest per chunk on the chunk's stream, behind its slot scan; with rs
+// (and nb, whose list may then live in the engine's scratch) the rescored form: the second pass per chunk, behind its k_nbest
 static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                                sr_result *d_results, uint32_t *d_scores, int16_t *d_mfcc, sr_vad_rec *d_vad, void *stream,
-                               const NbestOut *nb)
+                               const NbestOut *nb_in, const RescoreOut *rs = nullptr)
 {
     if (!h || !d_results) return fail(SR_ERR_BAD_ARG, "null argument");
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
-    if (nb) {
+    NbestOut nb_own{0, nullptr, nullptr};
+    const NbestOut *nb = nb_in;
+    if (rs) {
+        if (int rcr = check_rescore(h, nb_in->n_best, rs->out)) return rcr;
+        if (rs->out == nb_in->out) return fail(SR_ERR_BAD_ARG, "the rescored list must not be the first-pass list");
+        if (B > kRescoreMaxRows) return fail(SR_ERR_BAD_ARG, "batch too large");
+    } else if (nb) {
         if (int rcn = check_nbest(h, nb->n_best, nb->out)) return rcn;
     }
     if (B == 0) return SR_OK;
@@ -246,8 +253,13 @@ static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm
     if ((rc = check_batch(h, B))) return rc;
     ENTER_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
-    const bool own_scratch = !d_vad || !d_mfcc || !d_scores;  // (the host-buffer entry points pass the scratch buffers explicitly)
+    const bool own_scratch = !d_vad || !d_mfcc || !d_scores || rs;  // (the host-buffer entry points pass the scratch buffers explicitly)
     if (own_scratch && (rc = order_after_scratch_users(h, s))) return rc;
+    if (rs && !nb_in->out) {  // the first-pass list is not wanted: it lives in the engine's scratch
+        if ((rc = h->s_rs_first.reserve((size_t)B * nb_in->n_best))) return rc;
+        nb_own = NbestOut{nb_in->n_best, h->s_rs_first.p, nb_in->n_matched};
+        nb = &nb_own;
+    }
     if (!d_vad) {
         if ((rc = h->s_vad.reserve(B))) return rc;
         d_vad = h->s_vad.p;
@@ -288,6 +300,7 @@ static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm
         for (uint32_t i = 0; i < n_streams; i++) HIP_TRY(hipStreamWaitEvent(h->st_pipe[i], h->ev_fork, 0));
     }
     const uint32_t per = (B + n_chunks - 1) / n_chunks;
+    if (rs && (rc = reserve_rescore(h, n_chunks, per, B))) return rc;
     uint32_t c = 0;
     bool counted = false;
     for (uint32_t b0 = 0; b0 < B; b0 += per, c++) {
@@ -311,6 +324,9 @@ static int recognize_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm
         if (prof) HIP_TRY(hipEventRecord(ev[4], sc));
         // (outside the four stage intervals of sr_get_stage_ms; reads the scores, so it does not depend on which kernel did the scan)
         if (nb) launch_nbest(nbest_args(h, da.scores, n, *nb, b0), sc);
+        // the second pass of the chunk: its feature records, the frame counts in its VAD records, the list k_nbest just wrote
+        if (rs && (rc = launch_rescore(h, d_mfcc, &d_vad->frm_num, sizeof(sr_vad_rec) / 4, nb->n_best, nb->out, *rs, c, per, b0, n, sc)))
+            return rc;
     }
     if (n_chunks > 1) {
         for (uint32_t i = 0; i < n_streams; i++) {
@@ -341,6 +357,16 @@ int sr_recognize_nbest_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t p
 {
     const NbestOut nb{n_best, d_nbest, d_n_matched};
     return recognize_batch_dev(h, d_pcm, pcm_stride, buf_len, B, d_results, d_scores, d_mfcc, d_vad, stream, &nb);
+}
+
+int sr_recognize_rescored_batch_dev(sr_engine *h, const uint16_t *d_pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                                    uint32_t n_best, sr_nbest_entry *d_nbest, uint32_t *d_n_matched, sr_nbest_entry *d_rescored,
+                                    uint32_t *d_n_rescored, sr_result *d_results, uint32_t *d_scores, int16_t *d_mfcc,
+                                    sr_vad_rec *d_vad, void *stream)
+{
+    const NbestOut nb{n_best, d_nbest, d_n_matched};
+    const RescoreOut rs{d_rescored, d_n_rescored};
+    return recognize_batch_dev(h, d_pcm, pcm_stride, buf_len, B, d_results, d_scores, d_mfcc, d_vad, stream, &nb, &rs);
 }
 
 // Every segment the VAD finds (up to max_seg), each matched like segment 0.  The firmware's spch_recg stops at

@@ -51,6 +51,10 @@ int regroup_words(sr_engine *h, bool drained)
     std::vector<uint32_t> tab(order);
     tab.insert(tab.end(), start.begin(), start.end());
     tab.insert(tab.end(), ids.begin(), ids.end());
+    std::vector<uint32_t> group_of(h->K);  // the rescoring mark pass goes from a slot to its word group
+    for (uint32_t w = 0; w + 1 < start.size(); w++)
+        for (uint32_t p = start[w]; p < start[w + 1]; p++) group_of[order[p]] = w;
+    tab.insert(tab.end(), group_of.begin(), group_of.end());
     ENTER_DEVICE(h);
     if (!drained) HIP_TRY(hipDeviceSynchronize());
     DevBuf<uint32_t> fresh;

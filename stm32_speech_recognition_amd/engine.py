@@ -279,9 +279,45 @@ class Engine:
                                               C.c_void_p(stream)))
         return nb, nm
 
-    def recognize_nbest(self, pcm, n_best, want_scores=True, want_mfcc=True, want_vad=True, buf_len=None):
+    def rescore_nbest(self, mfcc, frames, nbest):
+        """sr_rescore_nbest_dp, the second pass: mfcc int16 [n_rows, max_frames, 12], frames uint32 [n_rows], nbest NBEST_DTYPE
+        [n_rows, n_best] (a first-pass list: nbest() of dtw() scores, or any list of candidate slots).  Every slot of every
+        candidate word gets its full-DP score (dtw_dp's value) and the words are ranked again on the device.  Returns
+        (entries NBEST_DTYPE [n_rows, n_best], n_rescored uint32 [n_rows])."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        nbest = np.ascontiguousarray(nbest, dtype=NBEST_DTYPE)
+        n = mfcc.shape[0]
+        nbest = nbest.reshape(n, -1)
+        assert len(frames) == n
+        out = np.zeros_like(nbest)
+        nr = np.zeros(n, dtype=np.uint32)
+        self._check(self.L.sr_rescore_nbest_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n),
+                                               C.c_uint32(nbest.shape[1]), _vp(nbest), _vp(out), _vp(nr)))
+        return out, nr
+
+    def rescore_nbest_dev(self, mfcc, frames, nbest, frames_stride=1, stream=None):
+        """sr_rescore_nbest_dp_dev on device tensors: mfcc int16 [n_rows, max_frames, 12]; nbest int32 [n_rows, n_best, 4];
+        frames = a tensor (or view) whose first element is row 0's frame count, the next row's frames_stride 32-bit words
+        further on: 1 for a plain int32 [n_rows], 4 for results[:, 2] and stream segment records, 6 for live segment records,
+        12 for vad[:, 9].  Asynchronous; returns (entries int32 [n_rows, n_best, 4], n_rescored int32 [n_rows])."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and nbest.is_cuda and nbest.is_contiguous()
+        n, n_best = nbest.shape[0], nbest.shape[1]
+        assert mfcc.shape[0] == n
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        out = torch.empty(n, n_best, 4, dtype=torch.int32, device=mfcc.device)
+        nr = torch.empty(n, dtype=torch.int32, device=mfcc.device)
+        self._check(self.L.sr_rescore_nbest_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                   C.c_uint32(n_best), _vp(nbest), _vp(out), _vp(nr), C.c_void_p(stream)))
+        return out, nr
+
+    def recognize_nbest(self, pcm, n_best, want_scores=True, want_mfcc=True, want_vad=True, buf_len=None, rescore=False):
         """recognize() plus the n_best best words of every capture (sr_recognize_nbest_batch): the same dict with
-        nbest NBEST_DTYPE [B, n_best] and n_matched uint32 [B]."""
+        nbest NBEST_DTYPE [B, n_best] and n_matched uint32 [B].  rescore=True (sr_recognize_rescored_batch): also rescored
+        NBEST_DTYPE [B, n_best] and n_rescored uint32 [B], the second pass of every list (rescore_nbest)."""
         pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
         B, S = pcm.shape
         buf_len = S if buf_len is None else buf_len
@@ -292,6 +328,13 @@ class Engine:
         vd = np.zeros(B, dtype=VAD_DTYPE) if want_vad else None
         nb = np.zeros((B, max(n_best, 0)), dtype=NBEST_DTYPE)
         nm = np.zeros(B, dtype=np.uint32)
+        if rescore:
+            rs = np.zeros((B, max(n_best, 0)), dtype=NBEST_DTYPE)
+            nr = np.zeros(B, dtype=np.uint32)
+            self._check(self.L.sr_recognize_rescored_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(buf_len), C.c_uint32(B),
+                                                           C.c_uint32(n_best), _vp(nb), _vp(nm), _vp(rs), _vp(nr), _vp(res),
+                                                           _vp(sc), _vp(mf), _vp(vd)))
+            return dict(results=res, scores=sc, mfcc=mf, vad=vd, nbest=nb, n_matched=nm, rescored=rs, n_rescored=nr)
         self._check(self.L.sr_recognize_nbest_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(buf_len), C.c_uint32(B),
                                                     C.c_uint32(n_best), _vp(nb), _vp(nm), _vp(res), _vp(sc), _vp(mf), _vp(vd)))
         return dict(results=res, scores=sc, mfcc=mf, vad=vd, nbest=nb, n_matched=nm)
@@ -535,10 +578,12 @@ class Engine:
             _vp(out["results"]), _vp(out["scores"]), _vp(out["mfcc"]), _vp(out["vad"]), C.c_void_p(stream)))
         return out
 
-    def recognize_nbest_dev(self, pcm, out, n_best, buf_len=None, stream=None):
+    def recognize_nbest_dev(self, pcm, out, n_best, buf_len=None, stream=None, rescore=False):
         """recognize_dev() plus the n_best best words of every capture (sr_recognize_nbest_batch_dev): out gains
         out["nbest"] int32 [B, n_best, 4] (sr_nbest_entry records; nbest_from_torch()) and out["n_matched"] int32 [B],
-        allocated here unless the caller put them there.  Asynchronous."""
+        allocated here unless the caller put them there.  rescore=True (sr_recognize_rescored_batch_dev): out also gains
+        out["rescored"] int32 [B, n_best, 4] and out["n_rescored"] int32 [B], the second pass of every list; a caller who
+        puts out["nbest"] = False there does not get the first-pass list back.  Asynchronous."""
         import torch
         assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
         B, S = pcm.shape
@@ -548,6 +593,17 @@ class Engine:
             out["nbest"] = torch.empty(B, max(n_best, 0), 4, dtype=torch.int32, device=pcm.device)
         if "n_matched" not in out:
             out["n_matched"] = torch.empty(B, dtype=torch.int32, device=pcm.device)
+        if rescore:
+            if out.get("rescored") is None:
+                out["rescored"] = torch.empty(B, max(n_best, 0), 4, dtype=torch.int32, device=pcm.device)
+            if "n_rescored" not in out:
+                out["n_rescored"] = torch.empty(B, dtype=torch.int32, device=pcm.device)
+            first = None if out["nbest"] is False else out["nbest"]
+            self._check(self.L.sr_recognize_rescored_batch_dev(
+                self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S if buf_len is None else buf_len), C.c_uint32(B), C.c_uint32(n_best),
+                _vp(first), _vp(out["n_matched"]), _vp(out["rescored"]), _vp(out["n_rescored"]), _vp(out["results"]),
+                _vp(out["scores"]), _vp(out["mfcc"]), _vp(out["vad"]), C.c_void_p(stream)))
+            return out
         self._check(self.L.sr_recognize_nbest_batch_dev(
             self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S if buf_len is None else buf_len), C.c_uint32(B), C.c_uint32(n_best),
             _vp(out["nbest"]), _vp(out["n_matched"]), _vp(out["results"]), _vp(out["scores"]), _vp(out["mfcc"]),
