@@ -468,6 +468,52 @@ int sr_set_dp_lanes(sr_engine *h, uint32_t lanes);
 int sr_dtw_dp_batch(sr_engine *h, const int16_t *in_mfcc, const uint32_t *in_frames, uint32_t B, uint32_t *scores);
 int sr_dtw_dp_batch_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, const sr_vad_rec *d_vad,
                         uint32_t B, uint32_t *d_scores, void *stream);
+
+/* ------------------------------------------------------------------ word spotting: subsequence DTW inside long features
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  Every other scorer takes an utterance the VAD has cut out, first frame to last
+ * frame.  This one has a free start and a free end: for a feature row in[0..N) and a valid template mdl[0..M) it says where
+ * inside the row the template matches best, and how well.  No existing call, record or score changes.
+ *   d(x,y)   get_dis (DTW.C:45-62) of in[x] and mdl[y], as everywhere.
+ *   paths    start at some (s, 0), end at some (e, M-1); steps (+1,+1), (+1,0), (0,+1), every horizontal or vertical step
+ *            directly after a diagonal one (symmetric P = 1: slope 1/2..2, so no band and no length gate); cost = sum of d.
+ *            D(x,0) = d(x,0), S(x,0) = x;
+ *            D(x,y) = d(x,y) + min(D(x-1,y-1), D(x-2,y-1) + d(x-1,y), D(x-1,y-2) + d(x,y-1)),  D = INF outside the grid.
+ *   ties     candidates are compared as (cost, start) pairs: S(x,y) is the smallest start among the paths of minimal cost.
+ *   score    q(e) = D(e,M-1) / (L + M), L = e - S(e,M-1) + 1, u32 division.  The first reachable end frame is M / 2.
+ *   windows  win_frames = 0: one window per row; else window w holds the end frames [w*win_frames, min((w+1)*win_frames, N))
+ *            and n_win = ceil(max_frames / win_frames) for every row.  A window's hit is the FIRST minimum of q(e) over its
+ *            reachable end frames (ascending e, strict <).  A window without a reachable end (past N, N <= M/2, N = 0, an
+ *            invalid slot) gets {SR_DIS_ERR, 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF}. */
+typedef struct sr_spot_hit { /* 16 bytes */
+    uint32_t dis;   /* q(e); SR_DIS_ERR: no hit */
+    uint32_t start; /* S, 0-based frame of the row */
+    uint32_t end;   /* e, 0-based, inclusive */
+    uint32_t acc;   /* D(e, M-1) */
+} sr_spot_hit;
+/* Stage level, DEVICE buffers: d_mfcc[n_rows][max_frames][12]; d_in_frames / frames_stride as for sr_rescore_nbest_dp_dev (so
+ * &d_vad[0].frm_num with stride 12 serves sr_mfcc_batch_dev's records; a failed record has frm_num 0).  A count above
+ * max_frames is clamped; nothing outside rows [0, frames) of a feature record is read.  d_hits[(row*n_win + w)*K + slot]
+ * (required): every record is written whole on every call.  d_scores (optional): the dis fields alone, u32 [n_rows*n_win][K]
+ * -- the layout sr_nbest_batch_dev takes with n_rows*n_win rows, so word map, N-best and rejection margin apply per window.
+ * Asynchronous on `stream`, no host synchronisation, no read-back.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_NO_TEMPLATES; SR_ERR_BAD_ARG
+ * for a null required pointer, frames_stride 0, n_rows*n_win above 16 776 960, a store whose longest template exceeds
+ * sr_spot_geometry's out[2]. */
+int sr_spot_dp_batch_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                         uint32_t win_frames, sr_spot_hit *d_hits, uint32_t *d_scores, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_spot_dp_batch(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                     uint32_t win_frames, sr_spot_hit *hits, uint32_t *scores);
+/* Whole path on HOST buffers: sr_mfcc_batch_status (its arguments, its per-record failure rules; mfcc, frm_num and status
+ * may be NULL here) followed by the stage over those rows; a failed record has no hits.  The device whole path is
+ * sr_mfcc_batch_dev followed by sr_spot_dp_batch_dev. */
+int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
+                  const int32_t *end, const uint32_t *mid, uint32_t win_frames, sr_spot_hit *hits, uint32_t *scores,
+                  int16_t *mfcc, uint32_t *frm_num, uint32_t *status);
+/* Host-only, MI355X's LDS figures: out[0] = n_win, out[1] = LDS bytes of one workgroup for a store whose longest template has
+ * tpl_rows rows, out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
+int sr_spot_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t win_frames, uint32_t out[4]);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -568,6 +614,8 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "mag_table_off"                  the frame kernel sends QUIET frames down the MID tier (v_sqrt_f32 root, literal filterbank
  *                                    term -- exact over the QUIET range too) instead of the magnitude table; read per launch
  *   "stream_tile_frames"             frames per tile of the stream VAD scan (16..1024, a multiple of 16; default 512)
+ *   "spot_chunk_cols"                end frames per kernel chunk of the word spotter (1..16383; default eight times the
+ *                                    longest template, 256 at least); read per launch and by sr_spot_geometry
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

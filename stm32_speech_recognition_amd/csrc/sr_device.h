@@ -26,6 +26,7 @@ enum DevHook {
     kHookMagCheapOff,     // "mag_cheap_off": sr_create behaves as if the device sweep of the cheap magnitude form had failed (bound 0)
     kHookMagTableOff,     // "mag_table_off": k_mfcc sends QUIET frames down the MID tier (cheap root, literal filterbank term) instead of the table
     kHookStreamTile,      // "stream_tile_frames": frames per tile of the stream VAD scan (16..1024, a multiple of 16)
+    kHookSpotChunk,       // "spot_chunk_cols": columns per chunk of the word spotter (1..16383; read per launch)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -263,6 +264,32 @@ struct RescoreMarkArgs {
     uint32_t mark_stride;
 };
 void launch_rescore_mark(const RescoreMarkArgs &a, hipStream_t s);
+
+// word spotting (k_spot.hip): subsequence DTW of every template inside every feature row.  The end frames of a row are cut
+// into chunks of chunk_cols columns, one wave each.  split = 0: a chunk holds `per` whole windows and writes their records
+// itself; split = 1: a window is cut into `per` chunks, each leaves one partial record and k_spot_finish reduces them.
+struct SpotArgs {
+    const int16_t *mfcc;        // [n_rows][max_frames][12]
+    const uint32_t *in_frames;  // frame count of row r at in_frames[r * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t n_rows;
+    uint32_t max_frames;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a boundary column
+    uint32_t n_win;             // windows per row
+    uint32_t win;               // end frames per window (max_frames when there is one window)
+    uint32_t chunk_cols;
+    uint32_t n_chunks;          // chunks per row
+    uint32_t split, per;
+    sr_spot_hit *hits;          // [n_rows * n_win][K]
+    uint32_t *scores;           // optional [n_rows * n_win][K]
+    sr_spot_hit *part;          // split only: [n_rows * n_chunks][K]
+};
+void launch_spot(const SpotArgs &a, hipStream_t s);
 
 // get_mdl (DTW.C:217-296): P independent pairs
 struct GetMdlArgs {

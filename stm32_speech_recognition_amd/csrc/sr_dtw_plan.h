@@ -57,12 +57,44 @@ void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &lds, hipSt
 void launch_dtw_dp_sparse(const DtwArgs &a, const uint8_t *marks, uint32_t mark_stride, uint32_t frames_stride, const uint32_t *tpl_rank,
                           uint32_t lanes, const LdsBudget &lds, hipStream_t s);
 
+// Word spotter (k_spot.hip).  LDS of a workgroup: the template image (32-byte rows) and one boundary column per wave (two
+// (cost, start) pairs = 16 bytes per row), both as long as the store's longest template.
+constexpr uint32_t kSpotWaves = 4;  // waves = chunks per workgroup
+inline uint32_t spot_lds_bytes(uint32_t tpl_len) { return tpl_len * (32u + kSpotWaves * 16u); }
+inline uint32_t spot_max_tpl(const LdsBudget &lds) { return lds.stage_cap / spot_lds_bytes(1); }
+// How the end frames of a row are cut into chunks (SpotArgs).  cols = 0: the default, eight times the longest template (the
+// lead-in of 2M - 2 columns a chunk recomputes is then a quarter of its own columns), 256 at least.  A chunk never straddles
+// a window edge: windows no longer than that are packed whole into a chunk, longer ones are cut into chunks of their own.
+struct SpotGeom {
+    uint32_t n_win, win, chunk_cols, n_chunks, split, per;
+};
+inline SpotGeom spot_geom(uint32_t tpl_len, uint32_t max_frames, uint32_t win_frames, uint32_t cols)
+{
+    SpotGeom g;
+    g.win = win_frames && win_frames < max_frames ? win_frames : max_frames;
+    g.n_win = (max_frames + g.win - 1) / g.win;
+    if (!cols) cols = tpl_len * 8u < 256u ? 256u : (tpl_len * 8u + 63u) & ~63u;
+    cols = cols > 16383u ? 16383u : cols;
+    g.split = g.win > cols;
+    if (g.split) {
+        g.chunk_cols = cols;
+        g.per = (g.win + cols - 1) / cols;  // chunks per window
+        g.n_chunks = g.n_win * g.per;
+    } else {
+        g.per = cols / g.win;               // windows per chunk
+        g.chunk_cols = g.per * g.win;
+        g.n_chunks = (g.n_win + g.per - 1) / g.per;
+    }
+    return g;
+}
+
 // sr_create: let every instance of the file's kernels take up to `bytes` of dynamic LDS (the default limit is 64 KiB);
 // returns the name of an instance that was refused, or nullptr
 const char *dtw_lds_allow_lds(uint32_t bytes);
 const char *dtw_cells_allow_lds(uint32_t bytes);
 const char *dtw_quad_allow_lds(uint32_t bytes);
 const char *dtw_dp_allow_lds(uint32_t bytes);
+const char *spot_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

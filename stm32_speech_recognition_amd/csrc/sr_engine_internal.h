@@ -201,6 +201,10 @@ struct sr_engine {
     DevBuf<uint32_t> s_rs_scores;
     DevBuf<sr_nbest_entry> s_rs_first, s_rs_out;
     DevBuf<uint32_t> s_rs_n;
+    // word spotting (sr_spot.cpp): the partial records of a call whose windows are longer than a kernel chunk, and the
+    // host-buffer forms' device copies of their outputs
+    DevBuf<sr_spot_hit> s_spot_part, s_spot_hits;
+    DevBuf<uint32_t> s_spot_scores;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant
@@ -251,3 +255,9 @@ int reserve_rescore(sr_engine *h, uint32_t n_chunks, uint32_t per, size_t n_rows
 // d_frames / in / out / n_rescored point at the CALL's first row
 int launch_rescore(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride, uint32_t n_best,
                    const sr_nbest_entry *in, const RescoreOut &out, uint32_t chunk, uint32_t per, size_t row0, uint32_t n, hipStream_t s);
+// ---- word spotting (sr_spot.cpp) --------------------------------------------------------------------------------------------
+// the conditions of sr_spot_dp_batch_dev on the engine and the store, and how a call of n_rows rows is cut into chunks
+int check_spot(const sr_engine *h, uint32_t n_rows, uint32_t win_frames, SpotGeom *g);
+// the stage over n_rows rows, enqueued on s (d_scores may be nullptr); reserves the partial records it needs
+int launch_spot_stage(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride, uint32_t n_rows,
+                      const SpotGeom &g, sr_spot_hit *d_hits, uint32_t *d_scores, hipStream_t s);

@@ -291,6 +291,39 @@ int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride,
     return hc.finish(rc);
 }
 
+// Word spotting, whole path (sr_spot.cpp has the stage): the records and the frame kernel of sr_mfcc_batch_status, then the
+// stage over the feature rows where they are, frame counts straight from the records (a failed one has frm_num 0: no hits)
+int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
+                  const int32_t *end, const uint32_t *mid, uint32_t win_frames, sr_spot_hit *hits, uint32_t *scores, int16_t *mfcc,
+                  uint32_t *frm_num, uint32_t *status)
+{
+    if (!h || !pcm || !start || !end || !mid || !hits) return fail(SR_ERR_BAD_ARG, "null argument");
+    SpotGeom g;
+    if (int rc_chk = check_spot(h, B, win_frames, &g)) return rc_chk;
+    if (B == 0) return SR_OK;
+    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
+    ENTER_HOST_CALL(h);
+    std::vector<sr_vad_rec> recs;
+    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
+    if (rc) return rc;
+    const size_t n_mfcc = h->mfcc_elems(B), n_rec = (size_t)B * g.n_win * h->K;
+    if ((rc = h->s_vad.reserve(B))) return rc;
+    if ((rc = h->s_mfcc.reserve(n_mfcc))) return rc;
+    if ((rc = h->s_spot_hits.reserve(n_rec))) return rc;
+    if (scores && (rc = h->s_spot_scores.reserve(n_rec))) return rc;
+    uint64_t ds = 0;
+    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
+    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
+    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
+    if ((rc = launch_spot_stage(h, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, g, h->s_spot_hits.p,
+                                scores ? h->s_spot_scores.p : nullptr, nullptr)))
+        return rc;
+    COPY_DOWN(hits, h->s_spot_hits.p, n_rec * sizeof(sr_spot_hit));
+    if (scores) COPY_DOWN(scores, h->s_spot_scores.p, n_rec * 4);
+    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
+    return SR_OK;
+}
+
 // the frame kernels' per-frame intermediate values for explicit segments: the records of sr_mfcc_batch_status, staged like
 // its large-batch path
 int sr_frame_features_batch(sr_engine *h, int kind, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,

@@ -30,7 +30,9 @@ NBEST_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("dis", "<u4"), ("coun
 NO_WORD, NBEST_MAX = 0xFFFFFFFF, 16
 # live sessions (sr_live_seg): a segment of a channel, 64-bit sample offsets since the channel's recording began
 LIVE_SEG_DTYPE = np.dtype([("channel", "<u4"), ("frm_num", "<u4"), ("start", "<i8"), ("end", "<i8")])
-assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48
+# word spotting (sr_spot_hit): q(e), the start and end frame of the best match inside a window, its accumulated cost
+SPOT_DTYPE = np.dtype([("dis", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4")])
+assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
 assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16 and NBEST_DTYPE.itemsize == 16
 assert LIVE_SEG_DTYPE.itemsize == 24
 
@@ -523,6 +525,57 @@ class Engine:
                                                C.c_void_p(stream)))
         return scores
 
+    def spot_windows(self, win_frames=0):
+        """windows per row of a spotting call with this engine's max_frames (sr_spot_geometry's out[0])"""
+        return 1 if win_frames == 0 else -(-self.max_frames // win_frames)
+
+    def spot(self, mfcc, frames, win_frames=0):
+        """OPT-IN word spotter (sr_spot_dp_batch): where inside each feature row every template matches best.  mfcc int16
+        [n_rows, max_frames, 12], frames uint32 [n_rows]; win_frames 0 = one window per row.  Returns (hits SPOT_DTYPE
+        [n_rows, n_win, K], scores uint32 [n_rows, n_win, K] = the dis fields, the layout nbest() takes)."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        shape = (n, self.spot_windows(win_frames), self.n_templates)
+        hits, sc = np.zeros(shape, dtype=SPOT_DTYPE), np.zeros(shape, dtype=np.uint32)
+        self._check(self.L.sr_spot_dp_batch(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), C.c_uint32(win_frames),
+                                            _vp(hits), _vp(sc)))
+        return hits, sc
+
+    def spot_dev(self, mfcc, frames, hits, scores=None, win_frames=0, frames_stride=1, stream=None):
+        """sr_spot_dp_batch_dev on device tensors: mfcc int16 [n_rows, max_frames, 12]; frames as for rescore_nbest_dev (the
+        first row's count, the next one frames_stride 32-bit words further on: 12 for vad[:, 9]); hits int32 [n_rows, n_win,
+        K, 4]; scores (optional) int32 [n_rows, n_win, K].  Asynchronous on `stream`; returns hits."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and hits.is_contiguous()
+        n = mfcc.shape[0]
+        assert hits.numel() == n * self.spot_windows(win_frames) * self.n_templates * 4
+        assert scores is None or (scores.is_contiguous() and scores.numel() * 4 == hits.numel())
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_spot_dp_batch_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                C.c_uint32(win_frames), _vp(hits), _vp(scores), C.c_void_p(stream)))
+        return hits
+
+    def spot_pcm(self, pcm, start, end, mid, win_frames=0):
+        """sr_spot_batch, the host whole path: mfcc_status() of segment [start[b], end[b]) of row b, then spot() over those
+        rows.  Returns dict(hits, scores, mfcc, frm_num, status); a failed record has no hits."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        shape = (B, self.spot_windows(win_frames), self.n_templates)
+        out = dict(hits=np.zeros(shape, dtype=SPOT_DTYPE), scores=np.zeros(shape, dtype=np.uint32),
+                   mfcc=np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16), frm_num=np.zeros(B, dtype=np.uint32),
+                   status=np.zeros(B, dtype=np.uint32))
+        self._check(self.L.sr_spot_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S), C.c_uint32(B), _vp(start), _vp(end),
+                                         _vp(mid), C.c_uint32(win_frames), _vp(out["hits"]), _vp(out["scores"]),
+                                         _vp(out["mfcc"]), _vp(out["frm_num"]), _vp(out["status"])))
+        return out
+
     def get_mdl(self, in1, n1, in2, n2, mdl_rows):
         """get_mdl (DTW.C:217-296) on P pairs: in1 int16 [P, rows1, 12], in2 int16 [P, rows2, 12].
         Returns (mdl int16 [P, mdl_rows, 12], mdl_frames uint32 [P], dis uint32 [P])."""
@@ -697,6 +750,17 @@ class Engine:
         n = C.c_uint32(0)
         self._check(self.L.sr_get_stage_launches(self.h, C.byref(n)))
         return dict(vad=ms[0], mfcc=ms[1], dtw=ms[2], argmin=ms[3], total=ms[4], launches_per_call=n.value)
+
+
+def spot_geometry(tpl_rows, max_frames, win_frames=0, testing=False):
+    """Host-only sr_spot_geometry: dict(n_win, lds_bytes of one workgroup for a store whose longest template has tpl_rows
+    rows, max_tpl_rows that fit, chunk_cols = end frames per kernel chunk)."""
+    L = load_library(testing)
+    out = (C.c_uint32 * 4)()
+    rc = L.sr_spot_geometry(C.c_uint32(tpl_rows), C.c_uint32(max_frames), C.c_uint32(win_frames), out)
+    if rc != 0:
+        raise SrError(f"sr_spot_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(n_win=out[0], lds_bytes=out[1], max_tpl_rows=out[2], chunk_cols=out[3])
 
 
 def live_geometry(chunk_max, max_frames=119, **kw):
