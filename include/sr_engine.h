@@ -514,6 +514,88 @@ int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32
  * tpl_rows rows, out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
 int sr_spot_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t win_frames, uint32_t out[4]);
 
+/* ------------------------------------------------------------------ full-DP alignment and word models from many examples
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this
+ * section says HOW the two were aligned, and builds word models from many examples on top of that (DTW barycentre
+ * averaging).  Neither call reads or writes the engine's template store; no existing call, record or score changes.
+ *   pair     an input row in[0..N) and a reference ref[0..R), both 12 x s16 per frame.
+ *   d(x,y)   get_dis (DTW.C:45-62), as in every other scorer.
+ *   gate     sr_dtw_dp_batch's: N >= 1, R >= 1 and not (N > 2R or 2N < R).
+ *   cells    those inside dtw_limit's parallelogram (DTW.C:76-109).
+ *   D        D(1,1) = d(1,1); D(x,y) = d(x,y) + min(D(x-1,y-1), D(x-1,y), D(x,y-1)).
+ *   acc, dis acc = D(N,R), dis = acc / (N + R): exactly the value sr_dtw_dp_batch_dev writes for the same pair.
+ *   path     traced back from (N,R) to (1,1): at each cell the reachable predecessor of minimal D; on ties (x-1,y-1), then
+ *            (x-1,y), then (x,y-1).  The steps are monotone, so the path is one span per input frame:
+ *            span[x] = y_first | y_last << 16, the 0-based inclusive reference rows matched to input frame x, and
+ *            path_len = sum over x of (y_last - y_first + 1).
+ *   status   SR_AL_TOO_LONG: N (after the clamp to max_frames) above SR_ALIGN_MAX_FRAMES -- it takes precedence;
+ *            SR_AL_GATED: an empty row, a pair that fails the gate, an unreachable end cell, or an invalid reference (its
+ *            index >= n_ref, its frame count 0 or above ref_rows); SR_AL_OK otherwise.
+ * A record that is not OK has dis = SR_DIS_ERR, acc = 0xFFFFFFFF, path_len = 0 and a span row of 0xFFFFFFFF.  On every call
+ * the span entries at x >= N are 0xFFFFFFFF; every record and every span row is written whole.
+ * SR_ALIGN_MAX_FRAMES: the predecessor marks cost 2 bits per cell -- 256 KiB per pair at 1024 x 1024, 67 MB at the 16 383-frame
+ * cap -- and enrolment material is words, not recordings. */
+#define SR_ALIGN_MAX_FRAMES 1024u
+#define SR_AL_OK 0u
+#define SR_AL_GATED 1u
+#define SR_AL_TOO_LONG 2u
+typedef struct sr_align_rec { /* 16 bytes */
+    uint32_t dis;
+    uint32_t acc;
+    uint32_t path_len;
+    uint32_t status;
+} sr_align_rec;
+/* DEVICE buffers: d_mfcc[n_rows][max_frames][12]; d_in_frames / frames_stride as for sr_rescore_nbest_dp_dev (a count above
+ * max_frames is clamped; nothing outside rows [0, frames) of a record or of a reference is read).  d_ref[n_ref][ref_rows][12],
+ * d_ref_frames[n_ref].  d_ref_of_row[n_rows]: the reference of each row; NULL: row r pairs with reference r, then n_ref must be
+ * >= n_rows.  d_rec[n_rows] (required), d_span[n_rows][max_frames] (optional).  Asynchronous on `stream`, no host
+ * synchronisation, no read-back; a call whose marks do not fit the LDS keeps them in the engine's scratch and runs as
+ * several launches on the same stream once they exceed 256 MiB.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_BAD_ARG for a null required
+ * pointer, frames_stride 0, ref_rows 0 or above SR_ALIGN_MAX_FRAMES, n_ref 0, n_ref < n_rows without d_ref_of_row, d_rec and
+ * d_span overlapping. */
+int sr_dtw_dp_align_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                        const int16_t *d_ref, const uint32_t *d_ref_frames, uint32_t ref_rows, uint32_t n_ref,
+                        const uint32_t *d_ref_of_row, sr_align_rec *d_rec, uint32_t *d_span, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_dtw_dp_align(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                    const int16_t *ref, const uint32_t *ref_frames, uint32_t ref_rows, uint32_t n_ref, const uint32_t *ref_of_row,
+                    sr_align_rec *rec, uint32_t *span);
+/* DBA training: M word models refined from E = ex_start[M] example rows in n_iter iterations (1..16).  Model m has the
+ * centroid C_m of F_m = cen_frames[m] frames and the examples e in [ex_start[m], ex_start[m+1]).  One iteration:
+ *   - every example is aligned as input against C_m as reference;
+ *   - for every OK example and every path point (x,y): sum[y][c] += in_e[x][c], cnt[y] += 1;
+ *   - C'_m[y][c] = cnt[y] ? sum[y][c] / cnt[y] : C_m[y][c], s32 division truncating toward zero (get_mean, DTW.C:195-205);
+ *   - F_m never changes; a model without an OK example stays as it is; output rows at or beyond F_m are zero;
+ *   - a centroid whose frame count is 0 or above cen_rows is invalid: all its cen_rows rows are copied through unchanged
+ *     and its examples are GATED.
+ * Iterations chain: the output of iteration i is the centroid set of iteration i + 1.  The sums are integers, so the result
+ * does not depend on the order in which examples are accumulated: two runs give identical bytes.
+ * stats (optional) [n_iter][M]: the OK and the failed examples of model m in that iteration and the sum of the OK examples'
+ * acc against the centroid that ENTERED it.
+ * ex_start[M+1] is a HOST array in both forms (ascending, ex_start[0] = 0), so that the call can check before anything is
+ * launched that (examples of m) x min(max_frames, SR_ALIGN_MAX_FRAMES) <= 65 535 for every model: then cnt stays within u16
+ * range and |sum| < 2^31 -- the s32 accumulators are exact.
+ * d_cen_in / d_cen_out[M][cen_rows][12] (the layout sr_set_templates_dense takes with tpl_stride = cen_rows*12); d_cen_out must
+ * not overlap d_cen_in.  The device form is ONE asynchronous operation on `stream`; marks, accumulators and the intermediate
+ * centroid set live in the engine's scratch.
+ * Errors as sr_dtw_dp_align_dev's, and SR_ERR_BAD_ARG for M 0, cen_rows 0 or above SR_ALIGN_MAX_FRAMES, n_iter outside 1..16,
+ * an ex_start that is not ascending from 0, the accumulator bound above, overlapping outputs. */
+typedef struct sr_train_stat { /* 16 bytes */
+    uint32_t n_ok;
+    uint32_t n_fail;
+    uint64_t acc;
+} sr_train_stat;
+int sr_train_models_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride,
+                           const uint32_t *ex_start, uint32_t M, const int16_t *d_cen_in, const uint32_t *d_cen_frames,
+                           uint32_t cen_rows, uint32_t n_iter, int16_t *d_cen_out, sr_train_stat *d_stats, void *stream);
+int sr_train_models_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, const uint32_t *ex_start,
+                       uint32_t M, const int16_t *cen_in, const uint32_t *cen_frames, uint32_t cen_rows, uint32_t n_iter,
+                       int16_t *cen_out, sr_train_stat *stats);
+/* Host-only, MI355X's LDS figures: out[0] = bytes of global scratch per pair for the predecessor marks (0: they live in LDS),
+ * out[1] = pairs per launch, out[2] = SR_ALIGN_MAX_FRAMES. */
+int sr_align_geometry(uint32_t max_frames, uint32_t ref_rows, uint32_t out[3]);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -616,6 +698,9 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "stream_tile_frames"             frames per tile of the stream VAD scan (16..1024, a multiple of 16; default 512)
  *   "spot_chunk_cols"                end frames per kernel chunk of the word spotter (1..16383; default eight times the
  *                                    longest template, 256 at least); read per launch and by sr_spot_geometry
+ *   "align_pairs"                    pairs per launch of the full-DP aligner (default: what 256 MiB of scratch hold); read
+ *                                    per call and by sr_align_geometry
+ *   "align_marks_global"             the aligner keeps its predecessor marks in global scratch even where they fit the LDS
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

@@ -27,6 +27,8 @@ enum DevHook {
     kHookMagTableOff,     // "mag_table_off": k_mfcc sends QUIET frames down the MID tier (cheap root, literal filterbank term) instead of the table
     kHookStreamTile,      // "stream_tile_frames": frames per tile of the stream VAD scan (16..1024, a multiple of 16)
     kHookSpotChunk,       // "spot_chunk_cols": columns per chunk of the word spotter (1..16383; read per launch)
+    kHookAlignPairs,      // "align_pairs": pairs per launch of the full-DP aligner (read per call and by sr_align_geometry)
+    kHookAlignGlobal,     // "align_marks_global": the aligner keeps its predecessor marks in global scratch whatever fits the LDS
     kHookCount
 };
 #ifdef SR_TESTING
@@ -290,6 +292,55 @@ struct SpotArgs {
     sr_spot_hit *part;          // split only: [n_rows * n_chunks][K]
 };
 void launch_spot(const SpotArgs &a, hipStream_t s);
+
+// full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
+// of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the
+// marks are indexed by the pair of the launch.
+struct AlignArgs {
+    const int16_t *mfcc;         // [n_rows][max_frames][12]
+    const uint32_t *in_frames;   // frame count of row r at in_frames[r * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t max_frames;
+    const int16_t *ref;          // [n_ref][ref_rows][12]
+    const uint32_t *ref_frames;  // [n_ref]; 0 or above ref_rows: an invalid reference
+    uint32_t ref_rows, n_ref;
+    const uint32_t *ref_of_row;  // optional [n_rows]; NULL: row r pairs with reference r
+    sr_align_rec *rec;
+    uint32_t *span;              // optional, [..][max_frames]
+    uint32_t out0;
+    uint32_t *marks;             // [n_pairs][mark_words] in global scratch; NULL: the marks live in LDS
+    uint32_t mark_w;             // mark words per input column: 16 reference rows per word, odd
+    uint32_t mark_words;         // mark words per pair: columns of the longest admissible row x mark_w
+    uint32_t row0, n_pairs;
+};
+void launch_align(const AlignArgs &a, size_t lds_bytes, hipStream_t s);
+// DBA training on top of it: the path points of the OK pairs of a launch summed into the models' accumulators, then one
+// pass that divides, keeps, zeroes and clears
+struct AlignAccumArgs {
+    const int16_t *mfcc;
+    const uint32_t *in_frames;
+    uint32_t frames_stride;
+    uint32_t max_frames;
+    const sr_align_rec *rec;     // [n_pairs] of the launch
+    const uint32_t *span;        // [n_pairs][max_frames]
+    const uint32_t *model_of;    // [n_rows] model of each example
+    const uint32_t *cen_frames;  // [M]
+    uint32_t cen_rows;
+    int32_t *sum;                // [M][cen_rows][12]
+    uint32_t *cnt;               // [M][cen_rows]
+    sr_train_stat *stats;        // optional [M]: this iteration's row
+    uint32_t row0, n_pairs;
+};
+void launch_align_accum(const AlignAccumArgs &a, hipStream_t s);
+struct AlignFinalArgs {
+    const int16_t *cen_cur;      // [M][cen_rows][12] the centroids that entered the iteration
+    int16_t *cen_next;           // [M][cen_rows][12]
+    const uint32_t *cen_frames;
+    uint32_t cen_rows, M;
+    int32_t *sum;
+    uint32_t *cnt;
+};
+void launch_align_finalise(const AlignFinalArgs &a, hipStream_t s);
 
 // get_mdl (DTW.C:217-296): P independent pairs
 struct GetMdlArgs {

@@ -88,6 +88,37 @@ inline SpotGeom spot_geom(uint32_t tpl_len, uint32_t max_frames, uint32_t win_fr
     return g;
 }
 
+// Full-DP aligner (k_align.hip): one wave = one workgroup per pair.  LDS: the reference image (32-byte rows), the boundary
+// column (one word per row) and, when they fit, the predecessor marks: 2 bits per cell, 16 reference rows per word, mark_w
+// words per input column (odd, so that the lanes' words spread over the banks).  The marks stay in LDS while
+// kAlignMinWgs workgroups -- two waves per SIMD -- still fit a CU; otherwise they go to global scratch, and a call is cut
+// into launches of as many pairs as kAlignScratch holds.
+constexpr uint32_t kAlignMinWgs = 8;
+constexpr size_t kAlignScratch = (size_t)256 << 20;
+constexpr uint32_t kAlignMaxPairs = 1u << 20;  // pairs of one launch at most
+struct AlignPlan {
+    uint32_t mark_w, mark_words;  // words per column, per pair
+    uint32_t lds_bytes;           // of one workgroup
+    bool lds_marks;
+    uint32_t pair_bytes;          // global scratch per pair: the marks (0 in LDS) + `extra`
+    uint32_t pairs;               // per launch
+};
+inline AlignPlan align_plan(uint32_t max_frames, uint32_t ref_rows, const LdsBudget &lds, size_t extra, bool force_global, uint32_t forced_pairs)
+{
+    AlignPlan p;
+    const uint32_t n_cap = max_frames < SR_ALIGN_MAX_FRAMES ? max_frames : SR_ALIGN_MAX_FRAMES;
+    p.mark_w = ((ref_rows + 15u) / 16u) | 1u;
+    p.mark_words = n_cap * p.mark_w;
+    const uint32_t base = ref_rows * 36u, with = base + p.mark_words * 4u;
+    p.lds_marks = !force_global && with <= lds.stage_cap && lds.wgs_per_cu(with) >= kAlignMinWgs;
+    p.lds_bytes = p.lds_marks ? with : base;
+    p.pair_bytes = (uint32_t)((p.lds_marks ? 0u : p.mark_words * 4u) + extra);
+    const size_t fit = p.pair_bytes ? kAlignScratch / p.pair_bytes : kAlignMaxPairs;
+    p.pairs = (uint32_t)(fit < 1 ? 1 : fit > kAlignMaxPairs ? kAlignMaxPairs : fit);
+    if (forced_pairs) p.pairs = forced_pairs < kAlignMaxPairs ? forced_pairs : kAlignMaxPairs;
+    return p;
+}
+
 // sr_create: let every instance of the file's kernels take up to `bytes` of dynamic LDS (the default limit is 64 KiB);
 // returns the name of an instance that was refused, or nullptr
 const char *dtw_lds_allow_lds(uint32_t bytes);
@@ -95,6 +126,7 @@ const char *dtw_cells_allow_lds(uint32_t bytes);
 const char *dtw_quad_allow_lds(uint32_t bytes);
 const char *dtw_dp_allow_lds(uint32_t bytes);
 const char *spot_allow_lds(uint32_t bytes);
+const char *align_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

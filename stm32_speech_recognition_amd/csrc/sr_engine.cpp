@@ -21,7 +21,8 @@ static std::atomic<int64_t> g_hooks[kHookCount];
 int64_t dev_hook(DevHook h) { return g_hooks[h].load(std::memory_order_relaxed); }
 static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc", "mfcc_grid", "perturb_log_thr",
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
-                                                   "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols"};
+                                                   "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols",
+                                                   "align_pairs", "align_marks_global"};
 #endif
 }  // namespace sr
 
@@ -263,7 +264,7 @@ int sr_create(const sr_config *cfg, sr_engine **out)
         (void)hipGetLastError();
     }
     // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
-    for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds}) {
+    for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, align_allow_lds}) {
         if (const char *kernel = allow(h->lds.per_wg)) {
             delete h;
             return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));
@@ -426,6 +427,13 @@ void sr_destroy(sr_engine *h)
     h->s_spot_part.release();
     h->s_spot_hits.release();
     h->s_spot_scores.release();
+    h->s_al_marks.release();
+    h->s_al_span.release();
+    h->s_al_rec.release();
+    h->s_al_map.release();
+    h->s_al_sum.release();
+    h->s_al_cnt.release();
+    h->s_al_cen.release();
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     for (auto &e : h->ev_call) (void)hipEventDestroy(e);
     for (auto &e : h->ev_chunk) (void)hipEventDestroy(e);

@@ -205,6 +205,12 @@ struct sr_engine {
     // host-buffer forms' device copies of their outputs
     DevBuf<sr_spot_hit> s_spot_part, s_spot_hits;
     DevBuf<uint32_t> s_spot_scores;
+    // full-DP alignment and DBA training (sr_align.cpp): the predecessor marks of one launch when they do not fit the LDS; a
+    // training call's per-launch spans and records, its example -> model map, accumulators and intermediate centroid set
+    DevBuf<uint32_t> s_al_marks, s_al_span, s_al_map, s_al_cnt;
+    DevBuf<sr_align_rec> s_al_rec;
+    DevBuf<int32_t> s_al_sum;
+    DevBuf<int16_t> s_al_cen;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant

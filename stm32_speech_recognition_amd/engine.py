@@ -32,7 +32,12 @@ NO_WORD, NBEST_MAX = 0xFFFFFFFF, 16
 LIVE_SEG_DTYPE = np.dtype([("channel", "<u4"), ("frm_num", "<u4"), ("start", "<i8"), ("end", "<i8")])
 # word spotting (sr_spot_hit): q(e), the start and end frame of the best match inside a window, its accumulated cost
 SPOT_DTYPE = np.dtype([("dis", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4")])
+# full-DP alignment (sr_align_rec) and DBA training statistics (sr_train_stat)
+ALIGN_DTYPE = np.dtype([("dis", "<u4"), ("acc", "<u4"), ("path_len", "<u4"), ("status", "<u4")])
+TRAIN_STAT_DTYPE = np.dtype([("n_ok", "<u4"), ("n_fail", "<u4"), ("acc", "<u8")])
+AL_OK, AL_GATED, AL_TOO_LONG, ALIGN_MAX_FRAMES = 0, 1, 2, 1024
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
+assert ALIGN_DTYPE.itemsize == 16 and TRAIN_STAT_DTYPE.itemsize == 16
 assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16 and NBEST_DTYPE.itemsize == 16
 assert LIVE_SEG_DTYPE.itemsize == 24
 
@@ -576,6 +581,104 @@ class Engine:
                                          _vp(out["mfcc"]), _vp(out["frm_num"]), _vp(out["status"])))
         return out
 
+    # ---- full-DP alignment and word models from many examples -----------------------------------------
+    def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
+        """OPT-IN (sr_dtw_dp_align): the optimal warping path of the full-DP scorer for every (row, reference) pair.  mfcc int16
+        [n, max_frames, 12], frames uint32 [n]; ref int16 [n_ref, ref_rows, 12], ref_frames uint32 [n_ref]; ref_of_row uint32
+        [n] or None (row r pairs with reference r).  Returns (rec ALIGN_DTYPE [n], span uint32 [n, max_frames] or None):
+        span[r, x] = y_first | y_last << 16, 0xFFFFFFFF past the row's frames and for a pair that was not aligned."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        ref = np.ascontiguousarray(ref, dtype=np.int16)
+        ref_frames = np.ascontiguousarray(ref_frames, dtype=np.uint32)
+        n, n_ref = mfcc.shape[0], ref.shape[0]
+        assert len(frames) == n and ref.shape[2] == N_COEF and len(ref_frames) == n_ref
+        if ref_of_row is not None:
+            ref_of_row = np.ascontiguousarray(ref_of_row, dtype=np.uint32)
+            assert len(ref_of_row) == n
+        rec = np.zeros(n, dtype=ALIGN_DTYPE)
+        span = np.zeros((n, self.max_frames), dtype=np.uint32) if want_span else None
+        self._check(self.L.sr_dtw_dp_align(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), _vp(ref), _vp(ref_frames),
+                                           C.c_uint32(ref.shape[1]), C.c_uint32(n_ref), _vp(ref_of_row), _vp(rec), _vp(span)))
+        return rec, span
+
+    def align_dev(self, mfcc, frames, ref, ref_frames, rec, span=None, ref_of_row=None, frames_stride=1, stream=None):
+        """sr_dtw_dp_align_dev on device tensors: mfcc int16 [n, max_frames, 12]; frames as for rescore_nbest_dev; ref int16
+        [n_ref, ref_rows, 12], ref_frames int32 [n_ref]; rec int32 [n, 4]; span (optional) int32 [n, max_frames]; ref_of_row
+        (optional) int32 [n].  Asynchronous on `stream`; returns rec."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and ref.is_contiguous() and rec.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and (span is None or (span.is_contiguous() and span.numel() == n * self.max_frames))
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_dtw_dp_align_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n), _vp(ref),
+                                               _vp(ref_frames), C.c_uint32(ref.shape[1]), C.c_uint32(ref.shape[0]), _vp(ref_of_row),
+                                               _vp(rec), _vp(span), C.c_void_p(stream)))
+        return rec
+
+    def train_models(self, mfcc, frames, ex_start, cen, cen_frames, n_iter=4):
+        """OPT-IN (sr_train_models_dp): DTW barycentre averaging.  Model m is refined from the example rows
+        [ex_start[m], ex_start[m + 1]) of mfcc int16 [E, max_frames, 12] (frames uint32 [E]), starting from cen int16
+        [M, cen_rows, 12] with cen_frames uint32 [M].  Returns (centroids int16 [M, cen_rows, 12] -- with cen_frames the layout
+        set_templates_dense takes --, stats TRAIN_STAT_DTYPE [n_iter, M])."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        ex_start = np.ascontiguousarray(ex_start, dtype=np.uint32)
+        cen = np.ascontiguousarray(cen, dtype=np.int16)
+        cen_frames = np.ascontiguousarray(cen_frames, dtype=np.uint32)
+        M = cen.shape[0]
+        assert cen.shape[2] == N_COEF and len(cen_frames) == M and len(ex_start) == M + 1 and len(frames) == mfcc.shape[0]
+        assert int(ex_start[-1]) <= mfcc.shape[0]
+        out = np.zeros_like(cen)
+        stats = np.zeros((n_iter, M), dtype=TRAIN_STAT_DTYPE)
+        self._check(self.L.sr_train_models_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), _vp(ex_start), C.c_uint32(M), _vp(cen),
+                                              _vp(cen_frames), C.c_uint32(cen.shape[1]), C.c_uint32(n_iter), _vp(out), _vp(stats)))
+        return out, stats
+
+    def train_models_dev(self, mfcc, frames, ex_start, cen_in, cen_frames, cen_out, n_iter=4, stats=None, frames_stride=1, stream=None):
+        """sr_train_models_dp_dev on device tensors (ex_start: a HOST sequence of M + 1 counts): cen_in / cen_out int16
+        [M, cen_rows, 12], cen_frames int32 [M], stats (optional) int32 [n_iter, M, 4].  One asynchronous operation on `stream`;
+        returns cen_out."""
+        import torch
+        ex_start = np.ascontiguousarray(ex_start, dtype=np.uint32)
+        M = cen_in.shape[0]
+        assert mfcc.is_cuda and mfcc.is_contiguous() and cen_in.is_contiguous() and cen_out.is_contiguous()
+        assert len(ex_start) == M + 1 and int(ex_start[-1]) <= mfcc.shape[0] and cen_out.shape == cen_in.shape
+        assert stats is None or (stats.is_contiguous() and stats.numel() * stats.element_size() == n_iter * M * 16)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_train_models_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), _vp(ex_start), C.c_uint32(M),
+                                                  _vp(cen_in), _vp(cen_frames), C.c_uint32(cen_in.shape[1]), C.c_uint32(n_iter),
+                                                  _vp(cen_out), _vp(stats), C.c_void_p(stream)))
+        return cen_out
+
+    def train_words(self, mfcc, frames, labels, n_iter=4, init=None):
+        """Word models from labelled examples: the rows are grouped by label (ascending label, rows of a word in their order),
+        each word starts from its first example -- or from init = (centroids int16 [M, rows, 12], frames [M]) in ascending
+        label order -- and train_models refines it.  Returns (centroids int16 [M, rows, 12], frames uint32 [M], word_ids
+        uint32 [M]): set_templates_dense(centroids, frames) and set_word_map(word_ids) make them the store."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        frames = np.minimum(np.ascontiguousarray(frames, dtype=np.uint32), self.max_frames)
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        assert len(labels) == len(frames) == mfcc.shape[0]
+        word_ids, counts = np.unique(labels, return_counts=True)
+        order = np.argsort(labels, kind="stable")
+        ex_start = np.concatenate(([0], np.cumsum(counts))).astype(np.uint32)
+        if init is None:
+            first = order[ex_start[:-1]]
+            cen_frames = frames[first]
+            cen = np.zeros((len(word_ids), max(int(cen_frames.max()), 1) + 1, N_COEF), np.int16)  # (one row of slack, as a store has)
+            for m, e in enumerate(first):
+                cen[m, :cen_frames[m]] = mfcc[e, :cen_frames[m]]
+        else:
+            cen, cen_frames = np.ascontiguousarray(init[0], dtype=np.int16), np.ascontiguousarray(init[1], dtype=np.uint32)
+            assert cen.shape[0] == len(word_ids) == len(cen_frames)
+        out, _ = self.train_models(mfcc[order], frames[order], ex_start, cen, cen_frames, n_iter)
+        return out, cen_frames.copy(), word_ids.astype(np.uint32)
+
     def get_mdl(self, in1, n1, in2, n2, mdl_rows):
         """get_mdl (DTW.C:217-296) on P pairs: in1 int16 [P, rows1, 12], in2 int16 [P, rows2, 12].
         Returns (mdl int16 [P, mdl_rows, 12], mdl_frames uint32 [P], dis uint32 [P])."""
@@ -761,6 +864,17 @@ def spot_geometry(tpl_rows, max_frames, win_frames=0, testing=False):
     if rc != 0:
         raise SrError(f"sr_spot_geometry error {rc}: {L.sr_last_error().decode()}")
     return dict(n_win=out[0], lds_bytes=out[1], max_tpl_rows=out[2], chunk_cols=out[3])
+
+
+def align_geometry(max_frames, ref_rows, testing=False):
+    """Host-only sr_align_geometry: dict(scratch_bytes per pair for the predecessor marks (0: they live in LDS), pairs per
+    launch, max_frames = SR_ALIGN_MAX_FRAMES)."""
+    L = load_library(testing)
+    out = (C.c_uint32 * 3)()
+    rc = L.sr_align_geometry(C.c_uint32(max_frames), C.c_uint32(ref_rows), out)
+    if rc != 0:
+        raise SrError(f"sr_align_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(scratch_bytes=out[0], pairs=out[1], max_frames=out[2])
 
 
 def live_geometry(chunk_max, max_frames=119, **kw):
