@@ -514,6 +514,73 @@ int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32
  * tpl_rows rows, out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
 int sr_spot_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t win_frames, uint32_t out[4]);
 
+/* ------------------------------------------------------------------ connected-word decoding: level-building DTW
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The spotter says where each template matches best, slot by slot; this section
+ * says which SEQUENCE of words a feature row in[0..N) contains (N clamped to max_frames): digits or a command and its
+ * argument spoken without pauses.  Level l holds the best parse of every prefix of the row into exactly l words; one level is
+ * one spotter-shaped pass whose start row carries the previous level's costs.  No existing call, record or score changes.
+ *   d(x,y)   get_dis (DTW.C:45-62), as everywhere.
+ *   words    a word is a path of the spotter's kind through one valid slot k of M_k frames: from (s, 0) to (e, M_k-1), steps
+ *            (+1,+1), (+1,0), (0,+1), every horizontal or vertical step directly after a diagonal one, cost = sum of d.
+ *   E_0(p)   cost of the prefix of length p (p = 0..N) without a word: p * skip_cost when skipping is on (skip_cost !=
+ *            SR_DIS_ERR), else E_0(0) = 0 and E_0(p > 0) = INF.
+ *   level l  >= 1, per slot: the spotter's recurrence with a CHARGED start, D(x,0) = E_{l-1}(x) + d(x,0), S(x,0) = x, the
+ *            start unreachable where E_{l-1}(x) is INF; everything else as in the word spotting section.
+ *   A_l(p)   p >= 1: the minimum over the valid slots k of (D_k(p-1, M_k-1) + word_cost, S, k), candidates compared as
+ *            (cost, start, slot): a tie goes to the smallest start, then to the smallest slot.
+ *   E_l(p)   min(A_l(p).cost, E_l(p-1) + skip_cost), the second term only when skipping is on; E_l(0) = INF.
+ *   count    n = n_words_exact when that is nonzero, else the n of 1..max_words with the smallest E_n(N), the fewest words
+ *            among equal costs.  No finite E_n(N) (an empty row, no valid slot, no parse): status SR_CH_NONE.
+ *   trace    p = N; for l = n down to 1: while A_l(p) is unreachable or A_l(p).cost != E_l(p), frame p-1 is skipped and
+ *            p -= 1; word l is A_l(p): its slot, start = S, end = p-1; then p = S.  The p frames left after level 1 are
+ *            leading skipped frames (none when skipping is off).  Filler between and after words is as short as the cost allows.
+ *   limits   max_words 1..16; skip_cost <= 65 535 or SR_DIS_ERR; word_cost <= 2^24; a store of at most 65 536 slots.  With
+ *            d <= 65 536, at most 3L cells in a word over L frames and N <= 16 383 every cost stays below
+ *            3 * 16 383 * 65 536 + 16 * 2^24 < 2^32: u32 costs are exact.  Arguments outside these limits are refused. */
+#define SR_CH_OK 0u
+#define SR_CH_NONE 1u
+typedef struct sr_chain_rec { /* 16 bytes */
+    uint32_t cost;    /* E_n(N); SR_DIS_ERR unless status is SR_CH_OK */
+    uint32_t n_words; /* n; 0 unless OK */
+    uint32_t skipped; /* frames of the row that belong to no word; 0 unless OK */
+    uint32_t status;  /* SR_CH_OK / SR_CH_NONE */
+} sr_chain_rec;
+typedef struct sr_chain_word { /* 32 bytes */
+    uint32_t word;     /* the engine's word map (sr_set_word_map) applied to slot */
+    uint32_t slot;
+    uint32_t start;    /* 0-based frame of the row */
+    uint32_t end;      /* 0-based, inclusive */
+    uint32_t acc;      /* the word's own path cost, without word_cost */
+    uint32_t dis;      /* acc / (L + M), L = end - start + 1, as the spotter's q */
+    uint32_t cum;      /* E_l at the word's end */
+    uint32_t reserved; /* 0 */
+} sr_chain_word;
+/* Stage level, DEVICE buffers: d_mfcc / d_in_frames / frames_stride as for sr_spot_dp_batch_dev; nothing outside rows
+ * [0, frames) of a feature record is read.  d_rec[n_rows] and d_words[n_rows][max_words] (required; word l of a row at index
+ * l-1, entries at or beyond n_words all ones), d_level_cost (optional) u32 [n_rows][max_words] = E_l(N) or SR_DIS_ERR: every
+ * record and every word row is written whole on every call.  One asynchronous operation on `stream` (a row's keys and prefix
+ * costs live in the engine's scratch, sr_decode_geometry), no host synchronisation, no read-back; two runs give the same bytes.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_NO_TEMPLATES; SR_ERR_BAD_ARG
+ * for a null required pointer, frames_stride 0, an argument outside the limits above, n_words_exact > max_words, a word map
+ * that does not fit the store, a store whose longest template exceeds sr_decode_geometry's out[2], outputs that overlap. */
+int sr_decode_words_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                           uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *d_rec,
+                           sr_chain_word *d_words, uint32_t *d_level_cost, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_decode_words_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                       uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec,
+                       sr_chain_word *words, uint32_t *level_cost);
+/* Whole path on HOST buffers: sr_mfcc_batch_status (its arguments, its per-record failure rules; mfcc, frm_num and status
+ * may be NULL here) followed by the stage over those rows; a failed record has no parse.  The device whole path is
+ * sr_mfcc_batch_dev followed by sr_decode_words_dp_dev. */
+int sr_decode_words_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
+                          const int32_t *end, const uint32_t *mid, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost,
+                          uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, int16_t *mfcc,
+                          uint32_t *frm_num, uint32_t *status);
+/* Host-only, MI355X's LDS figures: out[0] = scratch bytes per row, out[1] = rows per launch group (what 256 MiB of scratch
+ * hold, 65 535 at most), out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
+int sr_decode_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t max_words, uint32_t out[4]);
+
 /* ------------------------------------------------------------------ full-DP alignment and word models from many examples
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this
  * section says HOW the two were aligned, and builds word models from many examples on top of that (DTW barycentre
@@ -701,6 +768,10 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "align_pairs"                    pairs per launch of the full-DP aligner (default: what 256 MiB of scratch hold); read
  *                                    per call and by sr_align_geometry
  *   "align_marks_global"             the aligner keeps its predecessor marks in global scratch even where they fit the LDS
+ *   "chain_chunk_cols"               end frames per kernel chunk of the connected-word decoder (as "spot_chunk_cols"); read per
+ *                                    call and by sr_decode_geometry
+ *   "chain_rows"                     rows per launch group of the connected-word decoder (default: what 256 MiB of scratch
+ *                                    hold); read per call and by sr_decode_geometry
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

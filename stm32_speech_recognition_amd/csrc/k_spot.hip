@@ -19,25 +19,11 @@
 // a segmented scan over the lanes of a sweep plus a carry from sweep to sweep.  Chunks never straddle a window edge
 // (spot_geom): either a chunk holds whole windows and writes their records, or it is one of the pieces of a long window and
 // leaves a partial record that k_spot_finish reduces in chunk order.  No atomics; every record is written exactly once.
-#include "sr_dtw_dev.h"
 #include "sr_dtw_plan.h"
+#include "sr_spot_dev.h"
 
 namespace sr {
 
-constexpr uint64_t kSpotInf = ~0ull;
-
-__device__ __forceinline__ uint64_t spot_min(uint64_t a, uint64_t b) { return b < a ? b : a; }
-__device__ __forceinline__ uint64_t spot_add(uint64_t a, uint32_t d) { return a == kSpotInf ? kSpotInf : a + ((uint64_t)d << 32); }
-__device__ __forceinline__ uint64_t spot_shfl_up(uint64_t v, uint32_t by)
-{
-    const uint32_t lo = __shfl_up((uint32_t)v, by, 64), hi = __shfl_up((uint32_t)(v >> 32), by, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t spot_shfl(uint64_t v, uint32_t from)
-{
-    const uint32_t lo = __shfl((uint32_t)v, (int)from, 64), hi = __shfl((uint32_t)(v >> 32), (int)from, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 // the record of a window (or of a piece of one) from its key (q, e) and the winner's start and cost
 __device__ __forceinline__ sr_spot_hit spot_record(uint64_t key, uint32_t start, uint32_t acc)
 {

@@ -29,6 +29,8 @@ enum DevHook {
     kHookSpotChunk,       // "spot_chunk_cols": columns per chunk of the word spotter (1..16383; read per launch)
     kHookAlignPairs,      // "align_pairs": pairs per launch of the full-DP aligner (read per call and by sr_align_geometry)
     kHookAlignGlobal,     // "align_marks_global": the aligner keeps its predecessor marks in global scratch whatever fits the LDS
+    kHookChainChunk,      // "chain_chunk_cols": columns per chunk of the connected-word decoder (1..16383; read per call)
+    kHookChainRows,       // "chain_rows": rows per launch group of the connected-word decoder (read per call and by sr_decode_geometry)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -292,6 +294,37 @@ struct SpotArgs {
     sr_spot_hit *part;          // split only: [n_rows * n_chunks][K]
 };
 void launch_spot(const SpotArgs &a, hipStream_t s);
+
+// connected-word decoding (k_chain.hip): level building over the template store.  One launch group covers n_rows rows whose
+// scratch is A[row][level 1..max_words][max_frames + 1] (packed cost << 32 | start << 16 | slot, all ones = unreachable) and
+// E[row][level 0..max_words][max_frames + 1] (prefix costs, SR_DIS_ERR = unreachable); every pointer is the group's first row.
+struct ChainArgs {
+    const int16_t *mfcc;        // [n_rows][max_frames][12]
+    const uint32_t *in_frames;  // frame count of row r at in_frames[r * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t n_rows;            // <= 65 535
+    uint32_t max_frames;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;                 // <= 65 536: the slot is 16 bits of a key
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a boundary column
+    uint32_t chunk_cols;        // end frames per wave
+    uint32_t n_chunks;          // chunks per row
+    uint32_t max_words;         // levels
+    uint32_t n_words_exact;     // 0: the cheapest count
+    uint32_t skip_cost;         // SR_DIS_ERR: no skipping
+    uint32_t word_cost;
+    unsigned long long *A;
+    uint32_t *E;
+    const uint32_t *group_of_slot;  // the engine's word grouping (sr_nbest.cpp): slot -> group, group -> label
+    const uint32_t *word_id;
+    sr_chain_rec *rec;          // [n_rows]
+    sr_chain_word *words;       // [n_rows][max_words]
+    uint32_t *level_cost;       // optional [n_rows][max_words]
+};
+void launch_chain(const ChainArgs &a, hipStream_t s);  // init, max_words x (k_chain_words, k_chain_close), k_chain_trace
 
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the

@@ -88,6 +88,31 @@ inline SpotGeom spot_geom(uint32_t tpl_len, uint32_t max_frames, uint32_t win_fr
     return g;
 }
 
+// Connected-word decoder (k_chain.hip): k_spot's workgroup (spot_lds_bytes) and its chunks with one window per row
+// (spot_geom with win_frames 0).  Scratch of a row: max_words levels of u64 keys and max_words + 1 levels of u32 prefix costs,
+// max_frames + 1 entries each; rows go out in launch groups whose scratch stays within kChainScratch.
+constexpr size_t kChainScratch = (size_t)256 << 20;
+constexpr uint32_t kChainMaxWords = 16, kChainMaxSlots = 65536u, kChainMaxRows = 65535u;  // levels; 16-bit slot of a key; grid rows
+struct ChainPlan {
+    SpotGeom g;
+    size_t a_row, e_row;  // elements of A (u64) and E (u32) per row
+    size_t row_bytes;
+    uint32_t rows;        // per launch group
+};
+inline ChainPlan chain_plan(uint32_t tpl_len, uint32_t max_frames, uint32_t max_words, uint32_t cols, uint32_t forced_rows)
+{
+    ChainPlan p;
+    p.g = spot_geom(tpl_len, max_frames, 0u, cols);
+    if (!p.g.split) p.g.chunk_cols = max_frames, p.g.n_chunks = 1;  // the one window of a row fits one chunk
+    p.a_row = (size_t)max_words * (max_frames + 1u);
+    p.e_row = (size_t)(max_words + 1u) * (max_frames + 1u);
+    p.row_bytes = p.a_row * 8u + p.e_row * 4u;
+    const size_t fit = kChainScratch / p.row_bytes;
+    p.rows = (uint32_t)(fit < 1 ? 1 : fit > kChainMaxRows ? kChainMaxRows : fit);
+    if (forced_rows) p.rows = forced_rows < kChainMaxRows ? forced_rows : kChainMaxRows;
+    return p;
+}
+
 // Full-DP aligner (k_align.hip): one wave = one workgroup per pair.  LDS: the reference image (32-byte rows), the boundary
 // column (one word per row) and, when they fit, the predecessor marks: 2 bits per cell, 16 reference rows per word, mark_w
 // words per input column (odd, so that the lanes' words spread over the banks).  The marks stay in LDS while
@@ -127,6 +152,7 @@ const char *dtw_quad_allow_lds(uint32_t bytes);
 const char *dtw_dp_allow_lds(uint32_t bytes);
 const char *spot_allow_lds(uint32_t bytes);
 const char *align_allow_lds(uint32_t bytes);
+const char *chain_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

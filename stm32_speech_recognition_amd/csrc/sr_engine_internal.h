@@ -211,6 +211,9 @@ struct sr_engine {
     DevBuf<sr_align_rec> s_al_rec;
     DevBuf<int32_t> s_al_sum;
     DevBuf<int16_t> s_al_cen;
+    // connected-word decoding (sr_chain.cpp): the keys and prefix costs of one launch group
+    DevBuf<unsigned long long> s_ch_a;
+    DevBuf<uint32_t> s_ch_e;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant
@@ -267,3 +270,6 @@ int check_spot(const sr_engine *h, uint32_t n_rows, uint32_t win_frames, SpotGeo
 // the stage over n_rows rows, enqueued on s (d_scores may be nullptr); reserves the partial records it needs
 int launch_spot_stage(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride, uint32_t n_rows,
                       const SpotGeom &g, sr_spot_hit *d_hits, uint32_t *d_scores, hipStream_t s);
+// ---- connected-word decoding (sr_chain.cpp) -----------------------------------------------------------------------------------
+// the conditions of sr_decode_words_dp_dev on the engine, the store and the parameters (not on the buffers)
+int check_chain(const sr_engine *h, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost);

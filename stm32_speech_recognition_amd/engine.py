@@ -36,7 +36,13 @@ SPOT_DTYPE = np.dtype([("dis", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc",
 ALIGN_DTYPE = np.dtype([("dis", "<u4"), ("acc", "<u4"), ("path_len", "<u4"), ("status", "<u4")])
 TRAIN_STAT_DTYPE = np.dtype([("n_ok", "<u4"), ("n_fail", "<u4"), ("acc", "<u8")])
 AL_OK, AL_GATED, AL_TOO_LONG, ALIGN_MAX_FRAMES = 0, 1, 2, 1024
+# connected-word decoding (sr_chain_rec / sr_chain_word): a row's parse and its words in spoken order
+CHAIN_REC_DTYPE = np.dtype([("cost", "<u4"), ("n_words", "<u4"), ("skipped", "<u4"), ("status", "<u4")])
+CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4"), ("dis", "<u4"),
+                             ("cum", "<u4"), ("reserved", "<u4")])
+CH_OK, CH_NONE = 0, 1
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
+assert CHAIN_REC_DTYPE.itemsize == 16 and CHAIN_WORD_DTYPE.itemsize == 32
 assert ALIGN_DTYPE.itemsize == 16 and TRAIN_STAT_DTYPE.itemsize == 16
 assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16 and NBEST_DTYPE.itemsize == 16
 assert LIVE_SEG_DTYPE.itemsize == 24
@@ -581,6 +587,65 @@ class Engine:
                                          _vp(out["mfcc"]), _vp(out["frm_num"]), _vp(out["status"])))
         return out
 
+    # ---- connected-word decoding ----------------------------------------------------------------------------
+    @staticmethod
+    def _skip(skip_cost):
+        return DIS_ERR if skip_cost is None else int(skip_cost)
+
+    def decode_words(self, mfcc, frames, max_words=8, n_words=0, skip_cost=None, word_cost=0):
+        """OPT-IN connected-word decoder (sr_decode_words_dp): which sequence of words each feature row contains, by
+        level-building DTW over the template store.  mfcc int16 [n_rows, max_frames, 12], frames uint32 [n_rows]; n_words 0 =
+        the cheapest count of 1..max_words; skip_cost None = every frame belongs to a word.  Returns (rec CHAIN_REC_DTYPE
+        [n_rows], words CHAIN_WORD_DTYPE [n_rows, max_words] in spoken order, level_cost uint32 [n_rows, max_words])."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, max_words), dtype=CHAIN_WORD_DTYPE)
+        lc = np.zeros((n, max_words), dtype=np.uint32)
+        self._check(self.L.sr_decode_words_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), C.c_uint32(max_words),
+                                              C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(rec),
+                                              _vp(words), _vp(lc)))
+        return rec, words, lc
+
+    def decode_words_dev(self, mfcc, frames, rec, words, level_cost=None, max_words=8, n_words=0, skip_cost=None, word_cost=0,
+                         frames_stride=1, stream=None):
+        """sr_decode_words_dp_dev on device tensors: mfcc int16 [n_rows, max_frames, 12]; frames as for spot_dev; rec int32
+        [n_rows, 4]; words int32 [n_rows, max_words, 8]; level_cost (optional) int32 [n_rows, max_words].  Asynchronous on
+        `stream`; returns (rec, words, level_cost)."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and words.numel() == n * max_words * 8
+        assert level_cost is None or (level_cost.is_contiguous() and level_cost.numel() == n * max_words)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_decode_words_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                  C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)),
+                                                  C.c_uint32(word_cost), _vp(rec), _vp(words), _vp(level_cost), C.c_void_p(stream)))
+        return rec, words, level_cost
+
+    def decode_words_pcm(self, pcm, start, end, mid, max_words=8, n_words=0, skip_cost=None, word_cost=0):
+        """sr_decode_words_batch, the host whole path: mfcc_status() of segment [start[b], end[b]) of row b, then
+        decode_words() over those rows.  Returns dict(rec, words, level_cost, mfcc, frm_num, status); a failed record has
+        no parse."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        out = dict(rec=np.zeros(B, dtype=CHAIN_REC_DTYPE), words=np.zeros((B, max_words), dtype=CHAIN_WORD_DTYPE),
+                   level_cost=np.zeros((B, max_words), dtype=np.uint32),
+                   mfcc=np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16), frm_num=np.zeros(B, dtype=np.uint32),
+                   status=np.zeros(B, dtype=np.uint32))
+        self._check(self.L.sr_decode_words_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S), C.c_uint32(B), _vp(start), _vp(end),
+                                                 _vp(mid), C.c_uint32(max_words), C.c_uint32(n_words),
+                                                 C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(out["rec"]),
+                                                 _vp(out["words"]), _vp(out["level_cost"]), _vp(out["mfcc"]), _vp(out["frm_num"]),
+                                                 _vp(out["status"])))
+        return out
+
     # ---- full-DP alignment and word models from many examples -----------------------------------------
     def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
         """OPT-IN (sr_dtw_dp_align): the optimal warping path of the full-DP scorer for every (row, reference) pair.  mfcc int16
@@ -864,6 +929,17 @@ def spot_geometry(tpl_rows, max_frames, win_frames=0, testing=False):
     if rc != 0:
         raise SrError(f"sr_spot_geometry error {rc}: {L.sr_last_error().decode()}")
     return dict(n_win=out[0], lds_bytes=out[1], max_tpl_rows=out[2], chunk_cols=out[3])
+
+
+def decode_geometry(tpl_rows, max_frames, max_words=8, testing=False):
+    """Host-only sr_decode_geometry: dict(scratch_bytes per row for the levels' keys and prefix costs, rows per launch group,
+    max_tpl_rows that fit, chunk_cols = end frames per kernel chunk)."""
+    L = load_library(testing)
+    out = (C.c_uint32 * 4)()
+    rc = L.sr_decode_geometry(C.c_uint32(tpl_rows), C.c_uint32(max_frames), C.c_uint32(max_words), out)
+    if rc != 0:
+        raise SrError(f"sr_decode_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(scratch_bytes=out[0], rows=out[1], max_tpl_rows=out[2], chunk_cols=out[3])
 
 
 def align_geometry(max_frames, ref_rows, testing=False):
