@@ -514,6 +514,83 @@ int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32
  * tpl_rows rows, out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
 int sr_spot_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t win_frames, uint32_t out[4]);
 
+/* ------------------------------------------------------------------ live word spotting: spotter state carried between pushes
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The spotter above takes a complete feature row of at most max_frames frames.
+ * A session takes the frames of n_channels channels as they arrive, in pushes of any size up to chunk_max, keeps per
+ * (channel, slot) ONE column of the recurrence and the open window's first minimum on the device between calls, and emits
+ * every window's record when its last end frame has arrived: n * M cells per push of n frames, and no cap on a channel's
+ * length below 0xFFFF0000 frames.  No existing call, record or score changes.
+ * THE RULE: let Y_c be every feature frame pushed to channel c since it was opened or last ended, N = |Y_c|, W = win_frames
+ * (>= 1, fixed at open).  Window w of channel c holds the end frames [w*W, (w+1)*W).  A push emits the windows whose last end
+ * frame it consumed, by ascending channel, then ascending window; sr_spot_live_end emits the open window if it holds at
+ * least one frame (N mod W != 0).  For every slot the record of window w is the record the word spotting section defines for
+ * Y_c as ONE row of N frames with that win_frames -- byte for byte, whatever the chunking; start and end are 0-based frame
+ * indices of the channel's recording.  While N <= max_frames it is therefore what sr_spot_dp_batch[_dev] writes for that row.
+ * An invalid slot, and a window without a reachable end frame, get the no-hit record.  Every emitted record is written whole,
+ * exactly once.  A push that would take a channel past 0xFFFF0000 frames returns SR_ERR_BAD_ARG (absolute starts live in 32
+ * bits of the packed state).
+ * PCM sessions (mid given at open): the channel's samples X_c, R = |X_c|, are framed as sr_spot_batch frames a segment with
+ * start = 1, end = R and mid[c]: sample 0 serves only as pre-emphasis predecessor, frame j exists once
+ * R >= 1 + j*hop + frame_len; the records are those of the rule above on these frames, so while there are at most max_frames
+ * of them they equal sr_spot_batch(X_c, 1, R, mid[c], W).  The device keeps the samples from the next frame's predecessor on.
+ * Every call refused for its arguments, its counts or the store (SR_ERR_BAD_ARG, SR_ERR_BAD_CONFIG, SR_ERR_NO_TEMPLATES) is
+ * refused before anything is enqueued: it writes nothing and changes no state.  A HIP failure (SR_ERR_HIP: allocation, copy,
+ * launch) may come after part of a push has been enqueued; the session is then undefined and must be closed.  Pushes of one
+ * session may go to different streams: a push on another stream than the last push's is ordered behind it by an event, and
+ * the host forms and sr_spot_live_end run behind the last push likewise.  A session's state is shaped by the template store: a channel is
+ * bound to the store that was set when the session was opened or the channel last ended, and a push of frames to a channel
+ * whose store has since been replaced returns SR_ERR_BAD_ARG until that channel is ended (its open window is then dropped:
+ * the templates it was scored against are gone).  The session uses its engine's scratch buffers: the engine's
+ * one-caller-at-a-time rule covers its sessions. */
+typedef struct sr_spot_live sr_spot_live;
+typedef struct sr_spot_win { /* 8 bytes: which window an emitted row holds */
+    uint32_t channel;
+    uint32_t window;
+} sr_spot_win;
+/* host-only, no device: out[0] = most windows one channel can complete in one push of chunk_max frames, out[1] = device state
+ * bytes per channel for K slots whose longest template has tpl_rows rows (saturating), out[2] = the longest template that
+ * fits (sr_spot_geometry's out[2]) */
+int sr_spot_live_geometry(uint32_t tpl_rows, uint32_t K, uint32_t chunk_max, uint32_t win_frames, uint32_t out[3]);
+/* mid NULL: a feature session, chunk_max in frames, 1..max_frames.  mid a HOST array [n_channels]: a PCM session, chunk_max in
+ * samples; SR_ERR_BAD_ARG if a push of chunk_max samples could complete more than max_frames frames.  n_channels 1..65535,
+ * win_frames >= 1.  Configuration errors as sr_spot_dp_batch_dev (n_coef != 12, no templates, templates too long). */
+int sr_spot_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uint32_t win_frames, const uint32_t *mid,
+                      sr_spot_live **out);
+void sr_spot_live_close(sr_spot_live *l); /* before sr_destroy of its engine; waits for the session's last push */
+/* host-only: the EXACT number of window rows a push with these counts emits (n NULL: n_all each); 0 for counts a push refuses */
+uint32_t sr_spot_live_rows(const sr_spot_live *l, const uint32_t *n, uint32_t n_all);
+/* host-only, no session: the count sr_spot_live_rows is made of -- channel c stands at frames_before[c] frames and gets
+ * n_new[c] more: sum over c of (frames_before[c] + n_new[c]) / win_frames - frames_before[c] / win_frames; 0 for win_frames 0,
+ * a null array or a channel that would pass 0xFFFF0000 frames */
+uint32_t sr_spot_live_windows(uint32_t win_frames, const uint32_t *frames_before, const uint32_t *n_new, uint32_t n_channels);
+/* One push.  n: HOST array [n_channels] in both forms, 0 <= n[c] <= chunk_max, 0 leaves the channel untouched; NULL: n_all
+ * each.  Channel c's new frames are d_mfcc + c*row_stride (s16, 12 per frame; row_stride in s16 elements, at least 12 times
+ * the largest count); nothing past n[c] frames of a row is read.  DEVICE form: d_mfcc 8-byte aligned, row_stride a multiple
+ * of 4; ONE asynchronous operation on `stream`, no host synchronisation, no read-back.  d_hits[r*K + slot] and the optional
+ * d_scores[r*K + slot] (the dis fields: sr_nbest_batch_dev's input with *n_rows rows) are COMPACT over the emitted rows r;
+ * rows at and past *n_rows are not written.  wins[max_rows] and *n_rows are HOST outputs, filled from the counts alone before
+ * the call returns.  max_rows below sr_spot_live_rows() returns SR_ERR_BAD_ARG. */
+int sr_spot_live_push_dev(sr_spot_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                          uint32_t max_rows, sr_spot_hit *d_hits, uint32_t *d_scores, sr_spot_win *wins, uint32_t *n_rows,
+                          void *stream);
+/* the same on HOST buffers (2-byte aligned rows, any row_stride that holds the largest count) */
+int sr_spot_live_push(sr_spot_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                      uint32_t max_rows, sr_spot_hit *hits, uint32_t *scores, sr_spot_win *wins, uint32_t *n_rows);
+/* PCM sessions: channel c's new samples are d_pcm + c*pcm_stride, n in samples; alignment rules as sr_live_push_dev (device
+ * form: 16-byte aligned, pcm_stride a multiple of 8).  A copy kernel builds [kept | chunk] rows, the frame kernel launch of
+ * sr_mfcc_batch_dev turns them into the push's new frames, the spotter runs over those. */
+int sr_spot_live_push_pcm_dev(sr_spot_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                              uint32_t max_rows, sr_spot_hit *d_hits, uint32_t *d_scores, sr_spot_win *wins, uint32_t *n_rows,
+                              void *stream);
+int sr_spot_live_push_pcm(sr_spot_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                          uint32_t max_rows, sr_spot_hit *hits, uint32_t *scores, sr_spot_win *wins, uint32_t *n_rows);
+/* The listed channels' recordings end here: HOST outputs hits[n_ch][K] and wins[n_ch], of which *n_rows rows are written --
+ * the open window of each listed channel that has one, in the order listed.  A channel listed more than once counts once, at
+ * its first mention (it is fresh, with nothing open, by the second).  Waits for the device.  Each listed channel is then as
+ * freshly opened, and bound to the current store. */
+int sr_spot_live_end(sr_spot_live *l, const uint32_t *channels, uint32_t n_ch, sr_spot_hit *hits, sr_spot_win *wins,
+                     uint32_t *n_rows);
+
 /* ------------------------------------------------------------------ connected-word decoding: level-building DTW
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The spotter says where each template matches best, slot by slot; this section
  * says which SEQUENCE of words a feature row in[0..N) contains (N clamped to max_frames): digits or a command and its

@@ -295,6 +295,63 @@ struct SpotArgs {
 };
 void launch_spot(const SpotArgs &a, hipStream_t s);
 
+// live word spotting (k_spot_live.hip): k_spot's sweep resumed from push to push.  The state of a (channel, slot) pair is the
+// boundary column -- (Dd, min(Dd, Dn)) per template row, starts absolute -- and the window reduction's carry; a channel's
+// state is cols[K][tpl_len] followed by K carries, chan_stride bytes per channel.  The host knows every count: it says where
+// each channel stands and where its records go.
+struct SpotLiveChan {  // 32 bytes, one per channel and push
+    uint32_t x0;         // frames of the channel before this push = absolute index of its first new frame
+    uint32_t n;          // new frames (0: the channel is not touched)
+    uint32_t row_base;   // output row of the first window this push completes
+    uint32_t first_win;  // ... and that window's number, x0 / win
+    uint32_t kept;       // PCM sessions: samples kept from earlier pushes, new samples, and the samples at the front of
+    uint32_t n_samp;     // [kept | chunk] that no later frame needs (new frames * hop)
+    uint32_t drop;
+    uint32_t _pad;
+};
+// the carry: the first minimum so far of the window the channel's last frame lies in, two 16-byte words
+// {key = q << 32 | end (all ones = none; an invalid slot keeps it that way), start | cost << 32}, {window id, 0}
+// (read and written by spot_live_carry()'s users in k_spot_live.hip alone)
+constexpr uint32_t kSpotLiveCarryBytes = 32;
+struct SpotLiveArgs {
+    const int16_t *mfcc;        // channel c's new frames at mfcc + c * row_stride, 8-byte aligned rows
+    uint64_t row_stride;        // s16 elements
+    const SpotLiveChan *chan;   // [C]
+    uint32_t C;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a boundary column
+    uint32_t win;               // end frames per window, >= 1
+    uint8_t *state;             // [C][chan_stride]
+    uint64_t chan_stride;       // bytes, a multiple of 16
+    sr_spot_hit *hits;          // [rows][K], compact over the windows the push completes
+    uint32_t *scores;           // optional [rows][K]
+};
+void launch_spot_live(const SpotLiveArgs &a, hipStream_t s);
+struct SpotLiveFlush {  // one listed channel of sr_spot_live_end
+    uint32_t channel, row;  // row = 0xFFFFFFFF: no open window, the state is reset only
+    uint32_t wid, _pad;
+};
+void launch_spot_live_flush(const SpotLiveFlush *list, uint32_t n_list, uint8_t *state, uint64_t chan_stride, uint32_t K,
+                            uint32_t tpl_len, sr_spot_hit *hits, hipStream_t s);
+// PCM sessions: rows [kept | chunk] for the frame kernel, then what the next push's first frame needs back into `keep`
+struct SpotLivePcmArgs {
+    const SpotLiveChan *chan;
+    uint32_t C;
+    const uint16_t *pcm;        // [C][pcm_stride] the chunks
+    uint64_t pcm_stride;
+    uint16_t *keep;             // [C][keep_stride]
+    uint32_t keep_stride;
+    uint16_t *stage;            // [C][stage_stride], 16-byte aligned rows
+    uint64_t stage_stride;
+    uint32_t max_row;           // the longest [kept | chunk] row of this push
+};
+void launch_spot_live_stage(const SpotLivePcmArgs &a, hipStream_t s);
+void launch_spot_live_keep(const SpotLivePcmArgs &a, hipStream_t s);
+
 // connected-word decoding (k_chain.hip): level building over the template store.  One launch group covers n_rows rows whose
 // scratch is A[row][level 1..max_words][max_frames + 1] (packed cost << 32 | start << 16 | slot, all ones = unreachable) and
 // E[row][level 0..max_words][max_frames + 1] (prefix costs, SR_DIS_ERR = unreachable); every pointer is the group's first row.

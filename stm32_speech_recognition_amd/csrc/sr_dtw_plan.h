@@ -151,6 +151,7 @@ const char *dtw_cells_allow_lds(uint32_t bytes);
 const char *dtw_quad_allow_lds(uint32_t bytes);
 const char *dtw_dp_allow_lds(uint32_t bytes);
 const char *spot_allow_lds(uint32_t bytes);
+const char *spot_live_allow_lds(uint32_t bytes);
 const char *align_allow_lds(uint32_t bytes);
 const char *chain_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)

@@ -264,7 +264,8 @@ int sr_create(const sr_config *cfg, sr_engine **out)
         (void)hipGetLastError();
     }
     // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
-    for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, align_allow_lds, chain_allow_lds}) {
+    for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, spot_live_allow_lds, align_allow_lds,
+                       chain_allow_lds}) {
         if (const char *kernel = allow(h->lds.per_wg)) {
             delete h;
             return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));
@@ -549,6 +550,7 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
     h->K = K;
     h->tpl_rows = rows;
     h->tpl_stride = rows * nc;
+    h->store_serial++;
     plan_dtw(h, f.data(), v.data());
     // Chunk count of the device-resident pipeline by store size (round-4 sweeps, profiles/experiments/RESULTS.md): with
     // 100 templates 3 streams x 6..15 chunks are equivalent (22.3 ms per 65 536 utterances); with 500 templates the DTW

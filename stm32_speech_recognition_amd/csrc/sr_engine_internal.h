@@ -119,6 +119,7 @@ struct sr_engine {
     DevBuf<uint32_t> tpl_frames_s, tpl_orig;
     DevBuf<uint32_t> tpl_rank;     // [K] rank of each slot in that order (the inverse of tpl_orig): the sparse full-DP scorer's marks
     uint32_t K = 0, tpl_rows = 0, tpl_stride = 0;
+    uint64_t store_serial = 0;     // bumped by every template upload: what a live spotting session's state was shaped by (sr_spot_live.cpp)
     DtwPlan plan;                  // which DTW kernel serves this store, in what shape (plan_dtw, when the store is set)
     uint32_t dp_lanes = 0;         // sr_set_dp_lanes: lanes per pair of the opt-in full-DP scorer (0 = default)
     std::vector<uint32_t> cells_by_len;  // most band points per template length, computed once (dtw_cells_max_points)

@@ -32,6 +32,8 @@ NO_WORD, NBEST_MAX = 0xFFFFFFFF, 16
 LIVE_SEG_DTYPE = np.dtype([("channel", "<u4"), ("frm_num", "<u4"), ("start", "<i8"), ("end", "<i8")])
 # word spotting (sr_spot_hit): q(e), the start and end frame of the best match inside a window, its accumulated cost
 SPOT_DTYPE = np.dtype([("dis", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4")])
+# sr_spot_win: which (channel, window) an emitted row of a live spotting session holds
+SPOT_WIN_DTYPE = np.dtype([("channel", "<u4"), ("window", "<u4")])
 # full-DP alignment (sr_align_rec) and DBA training statistics (sr_train_stat)
 ALIGN_DTYPE = np.dtype([("dis", "<u4"), ("acc", "<u4"), ("path_len", "<u4"), ("status", "<u4")])
 TRAIN_STAT_DTYPE = np.dtype([("n_ok", "<u4"), ("n_fail", "<u4"), ("acc", "<u8")])
@@ -905,6 +907,12 @@ class Engine:
         None (noise_atap over each channel's head) or an ATAP_DTYPE array [n_channels].  Close it before the engine."""
         return LiveSession(self, n_channels, chunk_max, atap)
 
+    def spot_live(self, n_channels, chunk_max, win_frames, mid=None):
+        """sr_spot_live_open: a SpotSession of n_channels channels with windows of win_frames end frames.  mid None: a feature
+        session taking pushes of at most chunk_max frames per channel; mid uint32 [n_channels]: a PCM session, chunk_max in
+        samples.  Close it before the engine."""
+        return SpotSession(self, n_channels, chunk_max, win_frames, mid)
+
     def set_pipeline(self, streams=3, min_chunk=4096, max_chunks=12):
         """chunking of recognize_dev over the engine's internal streams (streams=1: one chunk, caller's stream)"""
         self._check(self.L.sr_set_pipeline(self.h, C.c_uint32(streams), C.c_uint32(min_chunk), C.c_uint32(max_chunks)))
@@ -1085,6 +1093,149 @@ class LiveSession:
         n = C.c_uint32(0)
         self.eng._check(self.L.sr_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(segs), C.byref(n)))
         return segs[:n.value]
+
+
+def spot_live_geometry(tpl_rows, K, chunk_max, win_frames):
+    """Host-only sr_spot_live_geometry: dict(max_windows one channel can complete in one push of chunk_max frames, state_bytes
+    on the device per channel, max_tpl_rows that fit)"""
+    L = load_library()
+    out = (C.c_uint32 * 3)()
+    rc = L.sr_spot_live_geometry(C.c_uint32(tpl_rows), C.c_uint32(K), C.c_uint32(chunk_max), C.c_uint32(win_frames), out)
+    if rc != 0:
+        raise SrError(f"sr_spot_live_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(max_windows=out[0], state_bytes=out[1], max_tpl_rows=out[2])
+
+
+def spot_live_windows(win_frames, frames_before, n_new):
+    """Host-only sr_spot_live_windows: the window rows a push emits when channel c stands at frames_before[c] frames and gets
+    n_new[c] more (what SpotSession.rows computes from the session's own counts)"""
+    L = load_library()
+    L.sr_spot_live_windows.restype = C.c_uint32
+    fb, nn = np.ascontiguousarray(frames_before, dtype=np.uint32), np.ascontiguousarray(n_new, dtype=np.uint32)
+    assert fb.shape == nn.shape and fb.ndim == 1
+    return int(L.sr_spot_live_windows(C.c_uint32(win_frames), _vp(fb), _vp(nn), C.c_uint32(len(fb))))
+
+
+class SpotSession:
+    """One sr_spot_live handle (Engine.spot_live): word spotting over chunked features or samples on n_channels channels, the
+    spotter's state carried between pushes.  The records of a channel's windows, over any chunking, are those of Engine.spot
+    on everything pushed to it as one row (include/sr_engine.h, "live word spotting")."""
+
+    def __init__(self, eng, n_channels, chunk_max, win_frames, mid=None):
+        self.eng, self.L, self.n_channels, self.chunk_max, self.win_frames = eng, eng.L, n_channels, chunk_max, win_frames
+        self.L.sr_spot_live_rows.restype = C.c_uint32
+        self.L.sr_spot_live_close.restype = None
+        self.L.sr_spot_live_close.argtypes = [C.c_void_p]
+        md = None if mid is None else np.ascontiguousarray(mid, dtype=np.uint32)
+        assert md is None or md.shape == (n_channels,)
+        self.pcm = md is not None
+        l = C.c_void_p()
+        eng._check(self.L.sr_spot_live_open(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(win_frames), _vp(md),
+                                            C.byref(l)))
+        self.l = l
+
+    def close(self):
+        if getattr(self, "l", None):
+            self.L.sr_spot_live_close(self.l)
+            self.l = None
+
+    def __del__(self):
+        try:
+            if getattr(self.eng, "h", None):  # a session never outlives its engine's handle
+                self.close()
+        except Exception:
+            pass
+
+    def _counts(self, counts, width):
+        """(host uint32 array or None, n_all)"""
+        if counts is None:
+            return None, width
+        ct = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert ct.shape == (self.n_channels,)
+        return ct, 0
+
+    def rows(self, counts):
+        """sr_spot_live_rows: the exact number of window rows a push with these counts (an int: that many on every channel)
+        emits"""
+        if np.isscalar(counts):
+            return int(self.L.sr_spot_live_rows(self.l, None, C.c_uint32(int(counts))))
+        ct, _ = self._counts(counts, 0)
+        return int(self.L.sr_spot_live_rows(self.l, _vp(ct), C.c_uint32(0)))
+
+    def _push_host(self, fn, data, stride, width, counts, max_rows):
+        ct, n_all = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = self.rows(width if ct is None else ct)
+        K = self.eng.n_templates
+        hits, sc = np.zeros((max_rows, K), dtype=SPOT_DTYPE), np.zeros((max_rows, K), dtype=np.uint32)
+        wins, n = np.zeros(max_rows, dtype=SPOT_WIN_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(hits), _vp(sc),
+                           _vp(wins), C.byref(n)))
+        return dict(hits=hits[:n.value], scores=sc[:n.value], wins=wins[:n.value], n_rows=n.value)
+
+    def _push_dev(self, fn, data, stride, width, counts, max_rows, scores, stream):
+        import torch
+        ct, n_all = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = self.rows(width if ct is None else ct)
+        K, dev = self.eng.n_templates, data.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        rows = max(max_rows, 1)
+        hits = torch.empty(rows, K, 4, dtype=torch.int32, device=dev)[:max_rows]
+        sc = torch.empty(rows, K, dtype=torch.int32, device=dev)[:max_rows] if scores else None
+        wins, n = np.zeros(max_rows, dtype=SPOT_WIN_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(hits), _vp(sc),
+                           _vp(wins), C.byref(n), C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            for t in (data, hits, sc):
+                if t is not None:
+                    t.record_stream(stream)  # allocated on the current stream, used on `stream`
+        return dict(hits=hits[:n.value], scores=None if sc is None else sc[:n.value], wins=wins[:n.value], n_rows=n.value)
+
+    def push(self, frames, counts=None, max_rows=None):
+        """sr_spot_live_push: frames int16 [n_channels, F, 12], counts [n_channels] (None: F each).  Returns dict(hits SPOT_DTYPE
+        [n_rows, K], scores uint32 [n_rows, K], wins SPOT_WIN_DTYPE [n_rows], n_rows) of numpy arrays."""
+        mf = np.ascontiguousarray(frames, dtype=np.int16)
+        assert mf.ndim == 3 and mf.shape[0] == self.n_channels and mf.shape[2] == N_COEF
+        F = mf.shape[1]
+        return self._push_host(self.L.sr_spot_live_push, mf, max(F, 1) * N_COEF, F, counts, max_rows)
+
+    def push_dev(self, frames, counts=None, max_rows=None, scores=True, stream=None):
+        """sr_spot_live_push_dev on a device tensor: frames int16 [n_channels, F, 12], counts a HOST array [n_channels] (None: F
+        each).  Asynchronous on `stream` (a torch.cuda.Stream, or the current one).  Returns dict(hits int32 [n_rows, K, 4],
+        scores int32 [n_rows, K] or None -- device tensors, compact over the emitted rows -- wins, n_rows on the host)."""
+        import torch
+        assert frames.is_cuda and frames.dtype == torch.int16 and frames.is_contiguous()
+        assert frames.ndim == 3 and frames.shape[0] == self.n_channels and frames.shape[2] == N_COEF
+        F = frames.shape[1]
+        return self._push_dev(self.L.sr_spot_live_push_dev, frames, max(F, 1) * N_COEF, F, counts, max_rows, scores, stream)
+
+    def push_pcm(self, chunks, counts=None, max_rows=None):
+        """sr_spot_live_push_pcm: chunks uint16 [n_channels, S], counts [n_channels] in samples (None: S each); returns as push"""
+        pcm = np.ascontiguousarray(chunks, dtype=np.uint16)
+        assert pcm.ndim == 2 and pcm.shape[0] == self.n_channels
+        S = pcm.shape[1]
+        return self._push_host(self.L.sr_spot_live_push_pcm, pcm, max(S, 1), S, counts, max_rows)
+
+    def push_pcm_dev(self, chunks, counts=None, max_rows=None, scores=True, stream=None):
+        """sr_spot_live_push_pcm_dev: chunks int16 [n_channels, S] on the device (u16 codes, S a multiple of 8); returns as
+        push_dev"""
+        import torch
+        assert chunks.is_cuda and chunks.dtype in (torch.int16, torch.uint16) and chunks.is_contiguous()
+        assert chunks.ndim == 2 and chunks.shape[0] == self.n_channels
+        S = chunks.shape[1]
+        return self._push_dev(self.L.sr_spot_live_push_pcm_dev, chunks, S, S, counts, max_rows, scores, stream)
+
+    def end(self, channels):
+        """sr_spot_live_end: the listed channels' recordings end here.  Returns dict(hits SPOT_DTYPE [n_rows, K], wins, n_rows):
+        the open window of each listed channel that has one; afterwards the channels are as freshly opened."""
+        ch = np.ascontiguousarray(np.atleast_1d(channels), dtype=np.uint32)
+        K = self.eng.n_templates
+        hits = np.zeros((max(len(ch), 1), K), dtype=SPOT_DTYPE)
+        wins, n = np.zeros(max(len(ch), 1), dtype=SPOT_WIN_DTYPE), C.c_uint32(0)
+        self.eng._check(self.L.sr_spot_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(hits), _vp(wins), C.byref(n)))
+        return dict(hits=hits[:n.value], wins=wins[:n.value], n_rows=n.value)
 
 
 def live_segs_from_torch(t):
