@@ -111,6 +111,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     // ---- lane-invariant constants --------------------------------------------------------------
     LaneTw tw;
     load_lane_tw(a.t, lane, tw);
+    real_leg_tw(tw);  // pass 2 multiplies duplicated real legs (sr_fft_dev.h window_store)
     if (w == 0 && lane < 4) {
         const uint32_t *f = &tw.s3[0][0][0];
 #pragma unroll
@@ -231,9 +232,9 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const int i = lane + 64 * k;
-                // stored as the pass-1 output A >> 2 of the s16 sample (the gather reads the low 16 bits, zero-extended); samples
-                // 0..63 (k = 0) are only ever A legs of pass 2 and are stored as that pass consumes them, >> 2 once more
-                if (i < kFrameLen) xw[i] = k == 0 ? window_sample<4>(s_pp[k], mid, hamm_m[k]) : window_sample<2>(s_pp[k], mid, hamm_m[k]);
+                // stored as pass 2 consumes them (sr_fft_dev.h window_store): samples 0..63 (k = 0) are only ever its A legs, the others
+                // its real B and C legs
+                if (i < kFrameLen) k == 0 ? window_store<0>(xw, i, s_pp[k], mid, hamm_m[k]) : window_store<1>(xw, i, s_pp[k], mid, hamm_m[k]);
             }
             if (fi + 1 < nf) {
                 const uint16_t *x = row + seg0 + (int)kHop * (int)(f0 + fi + 1);
@@ -249,9 +250,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             fft_front_real160(xw, lane, tw, s_tw3, v);
             fft_exchange(buf, lane, v, u);
 #pragma unroll
-            for (int e4 = 0; e4 < 4; e4++)
-                bfly_pk<false>(u[0][e4], u[1][e4], u[2][e4], u[3][e4], tw.s4[0][0], tw.s4[0][1], tw.s4[1][0], tw.s4[1][1],
-                               tw.s4[2][0], tw.s4[2][1], tw.s4[3][0], tw.s4[3][1]);
+            for (int e4 = 0; e4 < 4; e4++) fft_pass4_dbl(u, e4, tw);
             // pass 5: only x[j] and x[j+q] (bins < 512) are consumed (MFCC.C:49)
             wave_sync();
             uint32_t k5[4][4][2];
@@ -259,8 +258,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             uint32_t nn[8];  // re^2 + im^2 of the lane's eight bins (one v_dot2_i32_i16 each, from the stored 16-bit halves)
 #pragma unroll
             for (int e3 = 0; e3 < 4; e3++) {
-                bfly_pk<true>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
-                              k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
+                bfly_pk_dbl<true, false, 0>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
+                                            k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
                 if constexpr (kFeat == SR_FEAT_FFT) {  // x[j], x[j + 256] as the asm stores them: bins lane + 64 e3 (+ 256)
                     uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
                     fr[0] = u[e3][0];
@@ -448,7 +447,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
                     const int i = lane + 64 * k;
-                    if (i < kFrameLen) xw[i] = k == 0 ? window_sample<4>(s_pp[k], mid, hamm_m[k]) : window_sample<2>(s_pp[k], mid, hamm_m[k]);
+                    if (i < kFrameLen) k == 0 ? window_store<0>(xw, i, s_pp[k], mid, hamm_m[k]) : window_store<1>(xw, i, s_pp[k], mid, hamm_m[k]);
                 }
             };
             auto request = [&](uint32_t f) {
@@ -464,17 +463,15 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 uint32_t u[4][4];
                 fft_exchange(buf, lane, v, u);
 #pragma unroll
-                for (int e4 = 0; e4 < 4; e4++)
-                    bfly_pk<false>(u[0][e4], u[1][e4], u[2][e4], u[3][e4], tw.s4[0][0], tw.s4[0][1], tw.s4[1][0], tw.s4[1][1],
-                                   tw.s4[2][0], tw.s4[2][1], tw.s4[3][0], tw.s4[3][1]);
+                for (int e4 = 0; e4 < 4; e4++) fft_pass4_dbl(u, e4, tw);
                 wave_sync();
                 uint32_t k5[4][4][2];
                 load_tw32(s_tw5, lane, k5);
                 uint32_t nn[8];
 #pragma unroll
                 for (int e3 = 0; e3 < 4; e3++) {
-                    bfly_pk<true>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
-                                  k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
+                    bfly_pk_dbl<true, false, 0>(u[e3][0], u[e3][1], u[e3][2], u[e3][3], k5[e3][0][0], k5[e3][0][1], k5[e3][1][0],
+                                                k5[e3][1][1], k5[e3][2][0], k5[e3][2][1], k5[e3][3][0], k5[e3][3][1]);
                     if constexpr (kFeat == SR_FEAT_FFT) {
                         uint32_t *fr = frow + (f0 + fi) * kFeatW + lane + 64 * e3;
                         fr[0] = u[e3][0];

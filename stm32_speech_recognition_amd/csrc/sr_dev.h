@@ -177,6 +177,33 @@ __device__ __forceinline__ uint32_t pk_mad_swap(uint32_t a, uint32_t c, uint32_t
     asm("v_pk_mad_u16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(a), "s"(c), "v"(b));
     return r;
 }
+// a*c' + b per half where c' = (c.L1, c.H1) picks either half of c for either result half, and SWAP exchanges the halves of a as
+// in pk_mad_swap.  With c = (+m, -m) in ONE register the four multipliers of a butterfly's add chain -- (m, m), (-m, -m),
+// (m, -m), (-m, m) -- are operand selects of the same word.  VC: c lives in a VGPR (lane-dependent m), else in an SGPR.
+template <bool VC, int L1, int H1, bool SWAP = false>
+__device__ __forceinline__ uint32_t pk_mad_sel(uint32_t a, uint32_t c, uint32_t b)
+{
+    uint32_t r;
+    if constexpr (VC)
+        asm("v_pk_mad_u16 %0, %1, %2, %3 op_sel:[%4,%5,0] op_sel_hi:[%6,%7,1]" : "=v"(r) : "v"(a), "v"(c), "v"(b), "n"(SWAP ? 1 : 0), "n"(L1), "n"(SWAP ? 0 : 1), "n"(H1));
+    else
+        asm("v_pk_mad_u16 %0, %1, %2, %3 op_sel:[%4,%5,0] op_sel_hi:[%6,%7,1]" : "=v"(r) : "v"(a), "s"(c), "v"(b), "n"(SWAP ? 1 : 0), "n"(L1), "n"(SWAP ? 0 : 1), "n"(H1));
+    return r;
+}
+// a * (c.lo, c.lo) per half (v_pk_mul_lo_u16), c in a VGPR
+__device__ __forceinline__ uint32_t pk_mul_lo_lo(uint32_t a, uint32_t c)
+{
+    uint32_t r;
+    asm("v_pk_mul_lo_u16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(c));
+    return r;
+}
+// (a.lo * c.lo, a.lo * c.hi): the low half of a times both halves of the constant c, e.g. (a, 2 a) for c = (1, 2)
+__device__ __forceinline__ uint32_t pk_mul_lo_dup(uint32_t a, uint32_t c)
+{
+    uint32_t r;
+    asm("v_pk_mul_lo_u16 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(r) : "v"(a), "s"(c));
+    return r;
+}
 // (hi16(lo_src) , hi16(hi_src)) -> packed word: the ">>16" of a complex 32-bit pair in ONE v_perm_b32
 __device__ __forceinline__ uint32_t pk_hi16(int lo_src, int hi_src)
 {

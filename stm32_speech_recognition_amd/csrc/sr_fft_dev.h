@@ -2,6 +2,8 @@
 // gfx950 (MI355X, CDNA4) only; wave = 64 lanes; no MFMA (the path has no dense contraction), integer VALU + LDS.
 // Every kernel reproduces the reference's integer arithmetic bit for bit; cited lines are relative to the reference tree.
 #pragma once
+#include <type_traits>
+
 #include "sr_dev.h"
 
 namespace sr {
@@ -96,6 +98,108 @@ __device__ __forceinline__ void bfly_pk(uint32_t &x0, uint32_t &x1, uint32_t &x2
     r4_packed<HALF, true>(x0, br, bi, sr, si, tr, ti, x0, x1, x2, x3);
 }
 
+// ---- DOUBLED LEGS (round 9): the combine for legs that enter their multiply as 2 Y --------------------------------------
+// v_dot2_i32_i16(2 Y, K) is 2 X mod 2^32 whenever 2 Y is an i16, so for a product pair computed from a doubled leg
+//   p(X) = bits 15..30 of X = bits 16..31 of 2 X          : ONE v_perm_b32, the selector h() uses on plain products
+//   h(X) = bits 16..31 of X = p(X) >> 1 (arithmetic, per half) : one v_pk_ashrrev_i16, IF bit 31 of X equals bit 30, i.e. |X| < 2^30
+// -- two VALU per pair instead of three, no SDWA and none of its wait states.  A butterfly whose outputs are non-A legs of
+// the next pass emits them doubled (or times a lane's m in {1, 2}) so that doubling costs nothing there: the add chain above
+// becomes v_pk_mad_u16 with the multipliers (m, m), (-m, -m), (m, -m), (-m, m) -- operand selects of ONE word (+m, -m),
+// pk_mad_sel -- started from m * (A >> 2), the only extra instruction (it is not A >> 1: the low bit of A >> 2 is kept).
+// Sums are mod 2^16 in any order, as before; the doubled output is 2 x for the value x the asm stores iff |x| < 2^14.
+//
+// WHERE IT MAY BE USED.  Both conditions -- every doubled leg |Y| < 2^14, every product pair |B|, |C + D|, |C - D| < 2^30 --
+// are properties of the input range, so only the zero-padded real frame of k_mfcc takes this form (fft_front_real160 and
+// the passes 4-5 behind it); transforms of arbitrary 16-bit complex input (k_mfcc_ext, k_mfcc_gen, fft_full_wave) keep the
+// plain one.  The bound, with the constants of the table gen_twiddles writes (sr_tables.cpp; recomputed from the table
+// itself by tests/test_fft_leg_bounds.py): every entry has |Kc|, |Ks| <= 16384 (+16384 occurs: Kc at b = 0, Ks at m = 2,
+// b = q/2 -- which is why the LEG is doubled and never the coefficient: 32768 is no i16) and |Kc| + |Ks| <= 23171
+// (16384 sqrt 2, rounded entries).  With M the largest |component| entering a pass:
+//   a component of Y conj(K) is |Yr Kc + Yi Ks| <= 23171 M, of C +- D <= 46342 M;
+//   an output is (A >> 2) +- h(B) +- h or (p - h) of C' or D'~, each term rounded by at most 1:
+//   |x| <= M/4 + (23171 + 46342) M / 65536 + 3 < 1.3107 M + 3.
+//   pass 1 (folded into the window): x >> 2 of an s16                     -> M2 <= 8192, legs REAL (they enter pass 2 DUPLICATED,
+//                                                                            not doubled -- window_store below -- with the same 2 X)
+//   pass 2: real legs, D = 0: |h(B)|, |h(C)| <= 8192 * 16384 / 65536 = 2048, A leg stored >> 4: 2048 + 2 * 2048 + 3
+//                                                                         -> M3 <= 6147
+//   pass 3: 1.3107 * 6147 + 3                                             -> M4 <= 8060
+//   pass 4: 1.3107 * 8060 + 3                                             -> M5 <= 10568
+// All below 2^14 = 16384; the largest product pair is |C +- D| of pass 5, 46342 * 10568 < 4.9e8 < 2^30 = 1.07e9 (pass 5
+// doubles its B leg only: 23171 * 10568 < 2.5e8).  This holds for EVERY 16-bit capture: the window's s16 wrap bounds M2.
+constexpr uint32_t kPkTwo = 0xFFFE0002u;  // (+2, -2)
+
+// OUT = 0: outputs as the asm stores them; 1: doubled; 2: times the lane's m, `mul` = (+m, -m) in a VGPR.
+// a = OUT-scaled A >> 2.  B (when HAS_B) comes from a doubled leg; C', D' too iff DBL_CD.
+template <bool HALF, bool HAS_B, bool CD_SAME, bool DBL_CD, int OUT>
+__device__ __forceinline__ void r4_packed_dbl(uint32_t a, uint32_t mul, int br, int bi, int sr, int si, int tr, int ti,
+                                              uint32_t &x0, uint32_t &x1, uint32_t &x2, uint32_t &x3)
+{
+    // acc + x * (s_lo m, s_hi m), the halves of x exchanged if SWAP: L / H = 1 picks -m for that half
+    auto madd = [&](uint32_t x, auto L, auto H, auto SWAP, uint32_t acc) -> uint32_t {
+        constexpr int l = decltype(L)::value, h = decltype(H)::value;
+        constexpr bool swap = decltype(SWAP)::value;
+        if constexpr (OUT == 2) return pk_mad_sel<true, l, h, swap>(x, mul, acc);
+        else if constexpr (OUT == 1) return pk_mad_sel<false, l, h, swap>(x, kPkTwo, acc);
+        else if constexpr (swap) return pk_mad_swap(x, l ? kPkMinusPlus : kPkPlusMinus, acc);
+        else if constexpr (l != h) return pk_mad(x, l ? kPkMinusPlus : kPkPlusMinus, acc);
+        else if constexpr (l) return pk_sub(acc, x);
+        else return pk_add(acc, x);
+    };
+    constexpr std::integral_constant<int, 0> P{};
+    constexpr std::integral_constant<int, 1> N{};
+    constexpr std::false_type kStraight{};
+    constexpr std::integral_constant<bool, CD_SAME> kSwapC{};
+    uint32_t A1 = a, B1 = a;
+    if (HAS_B) {
+        const uint32_t pB = pk_hi16(br, bi), hB = pk_ashr(pB, 1);
+        A1 = madd(hB, P, P, kStraight, a);
+        B1 = madd(pB, N, N, kStraight, A1);
+    }
+    uint32_t pC = 0, hC;
+    if (DBL_CD) {
+        pC = pk_hi16(sr, si);
+        hC = pk_ashr(pC, 1);
+    } else {
+        hC = pk_hi16(sr, si);
+        if (!HALF) pC = pk_s15(sr, si);
+    }
+    x0 = madd(hC, P, P, kStraight, A1);
+    // D' with its halves swapped; CD_SAME: C''s own halves, exchanged by the operand selects (see r4_packed)
+    uint32_t pD = 0, hD;
+    if (CD_SAME) {
+        pD = pC;
+        hD = hC;
+    } else if (DBL_CD) {
+        pD = pk_hi16(ti, tr);
+        hD = pk_ashr(pD, 1);
+    } else {
+        hD = pk_hi16(ti, tr);
+        if (!HALF) pD = pk_s15(ti, tr);
+    }
+    x1 = madd(hD, P, N, kSwapC, B1);
+    if (!HALF) {
+        x2 = madd(pC, N, N, kStraight, x0);
+        x3 = madd(pD, N, P, kSwapC, x1);
+    }
+}
+
+// bfly_pk for a butterfly whose B leg x1 is doubled, and whose C and D legs x2, x3 are iff DBL_CD; outputs by OUT as above
+template <bool HALF, bool DBL_CD, int OUT>
+__device__ __forceinline__ void bfly_pk_dbl(uint32_t &x0, uint32_t &x1, uint32_t &x2, uint32_t &x3, uint32_t k1a,
+                                            uint32_t k1b, uint32_t k2a, uint32_t k2b, uint32_t k3a, uint32_t k3b,
+                                            uint32_t k3na, uint32_t k3nb, uint32_t mul = 0)
+{
+    int br, bi, cr, ci;
+    cxmul(x2, k2a, k2b, cr, ci);
+    cxmul(x1, k1a, k1b, br, bi);
+    const int sr = sdot2a(x3, k3a, cr), si = sdot2a(x3, k3b, ci);
+    const int tr = sdot2a(x3, k3na, cr), ti = sdot2a(x3, k3nb, ci);
+    uint32_t a = pk_ashr(x0, 2);
+    if (OUT == 1) a = pk_add(a, a);
+    if (OUT == 2) a = pk_mul_lo_lo(a, mul);
+    r4_packed_dbl<HALF, true, false, DBL_CD, OUT>(a, mul, br, bi, sr, si, tr, ti, x0, x1, x2, x3);
+}
+
 __device__ __forceinline__ uint32_t pk_neg(uint32_t w) { return pk_sub(0u, w); }
 
 __device__ __forceinline__ void bfly(uint32_t &x0, uint32_t &x1, uint32_t &x2, uint32_t &x3, uint32_t k1a, uint32_t k1b,
@@ -114,7 +218,7 @@ constexpr int kXchgWords = 1024 + 4 * 16;  // 1088
 
 // Coefficients a lane needs, all lane-invariant across frames -> loaded once per wave into VGPRs.
 struct LaneTw {
-    uint32_t s2[2][2];     // pass 2 (q=4):   legs j+q, j+2q (j+3q is always zero-padding)
+    uint32_t s2[2][2];     // pass 2 (q=4):   legs j+q, j+2q (j+3q is always zero-padding); k_mfcc: low halves duplicated, real_leg_tw
     uint32_t s3[4][4][2];  // pass 3 (q=16):  per d1, legs j+q, j+2q, j+3q, and the j+3q pair negated
     uint32_t s4[4][2];     // pass 4 (q=64)
     uint32_t s5[4][4][2];  // pass 5 (q=256): per d3
@@ -207,9 +311,33 @@ __device__ __forceinline__ void load_tw32_d0(const u32x4 *lds, int d0, uint32_t 
 // non-zero and every imaginary part is 0.  Pass 1 (.s:226-232) then degenerates exactly to
 // out[4*idx+k] = x[bitrev8(idx)] >> 2 (k = 0..3), so it is folded into the gather.
 // lane = d0 + 4*d3 + 16*d4 ; v[d1][d2] <-> j = d0 + 4*d1 + 16*d2 + 64*d3 + 256*d4.
-// xw: the windowed frame as one 32-bit word per sample (16-bit pattern in the low half, the high half is never read): 4-byte
-// stores of consecutive samples and the 2-byte reads below at word base + 16 m are both conflict-free; with two samples per
-// word the stores of lanes 2 m / 2 m + 1 went to one word
+// xw: the windowed frame as one 32-bit word per sample, written by window_store below: 4-byte stores of consecutive samples and
+// the reads below at word base + 16 m are both conflict-free; with two samples per word the stores of lanes 2 m / 2 m + 1 went
+// to one word.  Samples 0..63, the A legs of pass 2, are stored >> 2 once more (round 6), as the word (a, 2 a): butterfly
+// d2 = 0 reads the low half, the doubled butterflies d2 > 0 their 2 a from the high half.  Samples 64..159, its B and C legs,
+// are stored as (Y, Y): the real leg enters its multiply DUPLICATED instead of doubled -- with the coefficient word's low half
+// in both halves too (real_leg_tw), v_dot2_i32_i16((Y, Y), (K, K)) = 2 Y K, the doubled product at no instruction at all.
+constexpr uint32_t kPkOneTwo = 0x00020001u;  // (1, 2)
+template <int K>  // K = 0: sample i < 64
+__device__ __forceinline__ void window_store(uint32_t *xw, int i, uint32_t prev_cur, int mid, int hm)
+{
+    if (K == 0) {
+        xw[i] = pk_mul_lo_dup(window_sample<4>(prev_cur, mid, hm), kPkOneTwo);
+    } else {
+        // the pass-1 output A >> 2 as a 16-bit pattern into both halves: a second 2-byte LDS store, which takes no VALU slot
+        const uint32_t y = window_sample<2>(prev_cur, mid, hm);
+        xw[i] = y;
+        ((uint16_t *)(xw + i))[1] = (uint16_t)y;
+    }
+}
+// pass-2 coefficient words for duplicated real legs: (Kc, Ks) -> (Kc, Kc) and (-Ks, Kc) -> (-Ks, -Ks)
+__device__ __forceinline__ void real_leg_tw(LaneTw &tw)
+{
+#pragma unroll
+    for (int l = 0; l < 2; l++)
+#pragma unroll
+        for (int w = 0; w < 2; w++) tw.s2[l][w] = __builtin_amdgcn_perm(0u, tw.s2[l][w], 0x01000100u);
+}
 __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, const LaneTw &tw, const u32x4 *tw3_lds,
                                                   uint32_t (&v)[4][4])
 {
@@ -217,12 +345,15 @@ __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, 
     const int base = rev2(d4) + 4 * rev2(d3);
     // bitrev8(j>>2) = base + 16*rev2(d2) + 64*rev2(d1); >= 160 <=> zero padding
     uint32_t y[10];
+    y[0] = *(const uint16_t *)(xw + base);
 #pragma unroll
-    // already A >> 2 as a 16-bit pattern (pass 1, .s:147-148); m < 4 = samples 0..63 = the A legs of pass 2, stored >> 2 once more
-    for (int m = 0; m < 10; m++) y[m] = *(const uint16_t *)(xw + base + 16 * m);
+    for (int m = 1; m < 4; m++) y[m] = ((const uint16_t *)(xw + base + 16 * m))[1];
+#pragma unroll
+    for (int m = 4; m < 10; m++) y[m] = xw[base + 16 * m];
     // (the A legs go into packed adds as they are: opaque, or the compiler re-zeroes halves that ds_read_u16 has just zero-extended)
 #pragma unroll
     for (int m = 0; m < 4; m++) asm("" : "+v"(y[m]));
+    // pass 2: the outputs of butterfly d2 are all leg d2 of pass 3 -- d2 = 0 the A legs (plain), d2 > 0 doubled
 #pragma unroll
     for (int d2 = 0; d2 < 4; d2++) {
         const int r2 = ((d2 & 1) << 1) | (d2 >> 1);
@@ -230,26 +361,33 @@ __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, 
         uint32_t x2 = y[4 + r2];                                  // d1 = 2 -> rows  64..127
         uint32_t x1 = (d2 == 0) ? y[8] : (d2 == 2) ? y[9] : 0u;   // d1 = 1 -> rows 128..159, else padding
         uint32_t x3 = 0u;                                         // d1 = 3 -> rows >= 192: padding
-        // real samples (imaginary half of the packed word is 0): the general Y*conj(K) dot products give
-        // (Yr*Kc, -Yr*Ks) directly, no sign extension needed; D = 0 => C' = D' = C
+        // real samples, duplicated, against the duplicated coefficient halves (real_leg_tw): the dot products give
+        // (2 Yr*Kc, -2 Yr*Ks) directly; D = 0 => C' = D' = C
         int cr, ci;
         cxmul(x2, tw.s2[1][0], tw.s2[1][1], cr, ci);
         (void)x3;
-        if (d2 == 0 || d2 == 2) {
+        if (d2 == 0) {
             int br, bi;
             cxmul(x1, tw.s2[0][0], tw.s2[0][1], br, bi);
-            r4_packed<false, true, true, true>(x0, br, bi, cr, ci, cr, ci, v[0][d2], v[1][d2], v[2][d2], v[3][d2]);
+            r4_packed_dbl<false, true, true, true, 0>(x0, 0u, br, bi, cr, ci, cr, ci, v[0][d2], v[1][d2], v[2][d2], v[3][d2]);
+        } else if (d2 == 2) {
+            int br, bi;
+            cxmul(x1, tw.s2[0][0], tw.s2[0][1], br, bi);
+            r4_packed_dbl<false, true, true, true, 1>(x0, 0u, br, bi, cr, ci, cr, ci, v[0][d2], v[1][d2], v[2][d2], v[3][d2]);
         } else {
-            r4_packed<false, false, true, true>(x0, 0, 0, cr, ci, cr, ci, v[0][d2], v[1][d2], v[2][d2], v[3][d2]);
+            r4_packed_dbl<false, false, true, true, 1>(x0, 0u, 0, 0, cr, ci, cr, ci, v[0][d2], v[1][d2], v[2][d2], v[3][d2]);
         }
     }
     // pass-3 coefficients (24 words per lane) are parked in LDS, shared by the workgroup's waves
     uint32_t k3[4][4][2];
     load_tw32_d0(tw3_lds, lane & 3, k3);
+    // pass 3: across the exchange an output's leg in pass 4 is d3 of THIS lane -- d3 = 0 writes A legs (m = 1), the others
+    // doubled legs (m = 2)
+    const uint32_t mul = d3 ? kPkTwo : kPkPlusMinus;
 #pragma unroll
     for (int d1 = 0; d1 < 4; d1++)
-        bfly_pk<false>(v[d1][0], v[d1][1], v[d1][2], v[d1][3], k3[d1][0][0], k3[d1][0][1], k3[d1][1][0], k3[d1][1][1],
-                       k3[d1][2][0], k3[d1][2][1], k3[d1][3][0], k3[d1][3][1]);
+        bfly_pk_dbl<false, true, 2>(v[d1][0], v[d1][1], v[d1][2], v[d1][3], k3[d1][0][0], k3[d1][0][1], k3[d1][1][0], k3[d1][1][1],
+                                    k3[d1][2][0], k3[d1][2][1], k3[d1][3][0], k3[d1][3][1], mul);
 }
 
 // lane (d0,d3,d4) -> LDS -> lane' = j & 63 holding u[d3][d4]
@@ -266,6 +404,19 @@ __device__ __forceinline__ void fft_exchange(uint32_t *buf, int lane, const uint
     for (int e3 = 0; e3 < 4; e3++)
 #pragma unroll
         for (int e4 = 0; e4 < 4; e4++) u[e3][e4] = buf[xaddr(lane + 64 * e3 + 256 * e4)];
+}
+
+// Pass-4 butterfly e4 behind fft_front_real160 + fft_exchange: its B, C and D legs u[1..3][e4] arrive doubled (written by the lanes
+// with d3 > 0).  Its outputs u[.][e4] are all leg e4 of pass 5, which takes only its B leg doubled (its HALF form needs p() of B
+// alone: doubling C and D there would turn their single v_perm_b32 into two instructions) -- so butterfly e4 = 1 emits doubled.
+__device__ __forceinline__ void fft_pass4_dbl(uint32_t (&u)[4][4], int e4, const LaneTw &tw)
+{
+    if (e4 == 1)
+        bfly_pk_dbl<false, true, 1>(u[0][e4], u[1][e4], u[2][e4], u[3][e4], tw.s4[0][0], tw.s4[0][1], tw.s4[1][0], tw.s4[1][1],
+                                    tw.s4[2][0], tw.s4[2][1], tw.s4[3][0], tw.s4[3][1]);
+    else
+        bfly_pk_dbl<false, true, 0>(u[0][e4], u[1][e4], u[2][e4], u[3][e4], tw.s4[0][0], tw.s4[0][1], tw.s4[1][0], tw.s4[1][1],
+                                    tw.s4[2][0], tw.s4[2][1], tw.s4[3][0], tw.s4[3][1]);
 }
 
 // ---- the full complex transform, one wave per array (used by the generic kernels: k_fft.hip, k_mfcc_gen.hip) ----
