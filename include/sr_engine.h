@@ -658,6 +658,83 @@ int sr_decode_words_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride
  * hold, 65 535 at most), out[2] = the longest template that fits, out[3] = columns (end frames) per kernel chunk. */
 int sr_decode_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t max_words, uint32_t out[4]);
 
+/* ------------------------------------------------------------------ live connected-word decoding: decoder state carried between pushes
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The decoder above takes a complete feature row and pays N x max_words x K x M
+ * cells for it.  A session takes the frames of n_channels channels as they arrive, in pushes of any size up to chunk_max,
+ * keeps per (channel, level, slot) ONE column of the recurrence and per channel the A / E history on the device between
+ * calls, and after every push says how everything heard so far parses: n x max_words x K x M cells per push of n frames,
+ * plus a trace.  No existing call, record or score changes.
+ * THE RULE: let Y_c be every feature frame pushed to channel c since it was opened or last ended, N = |Y_c|; N is at most
+ * utt_frames, fixed at open in 1..16 383 (the u32 cost bound and the start field of a key end there).  Every push emits one
+ * row for every channel with n[c] > 0, by ascending channel: an sr_chain_rec, max_words x sr_chain_word and optionally
+ * level_cost[max_words].  The row is, byte for byte, what the connected-word decoding section defines for Y_c as ONE row of N
+ * frames with the session's max_words, n_words_exact, skip_cost, word_cost and the engine's current word map -- whatever the
+ * chunking.  Whenever an engine's max_frames >= N it therefore equals what sr_decode_words_dp[_dev] writes for that row.
+ * start and end are 0-based frame indices of the channel's recording.  Ties: smallest start, then slot, then fewest words,
+ * unchanged.  Why it is exact: column x of a level depends on column x-1 and E_{l-1}(x) only; A_l(p) and E_l(p) depend on
+ * frames < p only, so the history of a recording is a prefix of that of any longer one; count and trace read A, E and N.
+ * PCM sessions (mid given at open): the channel's samples X_c, R = |X_c|, are framed exactly as the live word spotting section
+ * frames them (a segment with start = 1, end = R and mid[c]); n[c] counts samples, a row is emitted for n[c] > 0 whether or
+ * not a frame was completed, and while there are at most max_frames frames the row equals sr_decode_words_batch(X_c, 1, R,
+ * mid[c]).
+ * Every call refused for its arguments, its counts or the store (SR_ERR_BAD_ARG, SR_ERR_BAD_CONFIG, SR_ERR_NO_TEMPLATES) is
+ * refused before anything is enqueued: it writes nothing and changes no state.  A HIP failure (SR_ERR_HIP) may come after
+ * part of a push has been enqueued; the session is then undefined and must be closed.  Stream ordering as in the spot
+ * session: a push on another stream than the last push's is ordered behind it by an event, the host forms and
+ * sr_decode_live_end run behind the last push likewise.  A channel is bound to the template store that was set when the
+ * session was opened or the channel last ended; a push to a channel whose store has since been replaced returns
+ * SR_ERR_BAD_ARG until that channel is ended (its recording is then dropped: it ends with the SR_CH_NONE record).  The
+ * session uses its engine's scratch buffers: the engine's one-caller-at-a-time rule covers its sessions. */
+typedef struct sr_decode_live sr_decode_live;
+typedef struct sr_chain_live_row { /* 8 bytes: which channel an emitted row holds */
+    uint32_t channel;
+    uint32_t frames; /* N after the push */
+} sr_chain_live_row;
+/* host-only, no device: out[0] = device state bytes per channel -- the columns, max_words * K * tpl_rows * 16, plus the A / E
+ * history, (utt_frames + 1) * (max_words * 8 + (max_words + 1) * 4) -- saturating; out[1] = the longest template that fits
+ * (sr_spot_geometry's out[2]); out[2] = the kernel launches one feature push enqueues, 2 * max_words + 2.  tpl_rows and
+ * utt_frames 1..16 383, K 1..65 536, max_words 1..16, chunk_max 1..utt_frames. */
+int sr_decode_live_geometry(uint32_t tpl_rows, uint32_t K, uint32_t max_words, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[3]);
+/* mid NULL: a feature session, chunk_max in frames, 1..utt_frames.  mid a HOST array [n_channels]: a PCM session, chunk_max in
+ * samples; SR_ERR_BAD_ARG if a push of chunk_max samples could complete more than min(max_frames, utt_frames) frames.
+ * n_channels 1..65535.  Argument limits and configuration errors exactly as sr_decode_words_dp_dev. */
+int sr_decode_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames, uint32_t max_words,
+                        uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid, sr_decode_live **out);
+void sr_decode_live_close(sr_decode_live *l); /* before sr_destroy of its engine; waits for the session's last push */
+/* One push.  n: HOST array [n_channels] in both forms, 0 <= n[c] <= chunk_max, 0 leaves the channel untouched; NULL: n_all
+ * each.  Channel c's new frames are d_mfcc + c*row_stride (s16, 12 per frame; row_stride in s16 elements, at least 12 times
+ * the largest count); nothing past n[c] frames of a row is read.  DEVICE form: d_mfcc 8-byte aligned, row_stride a multiple
+ * of 4; ONE asynchronous operation on `stream`, no host synchronisation, no read-back.  d_rec[r], d_words[r*max_words + i]
+ * and the optional d_level_cost[r*max_words + i] are COMPACT over the emitted rows r; rows at and past *n_rows are not
+ * written.  rows[max_rows] and *n_rows are HOST outputs, filled from the counts alone before the call returns.  Refused
+ * (SR_ERR_BAD_ARG): a count above chunk_max, a push that would take a channel past utt_frames, max_rows below the number of
+ * channels with n[c] > 0, a channel bound to a replaced store, a word map that does not fit, a null required pointer,
+ * outputs that overlap. */
+int sr_decode_live_push_dev(sr_decode_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                            uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost,
+                            sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+/* the same on HOST buffers (2-byte aligned rows, any row_stride that holds the largest count) */
+int sr_decode_live_push(sr_decode_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                        uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, sr_chain_live_row *rows,
+                        uint32_t *n_rows);
+/* PCM sessions: channel c's new samples are d_pcm + c*pcm_stride, n in samples; alignment rules as sr_spot_live_push_pcm_dev
+ * (device form: 16-byte aligned, pcm_stride a multiple of 8).  The spot session's copy kernels and the frame kernel launch of
+ * sr_mfcc_batch_dev turn them into the push's new frames, the decoder runs over those. */
+int sr_decode_live_push_pcm_dev(sr_decode_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                                uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost,
+                                sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_decode_live_push_pcm(sr_decode_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                            uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost,
+                            sr_chain_live_row *rows, uint32_t *n_rows);
+/* The listed channels' recordings end here: HOST outputs rec[n_ch], words[n_ch][max_words], the optional level_cost[n_ch]
+ * [max_words] and rows[n_ch], of which *n_rows rows are written -- one per DISTINCT listed channel, at its first mention: the
+ * decode of everything pushed to it (an empty channel gives the SR_CH_NONE record, as an empty row does in the batch call).
+ * Waits for the device.  Each listed channel is then as freshly opened, and bound to the current store.  rows overlapping
+ * rec, words or level_cost is refused like outputs that overlap in a push.  A HIP failure (SR_ERR_HIP) before the trace --
+ * an allocation -- writes nothing and leaves the session as it was; one after it leaves the session undefined, as in a push. */
+int sr_decode_live_end(sr_decode_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
+                       uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows);
+
 /* ------------------------------------------------------------------ full-DP alignment and word models from many examples
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this
  * section says HOW the two were aligned, and builds word models from many examples on top of that (DTW barycentre

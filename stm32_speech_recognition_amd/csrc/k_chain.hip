@@ -20,8 +20,6 @@
 
 namespace sr {
 
-constexpr uint32_t kChainNone = 0xFFFFFFFFu;  // an unreachable prefix cost (= SR_DIS_ERR)
-
 __device__ __forceinline__ unsigned long long *chain_A(const ChainArgs &a, uint32_t row, uint32_t level)  // level 1..max_words
 {
     return a.A + ((size_t)row * a.max_words + (level - 1)) * (a.max_frames + 1u);
@@ -165,67 +163,13 @@ __global__ void __launch_bounds__(256) k_chain_close(const ChainArgs a, const ui
     }
 }
 
-// the word count, the walk back through the levels, the records.  One wave per row looks at 64 prefix positions at a time.
+// the word count, the walk back through the levels, the records (chain_trace_row, sr_spot_dev.h).  One wave per row.
 __global__ void __launch_bounds__(64) k_chain_trace(const ChainArgs a)
 {
-    const uint32_t row = blockIdx.x, lane = threadIdx.x, W = a.max_words;
-    const uint32_t N = chain_frames(a, row);
-    sr_chain_word *words = a.words + (size_t)row * W;
-    // E_l(N) of every level; the count: the given one, or the first minimum in ascending l
-    uint32_t c = kChainNone;
-    if (lane >= 1 && lane <= W) c = chain_E(a, row, lane)[N];
-    if (a.level_cost && lane >= 1 && lane <= W) a.level_cost[(size_t)row * W + lane - 1] = c;
-    uint32_t n = a.n_words_exact;
-    if (!n) {
-        uint64_t key = ((uint64_t)c << 32) | lane;  // lanes without a level carry all-ones costs and lose to none of them
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) key = spot_min(key, spot_shfl(key, lane ^ (uint32_t)d));
-        n = (uint32_t)(key >> 32) == kChainNone ? 1u : (uint32_t)key;
-    }
-    const uint32_t total = __shfl(c, (int)n, 64);
-    const bool ok = total != kChainNone;
-    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    for (uint32_t i = (ok ? n : 0u) + lane; i < W; i += 64) words[i] = none;
-    if (!ok) {
-        if (lane == 0) a.rec[row] = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
-        return;
-    }
-    uint32_t p = N, in_words = 0;
-    for (uint32_t l = n; l >= 1; l--) {  // (uniform)
-        const unsigned long long *A = chain_A(a, row, l);
-        const uint32_t *E = chain_E(a, row, l);
-        // the first position at or below p whose own word closes E_l there; E_l(p) is finite, so there is one above 0
-        uint64_t key = kSpotInf;
-        uint32_t cum = 0;
-        while (p >= 1) {
-            const bool mine = lane < p;  // position p - lane >= 1
-            const uint64_t ky = mine ? A[p - lane] : kSpotInf;
-            const uint32_t e = mine ? E[p - lane] : kChainNone;
-            const unsigned long long hit = __ballot(mine && ky != kSpotInf && (uint32_t)(ky >> 32) == e);
-            if (hit) {
-                const uint32_t first = (uint32_t)__ffsll((long long)hit) - 1u;
-                key = spot_shfl(ky, first);
-                cum = __shfl(e, (int)first, 64);
-                p -= first;
-                break;
-            }
-            p = p > 64u ? p - 64u : 0u;
-        }
-        if (key == kSpotInf) {  // cannot happen while A and E agree; leave a whole record that says so
-            for (uint32_t i = lane; i < W; i += 64) words[i] = none;
-            if (lane == 0) a.rec[row] = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
-            return;
-        }
-        const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu, end = p - 1;
-        if (lane == 0) {
-            const uint32_t acc = (uint32_t)(key >> 32) - a.word_cost - chain_E(a, row, l - 1)[start];
-            words[l - 1] = sr_chain_word{a.word_id[a.group_of_slot[slot]], slot, start, end, acc, acc / (end - start + 1 + a.tpl_frames[slot]),
-                                         cum, 0u};
-        }
-        in_words += end - start + 1;
-        p = start;
-    }
-    if (lane == 0) a.rec[row] = sr_chain_rec{total, n, N - in_words, SR_CH_OK};
+    const uint32_t row = blockIdx.x, W = a.max_words;
+    chain_trace_row(chain_A(a, row, 1), chain_E(a, row, 0), a.max_frames + 1u, chain_frames(a, row), W, a.n_words_exact, a.word_cost, a.tpl_frames,
+                    a.group_of_slot, a.word_id, a.rec + row, a.words + (size_t)row * W, a.level_cost ? a.level_cost + (size_t)row * W : nullptr,
+                    threadIdx.x);
 }
 
 void launch_chain(const ChainArgs &a, hipStream_t s)

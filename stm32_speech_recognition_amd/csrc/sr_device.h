@@ -383,6 +383,40 @@ struct ChainArgs {
 };
 void launch_chain(const ChainArgs &a, hipStream_t s);  // init, max_words x (k_chain_words, k_chain_close), k_chain_trace
 
+// live connected-word decoding (k_chain_live.hip): the levels of k_chain.hip resumed from push to push.  Per channel the session
+// keeps one boundary column per (level, slot), cols[C][max_words][K][tpl_len], and the history A[C][max_words][P] /
+// E[C][max_words + 1][P], P = utt_frames + 1, in ChainArgs' layout with max_frames = utt_frames: after every push positions
+// 0..N of a channel hold what the batch decoder's scratch holds for its recording as one row.  The per-channel entry is the
+// spot session's (the PCM kernels read it): x0, n as there; row_base = the channel's compact output row; first_win != 0 = the
+// channel emits a row (a push: n > 0; sr_decode_live_end: a listed channel, n = 0, x0 = its frames).
+struct ChainLiveArgs {
+    const int16_t *mfcc;        // channel c's new frames at mfcc + c * row_stride, 8-byte aligned rows
+    uint64_t row_stride;        // s16 elements
+    const SpotLiveChan *chan;   // [C]
+    uint32_t C;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a boundary column
+    uint32_t P;                 // utt_frames + 1: positions of a level's history
+    uint32_t max_words;
+    uint32_t n_words_exact;
+    uint32_t skip_cost;         // SR_DIS_ERR: no skipping
+    uint32_t word_cost;
+    ulonglong2 *cols;
+    unsigned long long *A;
+    uint32_t *E;
+    const uint32_t *group_of_slot;
+    const uint32_t *word_id;
+    sr_chain_rec *rec;          // [rows], compact over the emitting channels
+    sr_chain_word *words;       // [rows][max_words]
+    uint32_t *level_cost;       // optional [rows][max_words]
+};
+void launch_chain_live(const ChainLiveArgs &a, hipStream_t s);        // init, max_words x (words, close), trace
+void launch_chain_live_trace(const ChainLiveArgs &a, hipStream_t s);  // the trace alone (sr_decode_live_end)
+
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the
 // marks are indexed by the pair of the launch.

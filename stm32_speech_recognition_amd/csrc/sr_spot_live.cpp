@@ -5,6 +5,7 @@
 // The host knows every count: each channel's frames so far, hence which windows a push completes and which output row each
 // of them gets (the mirror below).  Nothing is read back to size or to label an output.
 #include "sr_host_call.h"
+#include "sr_live_pcm.h"
 
 using namespace sr;
 
@@ -132,26 +133,8 @@ int upload_plan(sr_spot_live *l, const PushPlan &pl, hipStream_t s)
 // PCM sessions: [kept | chunk] rows, the frame kernel over them as sr_mfcc_batch_dev launches it, the samples to keep
 int launch_front_end(sr_spot_live *l, const PushPlan &pl, const uint16_t *d_pcm, uint64_t pcm_stride, hipStream_t s)
 {
-    sr_engine *h = l->h;
-    const SpotLivePcmArgs pa{l->d_chan.p, l->C, d_pcm, pcm_stride, l->keep.p, l->keep_stride, l->stage.p, l->stage_stride, pl.max_row};
-    launch_spot_live_stage(pa, s);
-    if (pl.max_frames) {
-        std::vector<sr_vad_rec> recs(l->C);
-        for (uint32_t c = 0; c < l->C; c++) {
-            sr_vad_rec &r = recs[c];
-            std::memset(&r, 0, sizeof r);
-            r.atap.mid_val = l->mid[c];
-            for (int i = 0; i < 2 * SR_MAX_SEG; i++) r.seg[i] = -1;
-            r.seg[0] = 1;  // sample 0 of a row is the first new frame's pre-emphasis predecessor
-            r.seg[1] = (int32_t)(pl.chan[c].kept + pl.chan[c].n_samp);
-            r.frm_num = pl.chan[c].n;
-        }
-        HIP_TRY(hipMemcpyAsync(l->recs.p, recs.data(), (size_t)l->C * sizeof(sr_vad_rec), hipMemcpyHostToDevice, s));
-        launch_mfcc(mfcc_args(h, l->stage.p, l->stage_stride, l->C, l->recs.p, l->feat.p), mfcc_mag_tab(h), s);
-    }
-    launch_spot_live_keep(pa, s);
-    HIP_TRY(hipGetLastError());
-    return SR_OK;
+    return live_pcm_front_end(l->h, l->d_chan.p, pl.chan, l->mid, pl.max_row, pl.max_frames, d_pcm, pcm_stride, l->keep.p, l->keep_stride,
+                              l->stage.p, l->stage_stride, l->recs.p, l->feat.p, s);
 }
 
 // the push is enqueued: the mirror follows, and the caller learns which window each row holds
@@ -260,8 +243,8 @@ int sr_spot_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uin
     if (!rc) rc = l->d_chan.reserve(n_channels);
     if (!rc && mid) {
         l->mid.assign(mid, mid + n_channels);
-        l->keep_stride = (h->frame_len + 7u) & ~7u;  // a channel keeps at most frame_len samples
-        l->stage_stride = ((uint64_t)2 * h->frame_len + chunk_max + 16 + 7) & ~7ull;  // [kept | chunk] and a frame of slack
+        l->keep_stride = live_pcm_keep_stride(h);
+        l->stage_stride = live_pcm_stage_stride(h, chunk_max);
         rc = l->keep.reserve((size_t)n_channels * l->keep_stride);
         if (!rc) rc = l->stage.reserve((size_t)n_channels * l->stage_stride);
         if (!rc) rc = l->recs.reserve(n_channels);

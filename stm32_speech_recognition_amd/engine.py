@@ -43,8 +43,10 @@ CHAIN_REC_DTYPE = np.dtype([("cost", "<u4"), ("n_words", "<u4"), ("skipped", "<u
 CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4"), ("dis", "<u4"),
                              ("cum", "<u4"), ("reserved", "<u4")])
 CH_OK, CH_NONE = 0, 1
+# sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
+CHAIN_LIVE_ROW_DTYPE = np.dtype([("channel", "<u4"), ("frames", "<u4")])
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
-assert CHAIN_REC_DTYPE.itemsize == 16 and CHAIN_WORD_DTYPE.itemsize == 32
+assert CHAIN_REC_DTYPE.itemsize == 16 and CHAIN_WORD_DTYPE.itemsize == 32 and CHAIN_LIVE_ROW_DTYPE.itemsize == 8
 assert ALIGN_DTYPE.itemsize == 16 and TRAIN_STAT_DTYPE.itemsize == 16
 assert ATAP_DTYPE.itemsize == 12 and STREAM_SEG_DTYPE.itemsize == 16 and NBEST_DTYPE.itemsize == 16
 assert LIVE_SEG_DTYPE.itemsize == 24
@@ -648,6 +650,11 @@ class Engine:
                                                  _vp(out["status"])))
         return out
 
+    def decode_live(self, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
+        """sr_decode_live_open: a DecodeSession of n_channels channels of at most utt_frames frames each.  mid None: a feature
+        session (chunk_max in frames); mid uint32 [n_channels]: a PCM session (chunk_max in samples)."""
+        return DecodeSession(self, n_channels, chunk_max, utt_frames, max_words, n_words, skip_cost, word_cost, mid)
+
     # ---- full-DP alignment and word models from many examples -----------------------------------------
     def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
         """OPT-IN (sr_dtw_dp_align): the optimal warping path of the full-DP scorer for every (row, reference) pair.  mfcc int16
@@ -1236,6 +1243,152 @@ class SpotSession:
         wins, n = np.zeros(max(len(ch), 1), dtype=SPOT_WIN_DTYPE), C.c_uint32(0)
         self.eng._check(self.L.sr_spot_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(hits), _vp(wins), C.byref(n)))
         return dict(hits=hits[:n.value], wins=wins[:n.value], n_rows=n.value)
+
+
+def decode_live_geometry(tpl_rows, K, max_words, utt_frames, chunk_max):
+    """Host-only sr_decode_live_geometry: dict(state_bytes on the device per channel, max_tpl_rows that fit, launches one
+    feature push enqueues)"""
+    L = load_library()
+    out = (C.c_uint32 * 3)()
+    rc = L.sr_decode_live_geometry(C.c_uint32(tpl_rows), C.c_uint32(K), C.c_uint32(max_words), C.c_uint32(utt_frames), C.c_uint32(chunk_max),
+                                   out)
+    if rc != 0:
+        raise SrError(f"sr_decode_live_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(state_bytes=out[0], max_tpl_rows=out[1], launches=out[2])
+
+
+class DecodeSession:
+    """One sr_decode_live handle (Engine.decode_live): connected-word decoding over chunked features or samples on n_channels
+    channels, the decoder's state carried between pushes.  After every push the row of a channel is Engine.decode_words on
+    everything pushed to it as one row (include/sr_engine.h, "live connected-word decoding")."""
+
+    def __init__(self, eng, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
+        self.eng, self.L, self.n_channels, self.chunk_max, self.utt_frames = eng, eng.L, n_channels, chunk_max, utt_frames
+        self.max_words = max_words
+        self.L.sr_decode_live_close.restype = None
+        self.L.sr_decode_live_close.argtypes = [C.c_void_p]
+        md = None if mid is None else np.ascontiguousarray(mid, dtype=np.uint32)
+        assert md is None or md.shape == (n_channels,)
+        self.pcm = md is not None
+        self._frames = np.zeros(n_channels, np.uint32)  # what the rows of the pushes said, per channel
+        l = C.c_void_p()
+        eng._check(self.L.sr_decode_live_open(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames),
+                                              C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(Engine._skip(skip_cost)),
+                                              C.c_uint32(word_cost), _vp(md), C.byref(l)))
+        self.l = l
+
+    def close(self):
+        if getattr(self, "l", None):
+            self.L.sr_decode_live_close(self.l)
+            self.l = None
+
+    def __del__(self):
+        try:
+            if getattr(self.eng, "h", None):  # a session never outlives its engine's handle
+                self.close()
+        except Exception:
+            pass
+
+    @property
+    def frames(self):
+        """frames of every channel's recording so far, uint32 [n_channels] (from the rows the calls returned)"""
+        return self._frames.copy()
+
+    def _counts(self, counts, width):
+        """(host uint32 array or None, n_all, the number of rows a push with these counts emits)"""
+        if counts is None:
+            return None, width, self.n_channels if width else 0
+        ct = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert ct.shape == (self.n_channels,)
+        return ct, 0, int((ct > 0).sum())
+
+    def _took(self, rows):
+        self._frames[rows["channel"]] = rows["frames"]
+
+    def _push_host(self, fn, data, stride, width, counts, max_rows):
+        ct, n_all, emit = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = emit
+        W = self.max_words
+        rec, words = np.zeros(max_rows, dtype=CHAIN_REC_DTYPE), np.zeros((max_rows, W), dtype=CHAIN_WORD_DTYPE)
+        lc = np.zeros((max_rows, W), dtype=np.uint32)
+        rows, n = np.zeros(max_rows, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(rec), _vp(words),
+                           _vp(lc), _vp(rows), C.byref(n)))
+        self._took(rows[:n.value])
+        return dict(rec=rec[:n.value], words=words[:n.value], level_cost=lc[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+    def _push_dev(self, fn, data, stride, width, counts, max_rows, level_cost, stream):
+        import torch
+        ct, n_all, emit = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = emit
+        W, dev = self.max_words, data.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        cap = max(max_rows, 1)
+        rec = torch.empty(cap, 4, dtype=torch.int32, device=dev)[:max_rows]
+        words = torch.empty(cap, W, 8, dtype=torch.int32, device=dev)[:max_rows]
+        lc = torch.empty(cap, W, dtype=torch.int32, device=dev)[:max_rows] if level_cost else None
+        rows, n = np.zeros(max_rows, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(rec), _vp(words),
+                           _vp(lc), _vp(rows), C.byref(n), C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            for t in (data, rec, words, lc):
+                if t is not None:
+                    t.record_stream(stream)  # allocated on the current stream, used on `stream`
+        self._took(rows[:n.value])
+        return dict(rec=rec[:n.value], words=words[:n.value], level_cost=None if lc is None else lc[:n.value], rows=rows[:n.value],
+                    n_rows=n.value)
+
+    def push(self, frames, counts=None, max_rows=None):
+        """sr_decode_live_push: frames int16 [n_channels, F, 12], counts [n_channels] (None: F each).  Returns dict(rec
+        CHAIN_REC_DTYPE [n_rows], words CHAIN_WORD_DTYPE [n_rows, max_words], level_cost uint32 [n_rows, max_words], rows
+        CHAIN_LIVE_ROW_DTYPE [n_rows], n_rows) of numpy arrays: one row per channel with a nonzero count."""
+        mf = np.ascontiguousarray(frames, dtype=np.int16)
+        assert mf.ndim == 3 and mf.shape[0] == self.n_channels and mf.shape[2] == N_COEF
+        F = mf.shape[1]
+        return self._push_host(self.L.sr_decode_live_push, mf, max(F, 1) * N_COEF, F, counts, max_rows)
+
+    def push_dev(self, frames, counts=None, max_rows=None, level_cost=True, stream=None):
+        """sr_decode_live_push_dev on a device tensor: frames int16 [n_channels, F, 12], counts a HOST array [n_channels] (None:
+        F each).  Asynchronous on `stream` (a torch.cuda.Stream, or the current one).  Returns dict(rec int32 [n_rows, 4], words
+        int32 [n_rows, max_words, 8], level_cost int32 [n_rows, max_words] or None -- device tensors, compact over the emitted
+        rows -- rows, n_rows on the host)."""
+        import torch
+        assert frames.is_cuda and frames.dtype == torch.int16 and frames.is_contiguous()
+        assert frames.ndim == 3 and frames.shape[0] == self.n_channels and frames.shape[2] == N_COEF
+        F = frames.shape[1]
+        return self._push_dev(self.L.sr_decode_live_push_dev, frames, max(F, 1) * N_COEF, F, counts, max_rows, level_cost, stream)
+
+    def push_pcm(self, chunks, counts=None, max_rows=None):
+        """sr_decode_live_push_pcm: chunks uint16 [n_channels, S], counts [n_channels] in samples (None: S each); returns as push"""
+        pcm = np.ascontiguousarray(chunks, dtype=np.uint16)
+        assert pcm.ndim == 2 and pcm.shape[0] == self.n_channels
+        S = pcm.shape[1]
+        return self._push_host(self.L.sr_decode_live_push_pcm, pcm, max(S, 1), S, counts, max_rows)
+
+    def push_pcm_dev(self, chunks, counts=None, max_rows=None, level_cost=True, stream=None):
+        """sr_decode_live_push_pcm_dev: chunks int16 [n_channels, S] on the device (u16 codes, S a multiple of 8); returns as
+        push_dev"""
+        import torch
+        assert chunks.is_cuda and chunks.dtype in (torch.int16, torch.uint16) and chunks.is_contiguous()
+        assert chunks.ndim == 2 and chunks.shape[0] == self.n_channels
+        S = chunks.shape[1]
+        return self._push_dev(self.L.sr_decode_live_push_pcm_dev, chunks, S, S, counts, max_rows, level_cost, stream)
+
+    def end(self, channels):
+        """sr_decode_live_end: the listed channels' recordings end here.  Returns dict(rec, words, level_cost, rows, n_rows) as
+        push: one row per distinct listed channel, the parse of everything pushed to it; afterwards the channels are as
+        freshly opened."""
+        ch = np.ascontiguousarray(np.atleast_1d(channels), dtype=np.uint32)
+        cap, W = max(len(ch), 1), self.max_words
+        rec, words = np.zeros(cap, dtype=CHAIN_REC_DTYPE), np.zeros((cap, W), dtype=CHAIN_WORD_DTYPE)
+        lc = np.zeros((cap, W), dtype=np.uint32)
+        rows, n = np.zeros(cap, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(self.L.sr_decode_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(lc), _vp(rows), C.byref(n)))
+        self._frames[rows[:n.value]["channel"]] = 0
+        return dict(rec=rec[:n.value], words=words[:n.value], level_cost=lc[:n.value], rows=rows[:n.value], n_rows=n.value)
 
 
 def live_segs_from_torch(t):
