@@ -265,6 +265,51 @@ void sr_oracle_vad(const sr_oracle *o, const uint16_t *vc, uint32_t buf_len, con
     }
 }
 
+/* ---- VAD.C:121-164, frame by frame -------------------------------------- */
+/* The sample loop of sr_oracle_vad above over ALL frames of the buffer (no stop after max_seg segments), with what it
+   computes per frame handed out instead of fed to the endpoint state machine: frm_sum, frm_zero and the "loud" decision
+   of VAD.C:164.  Each output is optional and holds one entry per frame; returns the frame count. */
+uint32_t sr_oracle_vad_frames(const sr_oracle *o, const uint16_t *vc, uint32_t buf_len, const sr_oracle_atap *atap,
+                              uint32_t *frm_sum_out, uint32_t *frm_zero_out, uint8_t *loud_out)
+{
+    uint8_t last_sig = 0; /* never reset: carries across samples AND frames (VAD.C:99) */
+    uint32_t fl = o->frame_len, hop = o->hop, n = 0;
+    uint32_t mid = atap->mid_val;
+    uint32_t a_thl = mid + atap->n_thl;
+    uint32_t b_thl = mid - atap->n_thl; /* wraps if n_thl > mid, as in the reference */
+
+    if (buf_len < fl)
+        return 0;
+    for (uint32_t i = 0; i < buf_len - fl; i += hop, n++) {
+        uint32_t frm_sum = 0, frm_zero = 0;
+        for (uint32_t h = 0; h < fl; h++) {
+            uint32_t v = vc[i + h];
+            frm_sum += (v > mid) ? (v - mid) : (mid - v);
+        }
+        for (uint32_t h = 0; h < fl - 1; h++) {
+            uint32_t v0 = vc[i + h], v1 = vc[i + h + 1];
+            if (v0 >= a_thl)
+                last_sig = 2;
+            else if (v0 < b_thl)
+                last_sig = 1;
+            if (v1 >= a_thl) {
+                if (last_sig == 1)
+                    frm_zero++;
+            } else if (v1 < b_thl) {
+                if (last_sig == 2)
+                    frm_zero++;
+            }
+        }
+        if (frm_sum_out)
+            frm_sum_out[n] = frm_sum;
+        if (frm_zero_out)
+            frm_zero_out[n] = frm_zero;
+        if (loud_out)
+            loud_out[n] = (frm_sum > atap->s_thl || frm_zero > atap->z_thl) ? 1 : 0;
+    }
+    return n;
+}
+
 /* ---- MFCC.C:27-62 ------------------------------------------------------- */
 int sr_oracle_fft_mag(const sr_oracle *o, const int16_t *frame, uint32_t len, uint32_t *mag)
 {

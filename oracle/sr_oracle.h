@@ -76,6 +76,10 @@ int sr_oracle_noise_atap(const sr_oracle *o, const uint16_t *noise, uint32_t n_l
 /* VAD.C:97-218.  seg[2*s], seg[2*s+1] = start/end sample offsets, -1 = NULL. */
 void sr_oracle_vad(const sr_oracle *o, const uint16_t *vc, uint32_t buf_len, const sr_oracle_atap *atap,
                    int32_t *seg);
+/* VAD.C:121-164 for every frame of the buffer (no stop after max_seg segments): frm_sum[f], frm_zero[f] and
+   loud[f] = (frm_sum > s_thl || frm_zero > z_thl) of frame f, each optional.  Returns the frame count. */
+uint32_t sr_oracle_vad_frames(const sr_oracle *o, const uint16_t *vc, uint32_t buf_len, const sr_oracle_atap *atap,
+                              uint32_t *frm_sum, uint32_t *frm_zero, uint8_t *loud);
 /* MFCC.C:27-62 (magnitude*10 of the first nfft/2 bins of one frame). */
 int sr_oracle_fft_mag(const sr_oracle *o, const int16_t *frame, uint32_t len, uint32_t *mag);
 /* MFCC.C:86-191.  buf[start-1] is read (MFCC.C:119).  Returns frm_num (0 if > max_frames). */

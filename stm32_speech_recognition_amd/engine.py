@@ -43,6 +43,8 @@ CHAIN_REC_DTYPE = np.dtype([("cost", "<u4"), ("n_words", "<u4"), ("skipped", "<u
 CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4"), ("dis", "<u4"),
                              ("cum", "<u4"), ("reserved", "<u4")])
 CH_OK, CH_NONE = 0, 1
+# sr_vad_debug_masks: 16 words per capture, 63 frames (one round of the VAD kernel) per 64-bit word
+VAD_MASK_WORDS, VAD_MASK_FRAMES = 16, 63
 # sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
 CHAIN_LIVE_ROW_DTYPE = np.dtype([("channel", "<u4"), ("frames", "<u4")])
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
@@ -443,6 +445,19 @@ class Engine:
         self._check(self.L.sr_vad_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S if buf_len is None else buf_len),
                                         C.c_uint32(B), _vp(vd)))
         return vd
+
+    def vad_debug_masks(self, pcm, buf_len=None):
+        """sr_vad_debug_masks (diagnostics): the VAD records of vad() and the per-frame "loud" bits (VAD.C:164) the kernel
+        based them on, masks uint64 [B, 16]: bit k of word r = frame 63 * r + k (unpack_vad_masks).  A capture's words
+        stay zero past the round in which its max_seg-th segment closed, and captures of more than 16 * 63 = 1 008 frames
+        are outside what the diagnostic holds."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        vd = np.zeros(B, dtype=VAD_DTYPE)
+        masks = np.zeros((B, VAD_MASK_WORDS), dtype=np.uint64)
+        self._check(self.L.sr_vad_debug_masks(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S if buf_len is None else buf_len),
+                                              C.c_uint32(B), _vp(vd), _vp(masks)))
+        return vd, masks
 
     def mfcc(self, pcm, start, end, mid):
         """get_mfcc of segment [start[b], end[b]) of row b with mid value mid[b]."""
@@ -1389,6 +1404,16 @@ class DecodeSession:
         self.eng._check(self.L.sr_decode_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(lc), _vp(rows), C.byref(n)))
         self._frames[rows[:n.value]["channel"]] = 0
         return dict(rec=rec[:n.value], words=words[:n.value], level_cost=lc[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+
+def unpack_vad_masks(masks, n_frames=None):
+    """Engine.vad_debug_masks' words uint64 [B, 16] as a bool array [B, F]: bit k of word r = frame 63 * r + k (bit 63 of a
+    word is never set).  F = n_frames, or all 1 008 frames the words can hold."""
+    m = np.ascontiguousarray(masks, dtype=np.uint64)
+    assert m.ndim == 2 and m.shape[1] == VAD_MASK_WORDS
+    bits = (m[:, :, None] >> np.arange(VAD_MASK_FRAMES, dtype=np.uint64)[None, None, :]) & np.uint64(1)
+    out = bits.astype(bool).reshape(m.shape[0], VAD_MASK_WORDS * VAD_MASK_FRAMES)
+    return out if n_frames is None else out[:, :n_frames]
 
 
 def live_segs_from_torch(t):

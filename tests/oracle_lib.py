@@ -150,6 +150,16 @@ class Oracle:
         self.L.sr_oracle_vad(self.h, _p(pcm), C.c_uint32(len(pcm)), C.byref(atap), _p(seg))
         return seg
 
+    def vad_frames(self, pcm, atap):
+        """VAD.C:121-164 for every frame of the buffer: (frm_sum uint32 [F], frm_zero uint32 [F], loud bool [F])"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        cap = len(pcm) // max(self.hop, 1) + 1
+        fs, fz, ld = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+        self.L.sr_oracle_vad_frames.restype = C.c_uint32
+        n = self.L.sr_oracle_vad_frames(self.h, _p(pcm), C.c_uint32(len(pcm)), C.byref(atap), _p(fs), _p(fz), _p(ld))
+        assert n <= cap
+        return fs[:n].copy(), fz[:n].copy(), ld[:n].astype(bool)
+
     def fft_mag(self, frame):
         frame = np.ascontiguousarray(frame, dtype=np.int16)
         mag = np.zeros(self.cfg.nfft // 2, dtype=np.uint32)
