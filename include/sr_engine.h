@@ -735,6 +735,85 @@ int sr_decode_live_push_pcm(sr_decode_live *l, const uint16_t *pcm, uint64_t pcm
 int sr_decode_live_end(sr_decode_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
                        uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows);
 
+/* ------------------------------------------------------------------ grammar-constrained decoding: level building over a word network
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The connected-word decoder accepts ANY sequence of words; an application has a
+ * syntax (digit strings of a known shape, a command and its argument).  A grammar is a finite-state network whose arcs carry
+ * words; the decoder below returns the cheapest parse among the word sequences the network accepts, and spends no cell on the
+ * others.  No existing call, record, score or byte changes.
+ *   grammar  states 0..S-1, state 0 the start; final_state[s] != 0 flags the final states; n_arcs distinct arcs (from, to,
+ *            word), word a label of the engine's word map (sr_set_word_map; default word = slot).  slots(w) = the valid slots
+ *            with label w.  For a pair (t, w) with at least one arc, From(t, w) = { s : (s, t, w) is an arc }.
+ *   limits   S 1..64 (a from-set is one 64-bit mask), n_arcs 1..4096, every word a label of the current map.  No duplicate
+ *            arcs, no empty (epsilon) arcs, no arc weights.  Dead and unreachable states are allowed; a word whose slots are
+ *            all invalid is allowed and contributes nothing.
+ * Everything not restated here is the connected-word decoding section: d, the word path, skip_cost, word_cost, the argument
+ * limits, the u32 cost bound, the record formats.
+ *   E_0(p,s) that section's E_0(p) for s = 0; INF for every other state.
+ *   charge   C_l(x; t, w) = min over s in From(t, w) of E_{l-1}(x, s).
+ *   level l  >= 1, per pair (t, w) and slot k of slots(w): the spotter's recurrence with D(x,0) = C_l(x; t, w) + d(x,0),
+ *            S(x,0) = x, the start unreachable where the charge is.
+ *   A_l(p,t) p >= 1: the minimum over all pairs (t, w) and all k of slots(w) of (D_k(p-1, M_k-1) + word_cost, S, k), candidates
+ *            compared as (cost, start, slot).  A slot has one label, so for a fixed t it occurs at most once.
+ *   E_l(p,t) min(A_l(p,t).cost, E_l(p-1,t) + skip_cost), the second term only when skipping is on; E_l(0,t) = INF.  Filler
+ *            after a word stays in that word's target state.
+ *   L_l      min over the final states f of E_l(N, f): the level cost.
+ *   count    n = n_words_exact when that is nonzero, else the n of 1..max_words with the smallest L_n, the fewest words among
+ *            equal costs.  No finite L_n: status SR_CH_NONE, with the decoder's record.
+ *   end      the smallest final state f with E_n(N, f) = L_n.
+ *   trace    p = N, t = f; for l = n down to 1: while A_l(p,t) is unreachable or its cost differs from E_l(p,t), p -= 1; word
+ *            l is A_l(p,t): its slot k, start = S, end = p-1, cum = E_l(p,t); acc = cost - word_cost - C_l(S; t, w(k)); the
+ *            source state is the smallest s of From(t, w(k)) with E_{l-1}(S, s) = C_l(S; t, w(k)); then p = S, t = s.
+ *   records  sr_chain_rec and sr_chain_word as they are; in rows written by the calls below sr_chain_word.reserved holds the
+ *            grammar state AFTER the word (t).  d_level_cost[l-1] = L_l.
+ * Why one pass per (slot, target state) serves every arc of that word into that state: min_s (E(x,s) + path) = (min_s E(x,s))
+ * + path, and the source state is recoverable from E_{l-1} at the start column.  A word-pair grammar (one state per word)
+ * therefore costs the K passes per level of the unconstrained decoder.
+ * Anchor: S = 1, final_state[0] = 1 and one arc (0, 0, w) per label give, byte for byte, what sr_decode_words_dp writes
+ * (reserved = 0 included).
+ * Out of scope: a live, push-by-push grammar session; arc weights; epsilon arcs; more than 64 states. */
+typedef struct sr_gram_arc { /* 16 bytes */
+    uint32_t from;
+    uint32_t to;
+    uint32_t word;
+    uint32_t reserved; /* 0 */
+} sr_gram_arc;
+typedef struct sr_grammar sr_grammar;
+/* Compiles the grammar against the engine's CURRENT store and word map: the distinct from-sets as 64-bit masks, the items
+ * (slot, target state, from-set) and, per level 1..16, the items that can matter.  The only call of this section that may wait
+ * for the device and upload.  arcs and final_state[n_states] are HOST arrays.  Many grammars may exist per engine (one per
+ * dialogue state).  A grammar is bound to the store and the word map it was compiled against: after either is set again a
+ * decode call with it returns SR_ERR_BAD_ARG and writes nothing.  Errors, nothing created: SR_ERR_BAD_CONFIG unless n_coef ==
+ * 12; SR_ERR_NO_TEMPLATES; SR_ERR_BAD_ARG for a null pointer, n_states 0 or above 64, n_arcs 0 or above 4096, a state index at
+ * or above n_states, a duplicate arc, nonzero reserved, a word the map does not have, no final state, a word map that does not
+ * fit the store, a store of more than 65 536 slots. */
+int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, uint32_t n_arcs, const uint8_t *final_state,
+                      sr_grammar **out);
+void sr_grammar_destroy(sr_grammar *g); /* before sr_destroy of its engine; waits for the device */
+/* Host-only.  Per-level pruning, exact (it never changes an output byte): level l of a call with max_words keeps item (slot,
+ * t, from-set) only if the from-set meets the states reachable from state 0 in exactly l-1 arcs and a final state is
+ * reachable from t in at most max_words - l further arcs; a level without items launches no word pass.  items_per_level
+ * (optional) [max_words]: the items kept at level l at index l-1.  out[0] = scratch bytes per row: (max_frames + 1) *
+ * (max_words * S * 8 + (max_words + 1) * S * 4 + from-sets * 4); out[1] = rows per launch group (what 256 MiB of scratch hold,
+ * 1..65 535); out[2] = kernel launches of one launch group: 2 (init, trace) + per level with items 3 (charge, words, close);
+ * out[3] = the number of distinct from-sets. */
+int sr_grammar_plan(const sr_grammar *g, uint32_t max_words, uint32_t *items_per_level, uint32_t out[4]);
+/* sr_decode_words_dp_dev under the grammar: its arguments, buffers, limits, errors and guarantees (one asynchronous operation
+ * on `stream`, no host synchronisation, no read-back, every record and word row written whole, two runs give the same bytes).
+ * Refused as well, before anything is launched or written (SR_ERR_BAD_ARG): a null grammar, a grammar of another engine, a
+ * grammar older than the engine's store or word map. */
+int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d_mfcc, const uint32_t *d_in_frames,
+                             uint32_t frames_stride, uint32_t n_rows, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost,
+                             uint32_t word_cost, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_decode_grammar_dp(sr_engine *h, const sr_grammar *g, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride,
+                         uint32_t n_rows, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost,
+                         sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost);
+/* whole path on HOST buffers: sr_decode_words_batch under the grammar */
+int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                            const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t max_words, uint32_t n_words_exact,
+                            uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost,
+                            int16_t *mfcc, uint32_t *frm_num, uint32_t *status);
+
 /* ------------------------------------------------------------------ full-DP alignment and word models from many examples
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this
  * section says HOW the two were aligned, and builds word models from many examples on top of that (DTW barycentre
@@ -923,9 +1002,10 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    per call and by sr_align_geometry
  *   "align_marks_global"             the aligner keeps its predecessor marks in global scratch even where they fit the LDS
  *   "chain_chunk_cols"               end frames per kernel chunk of the connected-word decoder (as "spot_chunk_cols"); read per
- *                                    call and by sr_decode_geometry
+ *                                    call and by sr_decode_geometry; the grammar decoder reads it likewise
  *   "chain_rows"                     rows per launch group of the connected-word decoder (default: what 256 MiB of scratch
- *                                    hold); read per call and by sr_decode_geometry
+ *                                    hold); read per call and by sr_decode_geometry; the grammar decoder and sr_grammar_plan
+ *                                    read it likewise
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

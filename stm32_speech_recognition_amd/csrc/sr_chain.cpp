@@ -56,6 +56,13 @@ static int check_stage(const sr_engine *h, const void *mfcc, const void *frames,
     return SR_OK;
 }
 
+int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
+                      uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
+                      const uint32_t *level_cost)
+{
+    return check_stage(h, mfcc, frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
+}
+
 extern "C" {
 
 int sr_decode_geometry(uint32_t tpl_rows, uint32_t max_frames, uint32_t max_words, uint32_t out[4])

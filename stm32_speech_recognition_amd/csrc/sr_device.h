@@ -383,6 +383,29 @@ struct ChainArgs {
 };
 void launch_chain(const ChainArgs &a, hipStream_t s);  // init, max_words x (k_chain_words, k_chain_close), k_chain_trace
 
+// grammar-constrained decoding (k_gram.hip): k_chain's levels over a word network of n_states states.  c is the decoder's
+// argument block with the scratch in the grammar's layout: c.A[row][level 1..max_words][state][max_frames + 1], c.E[row][level
+// 0..max_words][state][max_frames + 1]; C[row][from-set][max_frames + 1] holds the charges of the level in flight.  An item is
+// one word pass: a slot into a target state, charged by a from-set.  lists holds, level by level, the indices of the level's
+// items, the from-sets they use and their target states; lv[l - 1] says where and how many of each this call keeps.
+struct GramItem {
+    uint32_t slot, target, set, reserved;
+};
+struct GramLevel {
+    uint32_t item0, n_items, set0, n_sets, state0, n_states;
+};
+struct GramArgs {
+    ChainArgs c;
+    uint32_t n_states, n_sets, n_items;
+    const unsigned long long *masks;  // [n_sets]: the states of each from-set
+    const GramItem *items;            // [n_items], ascending (slot, target)
+    const uint32_t *lists;
+    const uint8_t *final_state;       // [n_states]
+    uint32_t *C;
+    GramLevel lv[16];
+};
+void launch_gram(const GramArgs &a, hipStream_t s);  // init, per level with items (charge, words, close), trace
+
 // live connected-word decoding (k_chain_live.hip): the levels of k_chain.hip resumed from push to push.  Per channel the session
 // keeps one boundary column per (level, slot), cols[C][max_words][K][tpl_len], and the history A[C][max_words][P] /
 // E[C][max_words + 1][P], P = utt_frames + 1, in ChainArgs' layout with max_frames = utt_frames: after every push positions

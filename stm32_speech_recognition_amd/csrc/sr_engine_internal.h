@@ -193,6 +193,7 @@ struct sr_engine {
     uint32_t word_spw = 1;
     DevBuf<uint32_t> wg_tab;            // order[K] | group_start[n_words + 1] | word_id[n_words] (sr_word_groups) | group_of_slot[K]
     uint32_t wg_K = 0, wg_words = 0;    // the store size the grouping was built for (0: none, or a map of another length)
+    uint64_t word_serial = 0;           // bumped whenever the grouping is rebuilt (a new map or a new store): what a grammar was compiled against (sr_gram.cpp)
     DevBuf<sr_nbest_entry> s_nbest;     // host-buffer forms: device copies of their N-best outputs
     DevBuf<uint32_t> s_nmatched;
     // two-pass rescoring (sr_rescore.cpp): the pair marks [chunk][K ranks][mark stride] and the second-pass score rows [rows][K]
@@ -274,3 +275,10 @@ int launch_spot_stage(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_fra
 // ---- connected-word decoding (sr_chain.cpp) -----------------------------------------------------------------------------------
 // the conditions of sr_decode_words_dp_dev on the engine, the store and the parameters (not on the buffers)
 int check_chain(const sr_engine *h, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost);
+// the conditions of sr_decode_words_dp_dev on its buffers as well (check_chain first)
+int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
+                      uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
+                      const uint32_t *level_cost);
+// ---- grammar-constrained decoding (sr_gram.cpp) -------------------------------------------------------------------------------
+// a grammar of this engine, compiled against its current store and word map
+int check_grammar(const sr_engine *h, const sr_grammar *g);

@@ -1,0 +1,294 @@
+// Grammar-constrained decoding (include/sr_engine.h, "grammar-constrained decoding"): the compile step of a grammar against
+// the engine's store and word map, the checks, the plan (which items each level keeps, the scratch of a row) and the slicing
+// of a call into launch groups.  Per group: k_gram_init, per level that keeps items (k_gram_charge, k_gram_words,
+// k_gram_close), k_gram_trace, everything on the caller's stream.  The whole-path host form is in sr_host.cpp, next to
+// sr_decode_words_batch.
+#include "sr_host_call.h"
+
+#include <map>
+#include <set>
+#include <unordered_set>
+
+using namespace sr;
+
+static constexpr uint32_t kGramMaxStates = 64, kGramMaxArcs = 4096, kGramMaxItems = 1u << 20;
+static constexpr uint32_t kFar = 0xFFFFFFFFu;  // a state from which no final state is reachable
+
+// The compiled form.  Items ascend by (slot, target).  Level l keeps the items whose from-set meets the states reachable from
+// state 0 in exactly l - 1 arcs; its lists are sorted by the distance (in arcs) from the target to a final state, so that
+// what a call with max_words keeps -- distance <= max_words - l -- is a PREFIX of each list, and a call only counts.
+struct sr_grammar {
+    sr_engine *h = nullptr;
+    uint64_t store_serial = 0, word_serial = 0;
+    uint32_t n_states = 0, n_sets = 0, n_items = 0, max_frames = 0, tpl_len = 0;
+    struct Level {
+        uint32_t item0 = 0, set0 = 0, state0 = 0;                                  // where the level's lists start in `lists`
+        uint32_t items[kChainMaxWords + 1] = {}, sets[kChainMaxWords + 1] = {}, states[kChainMaxWords + 1] = {};  // [j]: entries of distance < j
+    } lv[kChainMaxWords];
+    // device: masks u64 [n_sets] | items [n_items] | lists u32 | final u8 [n_states]
+    DevBuf<unsigned long long> blob;
+    size_t items_at = 0, lists_at = 0, final_at = 0;  // offsets in u64 units
+};
+
+namespace {
+
+struct Scratch {
+    size_t a_row, e_row, c_row, row_bytes;
+    uint32_t rows;
+    SpotGeom g;
+};
+
+Scratch gram_plan(const sr_grammar *g, uint32_t max_words)
+{
+    // testing build: the decoder's hooks put seams and small groups into small test shapes
+    const int64_t cols = dev_hook(kHookChainChunk), rows = dev_hook(kHookChainRows);
+    const ChainPlan cp = chain_plan(g->tpl_len, g->max_frames, max_words, cols > 0 ? (uint32_t)std::min<int64_t>(cols, 16383) : 0u, 0u);
+    Scratch p;
+    p.g = cp.g;
+    const size_t P = g->max_frames + 1u;
+    p.a_row = (size_t)max_words * g->n_states * P;
+    p.e_row = (size_t)(max_words + 1u) * g->n_states * P;
+    p.c_row = (size_t)g->n_sets * P;
+    p.row_bytes = p.a_row * 8u + (p.e_row + p.c_row) * 4u;
+    const size_t fit = kChainScratch / p.row_bytes;
+    p.rows = (uint32_t)(fit < 1 ? 1 : fit > kChainMaxRows ? kChainMaxRows : fit);
+    if (rows > 0) p.rows = (uint32_t)std::min<int64_t>(rows, kChainMaxRows);
+    return p;
+}
+
+// what level l (1-based) of a call with max_words keeps
+GramLevel level_of(const sr_grammar *g, uint32_t l, uint32_t max_words)
+{
+    const sr_grammar::Level &v = g->lv[l - 1];
+    const uint32_t j = max_words - l + 1;  // distances 0..max_words - l
+    return GramLevel{v.item0, v.items[j], v.set0, v.sets[j], v.state0, v.states[j]};
+}
+
+}  // namespace
+
+int check_grammar(const sr_engine *h, const sr_grammar *g)
+{
+    if (!g) return fail(SR_ERR_BAD_ARG, "null grammar");
+    if (g->h != h) return fail(SR_ERR_BAD_ARG, "the grammar belongs to another engine");
+    if (g->store_serial != h->store_serial) return fail(SR_ERR_BAD_ARG, "the template store changed since the grammar was compiled");
+    if (g->word_serial != h->word_serial) return fail(SR_ERR_BAD_ARG, "the word map changed since the grammar was compiled");
+    return SR_OK;
+}
+
+extern "C" {
+
+int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, uint32_t n_arcs, const uint8_t *final_state,
+                      sr_grammar **out)
+{
+    if (!h || !arcs || !final_state || !out) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (int rc = check_chain(h, 1, 0, SR_DIS_ERR, 0)) return rc;  // the engine and the store, as every decode call
+    if (n_states < 1 || n_states > kGramMaxStates) return fail(SR_ERR_BAD_ARG, "n_states must be 1..64");
+    if (n_arcs < 1 || n_arcs > kGramMaxArcs) return fail(SR_ERR_BAD_ARG, "n_arcs must be 1..4096");
+    const uint32_t S = n_states, K = h->K;
+    std::vector<uint32_t> label(K);
+    for (uint32_t k = 0; k < K; k++) label[k] = h->word_explicit ? h->word_labels[k] : k / h->word_spw;
+    const std::unordered_set<uint32_t> known(label.begin(), label.end());
+    std::map<std::pair<uint32_t, uint32_t>, uint64_t> from;  // (target, word) -> From as a mask, ordered
+    std::set<std::tuple<uint32_t, uint32_t, uint32_t>> seen;
+    for (uint32_t i = 0; i < n_arcs; i++) {
+        const sr_gram_arc &a = arcs[i];
+        const std::string at = "arc " + std::to_string(i);
+        if (a.from >= S || a.to >= S) return fail(SR_ERR_BAD_ARG, at + ": state index at or above n_states");
+        if (a.reserved) return fail(SR_ERR_BAD_ARG, at + ": reserved must be 0");
+        if (!known.count(a.word)) return fail(SR_ERR_BAD_ARG, at + ": word " + std::to_string(a.word) + " is no label of the word map");
+        if (!seen.emplace(a.from, a.to, a.word).second) return fail(SR_ERR_BAD_ARG, at + ": duplicate arc");
+        from[{a.to, a.word}] |= 1ull << a.from;
+    }
+    uint64_t finals = 0;
+    for (uint32_t s = 0; s < S; s++)
+        if (final_state[s]) finals |= 1ull << s;
+    if (!finals) return fail(SR_ERR_BAD_ARG, "no final state");
+
+    ENTER_DEVICE(h);
+    // slots(w): the VALID slots of the store, which lives on the device
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint8_t> valid(K);
+    std::vector<uint32_t> frames(K);
+    HIP_TRY(hipMemcpy(valid.data(), h->tpl_valid.p, K, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(frames.data(), h->tpl_frames.p, (size_t)K * 4, hipMemcpyDeviceToHost));
+    std::map<uint32_t, std::vector<uint32_t>> slots;
+    for (uint32_t k = 0; k < K; k++)
+        if (valid[k] && frames[k]) slots[label[k]].push_back(k);
+
+    // the distinct from-sets, and the items by ascending (slot, target)
+    std::vector<unsigned long long> masks;
+    std::map<uint64_t, uint32_t> set_of;
+    std::vector<GramItem> items;
+    for (const auto &f : from) {
+        const auto it = set_of.emplace(f.second, (uint32_t)masks.size());
+        if (it.second) masks.push_back(f.second);
+        const auto sl = slots.find(f.first.second);
+        if (sl == slots.end()) continue;  // every slot of the word is invalid: it contributes nothing
+        for (uint32_t k : sl->second) items.push_back(GramItem{k, f.first.first, it.first->second, 0u});
+    }
+    if (items.size() > kGramMaxItems) return fail(SR_ERR_BAD_ARG, "the grammar compiles to more than 2^20 (slot, state) items");
+    std::sort(items.begin(), items.end(), [](const GramItem &a, const GramItem &b) { return a.slot != b.slot ? a.slot < b.slot : a.target < b.target; });
+
+    // reach[i]: the states reachable from state 0 in exactly i arcs; dist[s]: the fewest arcs from s to a final state
+    uint64_t reach[kChainMaxWords] = {1ull};
+    for (uint32_t i = 1; i < kChainMaxWords; i++)
+        for (uint32_t a = 0; a < n_arcs; a++)
+            if (reach[i - 1] >> arcs[a].from & 1) reach[i] |= 1ull << arcs[a].to;
+    std::vector<uint32_t> dist(S, kFar);
+    for (uint32_t s = 0; s < S; s++)
+        if (finals >> s & 1) dist[s] = 0;
+    for (uint32_t round = 1; round < S; round++)
+        for (uint32_t a = 0; a < n_arcs; a++)
+            if (dist[arcs[a].to] != kFar && dist[arcs[a].to] + 1 < dist[arcs[a].from]) dist[arcs[a].from] = dist[arcs[a].to] + 1;
+
+    sr_grammar *g = new sr_grammar();
+    g->h = h;
+    g->store_serial = h->store_serial;
+    g->word_serial = h->word_serial;
+    g->n_states = S;
+    g->n_sets = (uint32_t)masks.size();
+    g->n_items = (uint32_t)items.size();
+    g->max_frames = h->cfg.max_frames;
+    g->tpl_len = h->tpl_rows - 1;
+    std::vector<uint32_t> lists;
+    for (uint32_t l = 1; l <= kChainMaxWords; l++) {
+        sr_grammar::Level &v = g->lv[l - 1];
+        // (distance, index) of the level's items, of the from-sets they use (by their nearest item) and of their targets
+        std::vector<std::pair<uint32_t, uint32_t>> li;
+        std::map<uint32_t, uint32_t> ls, lt;
+        for (uint32_t i = 0; i < items.size(); i++) {
+            const uint32_t d = dist[items[i].target];
+            if (!(masks[items[i].set] & reach[l - 1]) || d > kChainMaxWords - l) continue;
+            li.push_back({d, i});
+            auto s = ls.emplace(items[i].set, d);
+            if (!s.second && d < s.first->second) s.first->second = d;
+            lt.emplace(items[i].target, d);
+        }
+        auto emit = [&lists](std::vector<std::pair<uint32_t, uint32_t>> e, uint32_t *start, uint32_t *below) {
+            std::sort(e.begin(), e.end());
+            *start = (uint32_t)lists.size();
+            for (const auto &x : e) lists.push_back(x.second);
+            for (uint32_t j = 0; j <= kChainMaxWords; j++)
+                below[j] = (uint32_t)(std::lower_bound(e.begin(), e.end(), std::make_pair(j, 0u)) - e.begin());
+        };
+        std::vector<std::pair<uint32_t, uint32_t>> es, et;
+        for (const auto &s : ls) es.push_back({s.second, s.first});
+        for (const auto &t : lt) et.push_back({t.second, t.first});
+        emit(li, &v.item0, v.items);
+        emit(es, &v.set0, v.sets);
+        emit(et, &v.state0, v.states);
+    }
+
+    g->items_at = masks.size();
+    g->lists_at = g->items_at + items.size() * 2;
+    g->final_at = g->lists_at + (lists.size() + 1) / 2;
+    std::vector<unsigned long long> blob(g->final_at + (S + 7) / 8, 0ull);
+    std::memcpy(blob.data(), masks.data(), masks.size() * 8);
+    if (!items.empty()) std::memcpy(blob.data() + g->items_at, items.data(), items.size() * sizeof(GramItem));
+    if (!lists.empty()) std::memcpy(blob.data() + g->lists_at, lists.data(), lists.size() * 4);
+    for (uint32_t s = 0; s < S; s++) ((uint8_t *)(blob.data() + g->final_at))[s] = final_state[s] ? 1 : 0;
+    int rc = g->blob.reserve(blob.size());
+    if (!rc) {
+        const hipError_t e = hipMemcpy(g->blob.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(SR_ERR_HIP, std::string("grammar upload: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        g->blob.release();
+        delete g;
+        return rc;
+    }
+    *out = g;
+    return SR_OK;
+}
+
+void sr_grammar_destroy(sr_grammar *g)
+{
+    if (!g) return;
+    DeviceGuard guard;
+    if (guard.enter(g->h->device) == SR_OK) (void)hipDeviceSynchronize();  // a decode call in flight may still read the lists
+    g->blob.release();
+    delete g;
+}
+
+int sr_grammar_plan(const sr_grammar *g, uint32_t max_words, uint32_t *items_per_level, uint32_t out[4])
+{
+    if (!g || !out) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (max_words < 1 || max_words > kChainMaxWords) return fail(SR_ERR_BAD_ARG, "max_words must be 1..16");
+    const Scratch p = gram_plan(g, max_words);
+    uint32_t launches = 2;
+    for (uint32_t l = 1; l <= max_words; l++) {
+        const GramLevel lv = level_of(g, l, max_words);
+        if (items_per_level) items_per_level[l - 1] = lv.n_items;
+        if (lv.n_items) launches += 3;
+    }
+    out[0] = (uint32_t)std::min<size_t>(p.row_bytes, 0xFFFFFFFFu);
+    out[1] = p.rows;
+    out[2] = launches;
+    out[3] = g->n_sets;
+    return SR_OK;
+}
+
+int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d_mfcc, const uint32_t *d_in_frames,
+                             uint32_t frames_stride, uint32_t n_rows, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost,
+                             uint32_t word_cost, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost, void *stream)
+{
+    int rc = check_chain_stage(h, d_mfcc, d_in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec, d_words,
+                               d_level_cost);
+    if (rc || (rc = check_grammar(h, g)) || !n_rows) return rc;
+    ENTER_DEVICE(h);
+    const hipStream_t s = (hipStream_t)stream;
+    const Scratch p = gram_plan(g, max_words);
+    const uint32_t per = std::min(p.rows, n_rows);
+    if ((rc = order_after_scratch_users(h, s))) return rc;  // the keys, prefix costs and charges are the engine's
+    if ((rc = h->s_ch_a.reserve(per * p.a_row)) || (rc = h->s_ch_e.reserve(per * (p.e_row + p.c_row)))) return rc;
+    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    GramArgs a{};
+    a.n_states = g->n_states;
+    a.n_sets = g->n_sets;
+    a.n_items = g->n_items;
+    a.masks = g->blob.p;
+    a.items = (const GramItem *)(g->blob.p + g->items_at);
+    a.lists = (const uint32_t *)(g->blob.p + g->lists_at);
+    a.final_state = (const uint8_t *)(g->blob.p + g->final_at);
+    a.C = h->s_ch_e.p + per * p.e_row;  // behind the prefix costs of the largest group
+    for (uint32_t l = 1; l <= max_words; l++) a.lv[l - 1] = level_of(g, l, max_words);
+    for (uint32_t r0 = 0; r0 < n_rows; r0 += per) {  // the groups follow each other on s: one scratch serves them all
+        a.c = ChainArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
+                        std::min(per, n_rows - r0), h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,
+                        g->tpl_len, p.g.chunk_cols, p.g.n_chunks, max_words, n_words_exact, skip_cost, word_cost, h->s_ch_a.p,
+                        h->s_ch_e.p, t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0,
+                        d_words + (size_t)r0 * max_words, d_level_cost ? d_level_cost + (size_t)r0 * max_words : nullptr};
+        launch_gram(a, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return mark_scratch_user(h, s);
+}
+
+int sr_decode_grammar_dp(sr_engine *h, const sr_grammar *g, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride,
+                         uint32_t n_rows, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost,
+                         sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost)
+{
+    int rc = check_chain_stage(h, mfcc, in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
+    if (rc || (rc = check_grammar(h, g)) || !n_rows) return rc;
+    ENTER_HOST_CALL(h);
+    const size_t n_w = (size_t)n_rows * max_words;
+    TmpDevBuf<sr_chain_rec> d_rec;
+    TmpDevBuf<sr_chain_word> d_words;
+    TmpDevBuf<uint32_t> d_lc;
+    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_rec.reserve(n_rows)) ||
+        (rc = d_words.reserve(n_w)) || (level_cost && (rc = d_lc.reserve(n_w))))
+        return rc;
+    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
+    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
+    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
+    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
+    if ((rc = sr_decode_grammar_dp_dev(h, g, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec.p,
+                                       d_words.p, level_cost ? d_lc.p : nullptr, nullptr)))
+        return rc;
+    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
+    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
+    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
+    return SR_OK;
+}
+
+}  // extern "C"

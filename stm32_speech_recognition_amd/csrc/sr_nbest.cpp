@@ -45,6 +45,7 @@ int regroup_words(sr_engine *h, bool drained)
 {
     h->wg_K = 0;
     h->wg_words = 0;
+    h->word_serial++;
     if (!h->K || (h->word_explicit && h->word_labels.size() != h->K)) return SR_OK;
     std::vector<uint32_t> order, start, ids;
     if (int rc = word_groups(h->word_explicit ? h->word_labels.data() : nullptr, h->K, h->word_spw, order, start, ids)) return rc;

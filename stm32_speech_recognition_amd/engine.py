@@ -665,6 +665,61 @@ class Engine:
                                                  _vp(out["status"])))
         return out
 
+    # ---- grammar-constrained decoding ---------------------------------------------------------------------
+    def grammar(self, n_states, arcs, final):
+        """sr_grammar_create: a Grammar compiled against the current store and word map.  States 0..n_states - 1, state 0
+        the start; arcs = (from, to, word) triples, word a label of the word map; final = one flag per state.  The three
+        grammar_* helpers return exactly these arguments: eng.grammar(*grammar_sequence([...]))."""
+        return Grammar(self, n_states, arcs, final)
+
+    def decode_grammar(self, gram, mfcc, frames, max_words=8, n_words=0, skip_cost=None, word_cost=0):
+        """decode_words() under a Grammar (sr_decode_grammar_dp): the cheapest parse among the word sequences the grammar
+        accepts; the word rows' `reserved` holds the grammar state after each word."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, max_words), dtype=CHAIN_WORD_DTYPE)
+        lc = np.zeros((n, max_words), dtype=np.uint32)
+        self._check(self.L.sr_decode_grammar_dp(self.h, gram.g, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n),
+                                                C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)),
+                                                C.c_uint32(word_cost), _vp(rec), _vp(words), _vp(lc)))
+        return rec, words, lc
+
+    def decode_grammar_dev(self, gram, mfcc, frames, rec, words, level_cost=None, max_words=8, n_words=0, skip_cost=None,
+                           word_cost=0, frames_stride=1, stream=None):
+        """decode_words_dev() under a Grammar (sr_decode_grammar_dp_dev): the same tensors, asynchronous on `stream`."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and words.numel() == n * max_words * 8
+        assert level_cost is None or (level_cost.is_contiguous() and level_cost.numel() == n * max_words)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_decode_grammar_dp_dev(self.h, gram.g, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                    C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)),
+                                                    C.c_uint32(word_cost), _vp(rec), _vp(words), _vp(level_cost), C.c_void_p(stream)))
+        return rec, words, level_cost
+
+    def decode_grammar_pcm(self, gram, pcm, start, end, mid, max_words=8, n_words=0, skip_cost=None, word_cost=0):
+        """decode_words_pcm() under a Grammar (sr_decode_grammar_batch): the same dict."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        out = dict(rec=np.zeros(B, dtype=CHAIN_REC_DTYPE), words=np.zeros((B, max_words), dtype=CHAIN_WORD_DTYPE),
+                   level_cost=np.zeros((B, max_words), dtype=np.uint32),
+                   mfcc=np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16), frm_num=np.zeros(B, dtype=np.uint32),
+                   status=np.zeros(B, dtype=np.uint32))
+        self._check(self.L.sr_decode_grammar_batch(self.h, gram.g, _vp(pcm), C.c_uint64(S), C.c_uint32(S), C.c_uint32(B), _vp(start),
+                                                   _vp(end), _vp(mid), C.c_uint32(max_words), C.c_uint32(n_words),
+                                                   C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(out["rec"]),
+                                                   _vp(out["words"]), _vp(out["level_cost"]), _vp(out["mfcc"]), _vp(out["frm_num"]),
+                                                   _vp(out["status"])))
+        return out
+
     def decode_live(self, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
         """sr_decode_live_open: a DecodeSession of n_channels channels of at most utt_frames frames each.  mid None: a feature
         session (chunk_max in frames); mid uint32 [n_channels]: a PCM session (chunk_max in samples)."""
@@ -1258,6 +1313,67 @@ class SpotSession:
         wins, n = np.zeros(max(len(ch), 1), dtype=SPOT_WIN_DTYPE), C.c_uint32(0)
         self.eng._check(self.L.sr_spot_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(hits), _vp(wins), C.byref(n)))
         return dict(hits=hits[:n.value], wins=wins[:n.value], n_rows=n.value)
+
+
+GRAM_ARC_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("word", "<u4"), ("reserved", "<u4")])  # sr_gram_arc
+
+
+def grammar_any(labels):
+    """The anchor grammar: one state, final, one loop per label -- every sequence of words, byte for byte decode_words().
+    Returns (n_states, arcs, final) for Engine.grammar()."""
+    return 1, [(0, 0, int(w)) for w in dict.fromkeys(labels)], [1]
+
+
+def grammar_sequence(positions, optional_tail=False):
+    """A linear grammar: word i of a parse is one of the labels positions[i].  The last state is final; optional_tail makes
+    every state past the first word final too (the sequence may stop early).  Returns (n_states, arcs, final)."""
+    n = len(positions)
+    arcs = [(i, i + 1, int(w)) for i, ws in enumerate(positions) for w in dict.fromkeys(ws)]
+    return n + 1, arcs, [int(i == n or (optional_tail and i >= 1)) for i in range(n + 1)]
+
+
+def grammar_word_pairs(labels, allowed_pairs, first=None, last=None):
+    """A word-pair grammar: one state per word (1 + its index in labels) plus the start.  A parse may begin with a word of
+    `first`, b may follow a when (a, b) is in allowed_pairs, and it may end after a word of `last` (None: any word).
+    Returns (n_states, arcs, final)."""
+    labels = list(dict.fromkeys(int(w) for w in labels))
+    st = {w: 1 + i for i, w in enumerate(labels)}
+    arcs = [(0, st[w], w) for w in labels if first is None or w in first]
+    arcs += [(st[a], st[b], int(b)) for a, b in dict.fromkeys((int(a), int(b)) for a, b in allowed_pairs)]
+    return 1 + len(labels), arcs, [0] + [int(last is None or w in last) for w in labels]
+
+
+class Grammar:
+    """One sr_grammar handle: a word network compiled against its engine's store and word map (Engine.grammar).  Setting
+    the templates or the word map again makes it stale: decode calls then raise until a new one is compiled."""
+
+    def __init__(self, eng, n_states, arcs, final):
+        self.eng, self.L, self.g = eng, eng.L, None
+        a = np.zeros(len(arcs), dtype=GRAM_ARC_DTYPE)
+        for i, arc in enumerate(arcs):
+            a[i] = tuple(arc) + (0,) * (4 - len(arc))
+        final = np.ascontiguousarray(final, dtype=np.uint8)
+        assert len(final) == n_states
+        g = C.c_void_p()
+        eng._check(self.L.sr_grammar_create(eng.h, C.c_uint32(n_states), _vp(a), C.c_uint32(len(a)), _vp(final), C.byref(g)))
+        self.g, self.n_states = g, n_states
+
+    def plan(self, max_words=8):
+        """sr_grammar_plan (host only): dict(row_bytes, rows, launches, from_sets, items_per_level [max_words])."""
+        items, out = np.zeros(max_words, np.uint32), (C.c_uint32 * 4)()
+        self.eng._check(self.L.sr_grammar_plan(self.g, C.c_uint32(max_words), _vp(items), out))
+        return dict(row_bytes=out[0], rows=out[1], launches=out[2], from_sets=out[3], items_per_level=[int(i) for i in items])
+
+    def close(self):
+        if getattr(self, "g", None) and getattr(self.eng, "h", None):
+            self.L.sr_grammar_destroy(self.g)  # before sr_destroy of its engine
+        self.g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def decode_live_geometry(tpl_rows, K, max_words, utt_frames, chunk_max):
