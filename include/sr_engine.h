@@ -770,7 +770,7 @@ int sr_decode_live_end(sr_decode_live *l, const uint32_t *channels, uint32_t n_c
  * therefore costs the K passes per level of the unconstrained decoder.
  * Anchor: S = 1, final_state[0] = 1 and one arc (0, 0, w) per label give, byte for byte, what sr_decode_words_dp writes
  * (reserved = 0 included).
- * Out of scope: a live, push-by-push grammar session; arc weights; epsilon arcs; more than 64 states. */
+ * Out of scope: arc weights; epsilon arcs; more than 64 states.  (The push-by-push session is the next section.) */
 typedef struct sr_gram_arc { /* 16 bytes */
     uint32_t from;
     uint32_t to;
@@ -813,6 +813,74 @@ int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *p
                             const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t max_words, uint32_t n_words_exact,
                             uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost,
                             int16_t *mfcc, uint32_t *frm_num, uint32_t *status);
+
+/* ------------------------------------------------------------------ live grammar-constrained decoding: grammar state carried between pushes
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The live connected-word session under a grammar: a session takes the frames of
+ * n_channels channels as they arrive, keeps per (channel, level, kept item) ONE column of the recurrence and per channel the
+ * A / E history of every grammar state on the device between calls, and after every push says how everything heard so far
+ * parses UNDER THE GRAMMAR.  No existing call, record, score or byte changes.
+ * THE RULE: let Y_c be every feature frame pushed to channel c since it was opened or last ended, N = |Y_c| <= utt_frames
+ * (1..16 383).  Every push emits one row for every channel with n[c] > 0, by ascending channel: an sr_chain_rec, max_words x
+ * sr_chain_word and optionally level_cost[max_words], labelled by an sr_chain_live_row.  The row is, byte for byte, what the
+ * grammar-constrained decoding section defines for Y_c as ONE row of N frames under the session's grammar, max_words,
+ * n_words_exact, skip_cost and word_cost -- whatever the chunking; sr_chain_word.reserved (the state after the word) and
+ * level_cost[l-1] = L_l included.  Whenever an engine's max_frames >= N it therefore equals what sr_decode_grammar_dp[_dev]
+ * writes for that row.  Ties keep their rule: smallest start, then slot, then fewest words, then smallest final state, then
+ * smallest source state.  Why it is exact: A_l(p,t) and E_l(p,t) depend on frames < p only; column x of an item needs column
+ * x-1 and the charge at x, a minimum over E_{l-1}(x, .); count, end state and trace read A, E and N.
+ * PCM sessions (mid given at open) frame the samples exactly as the live connected-word decoding section does; a row is
+ * emitted for n[c] > 0 whether or not a frame was completed, and while there are at most max_frames frames the row equals
+ * sr_decode_grammar_batch(X_c, 1, R, mid[c]).
+ * A session is bound to ONE grammar at a time (one per dialogue state: sr_gram_live_set_grammar switches it between
+ * recordings).  A grammar is stale once the store or the word map has been set after sr_grammar_create: a push is then
+ * refused (SR_ERR_BAD_ARG), sr_gram_live_end drops the listed recordings (each ends with the SR_CH_NONE record), and
+ * sr_gram_live_set_grammar with a fresh grammar puts the session back to work.  Refusals, HIP failures, stream ordering and
+ * the engine's one-caller-at-a-time rule as in the live connected-word decoding section.  Teardown: the session before its
+ * grammar, the grammar before the engine.
+ * Out of scope: a grammar per channel; arc weights; epsilon arcs; more than 64 states; a history compacted to each level's
+ * target states (the dense [S] history is what sr_gram_live_geometry reports); splitting a push along time. */
+typedef struct sr_gram_live sr_gram_live;
+/* host-only, no device: out[0] = device state bytes per channel, saturating: columns * tpl_rows * 16 + (utt_frames + 1) * S *
+ * (max_words * 8 + (max_words + 1) * 4), tpl_rows the longest template of the store the grammar was compiled against; out[1] =
+ * the longest template that fits (sr_spot_geometry's out[2]); out[2] = the kernel launches of one feature push, 2 (init,
+ * trace) + 2 (words, close) per level that keeps items; out[3] = columns, the sum over the levels 1..max_words of the items
+ * sr_grammar_plan keeps there: a level stores boundary columns only for the items it sweeps.  max_words 1..16, utt_frames
+ * 1..16 383, chunk_max 1..utt_frames. */
+int sr_gram_live_geometry(const sr_grammar *g, uint32_t max_words, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[4]);
+/* sr_decode_live_open under g: its arguments, limits and errors; SR_ERR_BAD_ARG as well for a null grammar, a grammar of
+ * another engine, a grammar older than the engine's store or word map. */
+int sr_gram_live_open(sr_engine *h, const sr_grammar *g, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames,
+                      uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid,
+                      sr_gram_live **out);
+void sr_gram_live_close(sr_gram_live *l); /* before sr_grammar_destroy of its grammar; waits for the session's last push */
+/* The grammar of the next dialogue state, or a fresh one in the place of a stale one: accepted only while every channel is
+ * empty (freshly opened or ended), otherwise SR_ERR_BAD_ARG and the session stays as it was; refused like sr_gram_live_open
+ * for the grammar itself.  Lays the columns and the history out for g: what has to grow is allocated aside and swapped in
+ * after the last allocation, so an allocation failure (SR_ERR_HIP) leaves the session on its old grammar, buffers included. */
+int sr_gram_live_set_grammar(sr_gram_live *l, const sr_grammar *g);
+/* The four pushes: argument lists, alignment rules, compact outputs, host-filled rows / *n_rows, stream ordering by event and
+ * the refusal list of sr_decode_live_push_dev, _push, _push_pcm_dev and _push_pcm.  The device forms are ONE asynchronous
+ * operation on `stream`, no host synchronisation, no read-back.  A call refused for its arguments writes nothing and changes
+ * no state.  Refused as well (SR_ERR_BAD_ARG): any push while the session's grammar is stale. */
+int sr_gram_live_push_dev(sr_gram_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                          uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost,
+                          sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_gram_live_push(sr_gram_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                      uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, sr_chain_live_row *rows,
+                      uint32_t *n_rows);
+int sr_gram_live_push_pcm_dev(sr_gram_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                              uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost,
+                              sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_gram_live_push_pcm(sr_gram_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                          uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost,
+                          sr_chain_live_row *rows, uint32_t *n_rows);
+/* sr_decode_live_end under the grammar: HOST outputs, one row per DISTINCT listed channel at its first mention, the parse of
+ * everything pushed to it; waits for the device; each listed channel is then as freshly opened.  With a stale grammar the
+ * listed recordings are dropped: each gets the SR_CH_NONE record and frames = 0, and the channels are empty afterwards --
+ * whatever the engine's current store and word map are (a map that does not fit the store does not refuse this call: nothing
+ * of either is read), so a session can always be emptied for sr_gram_live_set_grammar. */
+int sr_gram_live_end(sr_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
+                     uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows);
 
 /* ------------------------------------------------------------------ full-DP alignment and word models from many examples
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this

@@ -440,6 +440,23 @@ struct ChainLiveArgs {
 void launch_chain_live(const ChainLiveArgs &a, hipStream_t s);        // init, max_words x (words, close), trace
 void launch_chain_live_trace(const ChainLiveArgs &a, hipStream_t s);  // the trace alone (sr_decode_live_end)
 
+// live grammar-constrained decoding (k_gram_live.hip): k_gram's levels resumed from push to push.  c is the live decoder's
+// argument block with the history in the grammar's layout, c.A[C][max_words][state][P] and c.E[C][max_words + 1][state][P],
+// and c.cols[C][columns][tpl_len]: one boundary column per item a level keeps, level l's first at col_off[l - 1], in the order
+// of the level's item list.  c.K is not read.  There is no row of charges: a sweep takes the minimum over the from-set itself.
+struct GramLiveArgs {
+    ChainLiveArgs c;
+    uint32_t n_states, n_items, columns;
+    const unsigned long long *masks;  // [n_sets]: the states of each from-set
+    const GramItem *items;            // [n_items], ascending (slot, target)
+    const uint32_t *lists;
+    const uint8_t *final_state;       // [n_states]
+    GramLevel lv[16];
+    uint32_t col_off[16];
+};
+void launch_gram_live(const GramLiveArgs &a, hipStream_t s);        // init, per level with items (words, close), trace
+void launch_gram_live_trace(const GramLiveArgs &a, hipStream_t s);  // the trace alone (no new frame, sr_gram_live_end)
+
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the
 // marks are indexed by the pair of the launch.

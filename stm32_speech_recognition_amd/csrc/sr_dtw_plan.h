@@ -156,6 +156,7 @@ const char *align_allow_lds(uint32_t bytes);
 const char *chain_allow_lds(uint32_t bytes);
 const char *chain_live_allow_lds(uint32_t bytes);
 const char *gram_allow_lds(uint32_t bytes);
+const char *gram_live_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

@@ -14,22 +14,7 @@ using namespace sr;
 static constexpr uint32_t kGramMaxStates = 64, kGramMaxArcs = 4096, kGramMaxItems = 1u << 20;
 static constexpr uint32_t kFar = 0xFFFFFFFFu;  // a state from which no final state is reachable
 
-// The compiled form.  Items ascend by (slot, target).  Level l keeps the items whose from-set meets the states reachable from
-// state 0 in exactly l - 1 arcs; its lists are sorted by the distance (in arcs) from the target to a final state, so that
-// what a call with max_words keeps -- distance <= max_words - l -- is a PREFIX of each list, and a call only counts.
-struct sr_grammar {
-    sr_engine *h = nullptr;
-    uint64_t store_serial = 0, word_serial = 0;
-    uint32_t n_states = 0, n_sets = 0, n_items = 0, max_frames = 0, tpl_len = 0;
-    struct Level {
-        uint32_t item0 = 0, set0 = 0, state0 = 0;                                  // where the level's lists start in `lists`
-        uint32_t items[kChainMaxWords + 1] = {}, sets[kChainMaxWords + 1] = {}, states[kChainMaxWords + 1] = {};  // [j]: entries of distance < j
-    } lv[kChainMaxWords];
-    // device: masks u64 [n_sets] | items [n_items] | lists u32 | final u8 [n_states]
-    DevBuf<unsigned long long> blob;
-    size_t items_at = 0, lists_at = 0, final_at = 0;  // offsets in u64 units
-};
-
+// (the compiled form, struct sr_grammar, is in sr_engine_internal.h: the live session of sr_gram_live.cpp reads it too)
 namespace {
 
 struct Scratch {
@@ -56,15 +41,15 @@ Scratch gram_plan(const sr_grammar *g, uint32_t max_words)
     return p;
 }
 
+}  // namespace
+
 // what level l (1-based) of a call with max_words keeps
-GramLevel level_of(const sr_grammar *g, uint32_t l, uint32_t max_words)
+GramLevel gram_level_of(const sr_grammar *g, uint32_t l, uint32_t max_words)
 {
     const sr_grammar::Level &v = g->lv[l - 1];
     const uint32_t j = max_words - l + 1;  // distances 0..max_words - l
     return GramLevel{v.item0, v.items[j], v.set0, v.sets[j], v.state0, v.states[j]};
 }
-
-}  // namespace
 
 int check_grammar(const sr_engine *h, const sr_grammar *g)
 {
@@ -217,7 +202,7 @@ int sr_grammar_plan(const sr_grammar *g, uint32_t max_words, uint32_t *items_per
     const Scratch p = gram_plan(g, max_words);
     uint32_t launches = 2;
     for (uint32_t l = 1; l <= max_words; l++) {
-        const GramLevel lv = level_of(g, l, max_words);
+        const GramLevel lv = gram_level_of(g, l, max_words);
         if (items_per_level) items_per_level[l - 1] = lv.n_items;
         if (lv.n_items) launches += 3;
     }
@@ -251,7 +236,7 @@ int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d
     a.lists = (const uint32_t *)(g->blob.p + g->lists_at);
     a.final_state = (const uint8_t *)(g->blob.p + g->final_at);
     a.C = h->s_ch_e.p + per * p.e_row;  // behind the prefix costs of the largest group
-    for (uint32_t l = 1; l <= max_words; l++) a.lv[l - 1] = level_of(g, l, max_words);
+    for (uint32_t l = 1; l <= max_words; l++) a.lv[l - 1] = gram_level_of(g, l, max_words);
     for (uint32_t r0 = 0; r0 < n_rows; r0 += per) {  // the groups follow each other on s: one scratch serves them all
         a.c = ChainArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                         std::min(per, n_rows - r0), h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,

@@ -1,0 +1,381 @@
+// Live grammar-constrained decoding (include/sr_engine.h, "live grammar-constrained decoding"): sr_decode_live.cpp under a
+// grammar.  Feature frames or samples arrive in pushes; per (channel, level, kept item) the boundary column and per channel
+// the A / E history of every grammar state stay on the device between calls (k_gram_live.hip).  OPT-IN EXTENSION, NO
+// REFERENCE COUNTERPART.
+//
+// The host knows every count (the decoder's mirror, sr_decode_live_plan.h) and every column offset (sr_gram_live_plan.h):
+// nothing is read back to size or to label an output.  Refusals come in the order plan, inputs, outputs, device; the checks,
+// the plan upload, the PCM front end and the ordering of pushes are the live decoder's own (sr_decode_live_host.h).
+#include "sr_decode_live_host.h"
+#include "sr_gram_live_plan.h"
+
+using namespace sr;
+
+struct sr_gram_live {
+    sr_engine *h = nullptr;
+    const sr_grammar *g = nullptr;        // the grammar of the current dialogue state (sr_gram_live_set_grammar switches it)
+    DecodeLiveMirror m;                   // bound to kGramLiveBound throughout: the grammar carries the store and the word map
+    uint32_t max_words = 0, n_words_exact = 0, skip_cost = 0, word_cost = 0;
+    std::vector<uint32_t> mid;            // PCM sessions: the channels' mid values
+    // what g keeps per level of max_words, and where each level's columns start
+    GramLevel lv[kChainMaxWords] = {};
+    GramLiveLayout lay;
+    uint32_t tpl_len = 0;
+    DevBuf<ulonglong2> cols;              // [C][columns][tpl_len]
+    DevBuf<unsigned long long> A;         // [C][max_words][S][utt_frames + 1]
+    DevBuf<uint32_t> E;                   // [C][max_words + 1][S][utt_frames + 1]
+    DevBuf<SpotLiveChan> d_chan;
+    // PCM sessions: kept samples, the rows [kept | chunk], their records and the features of one push
+    DevBuf<uint16_t> keep, stage;
+    DevBuf<sr_vad_rec> recs;
+    DevBuf<int16_t> feat;
+    uint32_t keep_stride = 0;
+    uint64_t stage_stride = 0;
+    hipEvent_t ev_last = nullptr;         // end of the last push (sr_gram_live_end / _close / _set_grammar wait for it)
+    hipStream_t last_stream = nullptr;    // ... and the stream it ran on: a push on another stream runs behind it
+    bool pending = false;
+};
+
+namespace {
+
+constexpr uint32_t kGramLiveMaxChannels = 65535u;  // a grid dimension
+constexpr uint32_t kGramLiveMaxFrames = 16383u;    // the u32 cost bound and the 14-bit start of a key
+
+int check_store(const sr_gram_live *l) { return check_chain(l->h, l->max_words, l->n_words_exact, l->skip_cost, l->word_cost); }  // sr_gram_live_set_grammar
+
+bool stale(const sr_gram_live *l, std::string *why)
+{
+    return gram_live_stale(l->g->store_serial, l->g->word_serial, l->h->store_serial, l->h->word_serial, why);
+}
+
+// room for `count` elements behind `cur`: a NEW buffer in `fresh` when cur is too small, cur itself untouched (DevBuf::reserve
+// would free it first)
+template <typename T>
+int grow_aside(const DevBuf<T> &cur, DevBuf<T> &fresh, size_t count)
+{
+    return count > cur.n ? fresh.reserve(count) : SR_OK;
+}
+template <typename T>
+void take(DevBuf<T> &cur, DevBuf<T> &fresh)
+{
+    if (!fresh.p) return;
+    std::swap(cur, fresh);
+    fresh.release();  // the old buffer: nothing of the session is in flight (a fresh session, or sr_gram_live_set_grammar has waited)
+}
+
+// The columns and the history laid out for g, then g adopted.  Whatever has to grow is allocated ASIDE, and the session's
+// buffers, layout and grammar change only after the last allocation has succeeded: a failed allocation frees what was
+// allocated aside and leaves the session exactly as it was, on its old grammar.
+int adopt(sr_gram_live *l, const sr_grammar *g)
+{
+    GramLevel lv[kChainMaxWords] = {};
+    uint32_t items[kChainMaxWords] = {};
+    for (uint32_t i = 1; i <= l->max_words; i++) {
+        lv[i - 1] = gram_level_of(g, i, l->max_words);
+        items[i - 1] = lv[i - 1].n_items;
+    }
+    const GramLiveLayout lay = gram_live_layout(items, l->max_words);
+    const size_t C = l->m.C, P = (size_t)l->m.utt_frames + 1, S = g->n_states;
+    TmpDevBuf<ulonglong2> cols;
+    TmpDevBuf<unsigned long long> A;
+    TmpDevBuf<uint32_t> E;
+    if (int rc = grow_aside(l->cols, cols, C * lay.columns * g->tpl_len)) return rc;
+    if (int rc = grow_aside(l->A, A, C * l->max_words * S * P)) return rc;
+    if (int rc = grow_aside(l->E, E, C * (l->max_words + 1u) * S * P)) return rc;
+    take<ulonglong2>(l->cols, cols);
+    take<unsigned long long>(l->A, A);
+    take<uint32_t>(l->E, E);
+    std::copy(lv, lv + kChainMaxWords, l->lv);
+    l->lay = lay;
+    l->tpl_len = g->tpl_len;
+    l->g = g;
+    return SR_OK;
+}
+
+// a push is refused for a stale grammar first, then for its counts
+int plan_push(const sr_gram_live *l, const uint32_t *n, uint32_t n_all, DecodeLivePlan *pl)
+{
+    std::string why;
+    if (stale(l, &why)) return fail(SR_ERR_BAD_ARG, why);
+    if (!decode_live_plan(l->m, kGramLiveBound, n, n_all, pl, &why)) return fail(SR_ERR_BAD_ARG, why);
+    return SR_OK;
+}
+
+GramLiveArgs live_args(const sr_gram_live *l, const int16_t *d_mfcc, uint64_t row_stride, sr_chain_rec *d_rec, sr_chain_word *d_words,
+                       uint32_t *d_level_cost)
+{
+    const sr_engine *h = l->h;
+    const sr_grammar *g = l->g;
+    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    GramLiveArgs a{};
+    a.c = ChainLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->m.C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride, l->tpl_len,
+                        l->m.utt_frames + 1u, l->max_words, l->n_words_exact, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p,
+                        t ? t + h->K + 2 * (size_t)h->wg_words + 1 : nullptr, t ? t + h->K + h->wg_words + 1 : nullptr, d_rec, d_words,
+                        d_level_cost};  // (no grouping: only a dropped recording is traced then, which reads neither)
+    a.n_states = g->n_states;
+    a.n_items = g->n_items;
+    a.columns = l->lay.columns;
+    a.masks = g->blob.p;
+    a.items = (const GramItem *)(g->blob.p + g->items_at);
+    a.lists = (const uint32_t *)(g->blob.p + g->lists_at);
+    a.final_state = (const uint8_t *)(g->blob.p + g->final_at);
+    std::copy(l->lv, l->lv + kChainMaxWords, a.lv);
+    std::copy(l->lay.col_off, l->lay.col_off + kChainMaxWords, a.col_off);
+    return a;
+}
+
+// the levels over the new frames of every channel and the trace of every emitting one, enqueued on s
+int launch_push(sr_gram_live *l, const DecodeLivePlan &pl, const int16_t *d_mfcc, uint64_t row_stride, sr_chain_rec *d_rec,
+                sr_chain_word *d_words, uint32_t *d_level_cost, hipStream_t s)
+{
+    if (!pl.rows) return SR_OK;
+    const GramLiveArgs a = live_args(l, d_mfcc, row_stride, d_rec, d_words, d_level_cost);
+    if (pl.max_frames) launch_gram_live(a, s);
+    else launch_gram_live_trace(a, s);  // (PCM) samples, but no new frame: the parse so far again
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sr_gram_live_geometry(const sr_grammar *g, uint32_t max_words, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[4])
+{
+    if (!g || !out || max_words < 1 || max_words > kChainMaxWords || !utt_frames || utt_frames > kGramLiveMaxFrames || !chunk_max ||
+        chunk_max > utt_frames)
+        return fail(SR_ERR_BAD_ARG, "null / zero argument, or one outside its range");
+    uint32_t items[kChainMaxWords] = {};
+    for (uint32_t l = 1; l <= max_words; l++) items[l - 1] = gram_level_of(g, l, max_words).n_items;
+    const GramLiveLayout lay = gram_live_layout(items, max_words);
+    const LdsBudget mi355x;  // no device: MI355X's figures
+    out[0] = gram_live_state_bytes(lay.columns, g->tpl_len, g->n_states, max_words, utt_frames);
+    out[1] = spot_max_tpl(mi355x);
+    out[2] = lay.launches();
+    out[3] = lay.columns;
+    return SR_OK;
+}
+
+int sr_gram_live_open(sr_engine *h, const sr_grammar *g, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames, uint32_t max_words,
+                      uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid, sr_gram_live **out)
+{
+    if (!h || !out) return fail(SR_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = check_chain(h, max_words, n_words_exact, skip_cost, word_cost)) return rc;
+    if (int rc = check_grammar(h, g)) return rc;
+    if (!n_channels || n_channels > kGramLiveMaxChannels || !utt_frames || utt_frames > kGramLiveMaxFrames)
+        return fail(SR_ERR_BAD_ARG, "n_channels not in 1..65535 / utt_frames not in 1..16383");
+    if (!chunk_max) return fail(SR_ERR_BAD_ARG, "chunk_max 0");
+    if (mid) {
+        if (((uint64_t)chunk_max + h->hop - 1) / h->hop > std::min(h->cfg.max_frames, utt_frames))
+            return fail(SR_ERR_BAD_ARG, "a push of chunk_max samples could complete more than min(max_frames, utt_frames) frames");
+        for (uint32_t c = 0; c < n_channels; c++)
+            if (mid[c] > 0xFFFFu) return fail(SR_ERR_BAD_ARG, "mid exceeds the u16 sample range");
+        if (int rc = check_batch(h, n_channels)) return rc;
+    } else if (chunk_max > utt_frames) {
+        return fail(SR_ERR_BAD_ARG, "chunk_max not in 1..utt_frames");
+    }
+    ENTER_DEVICE(h);
+    sr_gram_live *l = new sr_gram_live();
+    l->h = h;
+    l->m.open(n_channels, kGramLiveBound);
+    l->m.chunk_max = chunk_max;
+    l->m.utt_frames = utt_frames;
+    l->m.pcm = mid != nullptr;
+    l->m.frame_len = h->frame_len;
+    l->m.hop = h->hop;
+    l->max_words = max_words;
+    l->n_words_exact = n_words_exact;
+    l->skip_cost = skip_cost;
+    l->word_cost = word_cost;
+    int rc = adopt(l, g);
+    if (!rc) rc = l->d_chan.reserve(n_channels);
+    if (!rc && mid) {
+        l->mid.assign(mid, mid + n_channels);
+        l->keep_stride = live_pcm_keep_stride(h);
+        l->stage_stride = live_pcm_stage_stride(h, chunk_max);
+        rc = l->keep.reserve((size_t)n_channels * l->keep_stride);
+        if (!rc) rc = l->stage.reserve((size_t)n_channels * l->stage_stride);
+        if (!rc) rc = l->recs.reserve(n_channels);
+        if (!rc) rc = l->feat.reserve(h->mfcc_elems(n_channels));
+    }
+    if (!rc && hipEventCreateWithFlags(&l->ev_last, hipEventDisableTiming) != hipSuccess) rc = fail(SR_ERR_HIP, "hipEventCreate failed");
+    if (rc) {
+        (void)hipGetLastError();
+        sr_gram_live_close(l);
+        return rc;
+    }
+    *out = l;
+    return SR_OK;
+}
+
+void sr_gram_live_close(sr_gram_live *l)
+{
+    if (!l) return;
+    DeviceGuard guard;
+    (void)guard.enter(l->h->device);
+    if (l->pending) (void)hipEventSynchronize(l->ev_last);
+    l->cols.release();
+    l->A.release();
+    l->E.release();
+    l->d_chan.release();
+    l->keep.release();
+    l->stage.release();
+    l->recs.release();
+    l->feat.release();
+    if (l->ev_last) (void)hipEventDestroy(l->ev_last);
+    delete l;
+}
+
+int sr_gram_live_set_grammar(sr_gram_live *l, const sr_grammar *g)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    if (int rc = check_grammar(l->h, g)) return rc;
+    if (int rc = check_store(l)) return rc;  // the store g was compiled against must fit the sweep's LDS image as well
+    std::string why;
+    if (!gram_live_all_empty(l->m, &why)) return fail(SR_ERR_BAD_ARG, why);
+    ENTER_DEVICE(l->h);
+    if (l->pending) {  // nothing of an empty session is in flight but a trace, which reads the old grammar's lists
+        HIP_TRY(hipEventSynchronize(l->ev_last));
+        l->pending = false;
+    }
+    return adopt(l, g);
+}
+
+int sr_gram_live_push_dev(sr_gram_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                          sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost, sr_chain_live_row *rows, uint32_t *n_rows,
+                          void *stream)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    DecodeLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_frames_in(l, pl, d_mfcc, row_stride, true);
+    if (!rc) rc = check_outputs(l, pl.rows, max_rows, d_rec, d_words, d_level_cost, rows);
+    if (rc) return rc;
+    ENTER_DEVICE(l->h);
+    const hipStream_t s = (hipStream_t)stream;
+    if (pl.rows) {
+        if ((rc = order_after_last_push(l, s))) return rc;
+        if ((rc = upload_chan(l, pl.chan, s))) return rc;
+        if ((rc = launch_push(l, pl, d_mfcc, row_stride, d_rec, d_words, d_level_cost, s))) return rc;
+    }
+    decode_live_advance(l->m, pl, rows, n_rows);
+    return pl.rows ? mark_push(l, s) : SR_OK;
+}
+
+int sr_gram_live_push(sr_gram_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                      sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    DecodeLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_frames_in(l, pl, mfcc, row_stride, false);
+    if (!rc) rc = check_outputs(l, pl.rows, max_rows, rec, words, level_cost, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_HOST_CALL(h);
+    HostOutputs o;
+    if (pl.rows) {
+        const size_t ds = (size_t)pl.max_frames * kCoef;  // device rows hold the largest count
+        if ((rc = h->s_mfcc.reserve((size_t)l->m.C * ds))) return rc;
+        if ((rc = o.reserve(pl.rows, l->max_words, level_cost != nullptr))) return rc;
+        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
+            if (pl.chan[c].n) COPY_UP(h->s_mfcc.p + c * ds, mfcc + (size_t)c * row_stride, (size_t)pl.chan[c].n * kCoef * 2);
+        if ((rc = order_after_last_push(l, nullptr))) return rc;
+        if ((rc = upload_chan(l, pl.chan, nullptr))) return rc;
+        if ((rc = launch_push(l, pl, h->s_mfcc.p, ds, o.rec.p, o.words.p, level_cost ? o.lc.p : nullptr, nullptr))) return rc;
+    }
+    decode_live_advance(l->m, pl, rows, n_rows);
+    if (pl.rows && (rc = mark_push(l, nullptr))) return rc;
+    return pl.rows ? o.down(pl.rows, l->max_words, rec, words, level_cost) : SR_OK;
+}
+
+int sr_gram_live_push_pcm_dev(sr_gram_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                              sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_level_cost, sr_chain_live_row *rows, uint32_t *n_rows,
+                              void *stream)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    DecodeLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_pcm_in(l, pl, d_pcm, pcm_stride, true);
+    if (!rc) rc = check_outputs(l, pl.rows, max_rows, d_rec, d_words, d_level_cost, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_DEVICE(h);
+    const hipStream_t s = (hipStream_t)stream;
+    if (pl.rows) {
+        if ((rc = order_after_last_push(l, s))) return rc;
+        if ((rc = upload_chan(l, pl.chan, s))) return rc;
+        if ((rc = launch_front_end(l, pl, d_pcm, pcm_stride, s))) return rc;
+        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, d_rec, d_words, d_level_cost, s))) return rc;
+    }
+    decode_live_advance(l->m, pl, rows, n_rows);
+    return pl.rows ? mark_push(l, s) : SR_OK;
+}
+
+int sr_gram_live_push_pcm(sr_gram_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                          sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    DecodeLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_pcm_in(l, pl, pcm, pcm_stride, false);
+    if (!rc) rc = check_outputs(l, pl.rows, max_rows, rec, words, level_cost, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_HOST_CALL(h);
+    HostOutputs o;
+    if (pl.rows) {
+        const uint64_t ds = dev_pitch(pl.max_n);
+        if ((rc = h->s_pcm.reserve((size_t)l->m.C * ds))) return rc;
+        if ((rc = o.reserve(pl.rows, l->max_words, level_cost != nullptr))) return rc;
+        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
+            if (pl.chan[c].n_samp) COPY_UP(h->s_pcm.p + c * ds, pcm + (size_t)c * pcm_stride, (size_t)pl.chan[c].n_samp * 2);
+        if ((rc = order_after_last_push(l, nullptr))) return rc;
+        if ((rc = upload_chan(l, pl.chan, nullptr))) return rc;
+        if ((rc = launch_front_end(l, pl, h->s_pcm.p, ds, nullptr))) return rc;
+        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, o.rec.p, o.words.p, level_cost ? o.lc.p : nullptr, nullptr)))
+            return rc;
+    }
+    decode_live_advance(l->m, pl, rows, n_rows);
+    if (pl.rows && (rc = mark_push(l, nullptr))) return rc;
+    return pl.rows ? o.down(pl.rows, l->max_words, rec, words, level_cost) : SR_OK;
+}
+
+int sr_gram_live_end(sr_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost,
+                     sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l || (n_ch && !channels)) return fail(SR_ERR_BAD_ARG, "null argument");
+    sr_engine *h = l->h;
+    std::vector<SpotLiveChan> chan;
+    std::vector<sr_chain_live_row> order;
+    std::string why;
+    // Under a stale grammar the history belongs to a store or a word map that is gone: every listed recording is dropped.  Its
+    // trace has N = 0 and reads neither the store nor the word map, so whatever state those are in, the channels can be ended.
+    const bool dropped = stale(l, &why);
+    if (!decode_live_end_list(l->m, dropped ? kGramLiveStale : kGramLiveBound, channels, n_ch, &chan, &order, &why)) return fail(SR_ERR_BAD_ARG, why);
+    const uint32_t n_out = (uint32_t)order.size();
+    if (int rc = check_outputs(l, n_out, n_out, rec, words, level_cost, rows, !dropped)) return rc;
+    if (int rc = check_end_rows(l, n_out, rec, words, level_cost, rows)) return rc;
+    if (!n_out) {
+        if (n_rows) *n_rows = 0;
+        return SR_OK;
+    }
+    ENTER_HOST_CALL(h);
+    if (l->pending) {
+        HIP_TRY(hipEventSynchronize(l->ev_last));
+        l->pending = false;
+    }
+    HostOutputs o;
+    if (int rc = o.reserve(n_out, l->max_words, level_cost != nullptr)) return rc;
+    if (int rc = upload_chan(l, chan, nullptr)) return rc;
+    launch_gram_live_trace(live_args(l, nullptr, 0, o.rec.p, o.words.p, level_cost ? o.lc.p : nullptr), nullptr);
+    HIP_TRY(hipGetLastError());
+    if (int rc = o.down(n_out, l->max_words, rec, words, level_cost)) return rc;
+    decode_live_reset(l->m, kGramLiveBound, order);
+    for (uint32_t r = 0; r < n_out; r++) rows[r] = order[r];
+    if (n_rows) *n_rows = n_out;
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -725,6 +725,12 @@ class Engine:
         session (chunk_max in frames); mid uint32 [n_channels]: a PCM session (chunk_max in samples)."""
         return DecodeSession(self, n_channels, chunk_max, utt_frames, max_words, n_words, skip_cost, word_cost, mid)
 
+    def decode_grammar_live(self, gram, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0,
+                            mid=None):
+        """sr_gram_live_open: a GrammarSession -- decode_live() under a Grammar, which sess.set_grammar() switches between
+        recordings.  Close the session before the grammar."""
+        return GrammarSession(self, gram, n_channels, chunk_max, utt_frames, max_words, n_words, skip_cost, word_cost, mid)
+
     # ---- full-DP alignment and word models from many examples -----------------------------------------
     def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
         """OPT-IN (sr_dtw_dp_align): the optimal warping path of the full-DP scorer for every (row, reference) pair.  mfcc int16
@@ -1391,26 +1397,33 @@ def decode_live_geometry(tpl_rows, K, max_words, utt_frames, chunk_max):
 class DecodeSession:
     """One sr_decode_live handle (Engine.decode_live): connected-word decoding over chunked features or samples on n_channels
     channels, the decoder's state carried between pushes.  After every push the row of a channel is Engine.decode_words on
-    everything pushed to it as one row (include/sr_engine.h, "live connected-word decoding")."""
+    everything pushed to it as one row (include/sr_engine.h, "live connected-word decoding").  GrammarSession shares this body:
+    the two C sessions take the same arguments behind their prefix, and sr_gram_live_open one more behind the engine."""
 
-    def __init__(self, eng, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
+    _PREFIX = "sr_decode_live_"  # the C entry points of the session
+
+    def __init__(self, eng, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None, _first=()):
+        """_first: what the session's open call takes between the engine and n_channels (subclasses)"""
         self.eng, self.L, self.n_channels, self.chunk_max, self.utt_frames = eng, eng.L, n_channels, chunk_max, utt_frames
         self.max_words = max_words
-        self.L.sr_decode_live_close.restype = None
-        self.L.sr_decode_live_close.argtypes = [C.c_void_p]
+        self._fn("close").restype = None
+        self._fn("close").argtypes = [C.c_void_p]
         md = None if mid is None else np.ascontiguousarray(mid, dtype=np.uint32)
         assert md is None or md.shape == (n_channels,)
         self.pcm = md is not None
         self._frames = np.zeros(n_channels, np.uint32)  # what the rows of the pushes said, per channel
         l = C.c_void_p()
-        eng._check(self.L.sr_decode_live_open(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames),
-                                              C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(Engine._skip(skip_cost)),
-                                              C.c_uint32(word_cost), _vp(md), C.byref(l)))
+        eng._check(self._fn("open")(eng.h, *_first, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames),
+                                    C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(Engine._skip(skip_cost)),
+                                    C.c_uint32(word_cost), _vp(md), C.byref(l)))
         self.l = l
+
+    def _fn(self, name):
+        return getattr(self.L, self._PREFIX + name)
 
     def close(self):
         if getattr(self, "l", None):
-            self.L.sr_decode_live_close(self.l)
+            self._fn("close")(self.l)
             self.l = None
 
     def __del__(self):
@@ -1479,7 +1492,7 @@ class DecodeSession:
         mf = np.ascontiguousarray(frames, dtype=np.int16)
         assert mf.ndim == 3 and mf.shape[0] == self.n_channels and mf.shape[2] == N_COEF
         F = mf.shape[1]
-        return self._push_host(self.L.sr_decode_live_push, mf, max(F, 1) * N_COEF, F, counts, max_rows)
+        return self._push_host(self._fn("push"), mf, max(F, 1) * N_COEF, F, counts, max_rows)
 
     def push_dev(self, frames, counts=None, max_rows=None, level_cost=True, stream=None):
         """sr_decode_live_push_dev on a device tensor: frames int16 [n_channels, F, 12], counts a HOST array [n_channels] (None:
@@ -1490,14 +1503,14 @@ class DecodeSession:
         assert frames.is_cuda and frames.dtype == torch.int16 and frames.is_contiguous()
         assert frames.ndim == 3 and frames.shape[0] == self.n_channels and frames.shape[2] == N_COEF
         F = frames.shape[1]
-        return self._push_dev(self.L.sr_decode_live_push_dev, frames, max(F, 1) * N_COEF, F, counts, max_rows, level_cost, stream)
+        return self._push_dev(self._fn("push_dev"), frames, max(F, 1) * N_COEF, F, counts, max_rows, level_cost, stream)
 
     def push_pcm(self, chunks, counts=None, max_rows=None):
         """sr_decode_live_push_pcm: chunks uint16 [n_channels, S], counts [n_channels] in samples (None: S each); returns as push"""
         pcm = np.ascontiguousarray(chunks, dtype=np.uint16)
         assert pcm.ndim == 2 and pcm.shape[0] == self.n_channels
         S = pcm.shape[1]
-        return self._push_host(self.L.sr_decode_live_push_pcm, pcm, max(S, 1), S, counts, max_rows)
+        return self._push_host(self._fn("push_pcm"), pcm, max(S, 1), S, counts, max_rows)
 
     def push_pcm_dev(self, chunks, counts=None, max_rows=None, level_cost=True, stream=None):
         """sr_decode_live_push_pcm_dev: chunks int16 [n_channels, S] on the device (u16 codes, S a multiple of 8); returns as
@@ -1506,7 +1519,7 @@ class DecodeSession:
         assert chunks.is_cuda and chunks.dtype in (torch.int16, torch.uint16) and chunks.is_contiguous()
         assert chunks.ndim == 2 and chunks.shape[0] == self.n_channels
         S = chunks.shape[1]
-        return self._push_dev(self.L.sr_decode_live_push_pcm_dev, chunks, S, S, counts, max_rows, level_cost, stream)
+        return self._push_dev(self._fn("push_pcm_dev"), chunks, S, S, counts, max_rows, level_cost, stream)
 
     def end(self, channels):
         """sr_decode_live_end: the listed channels' recordings end here.  Returns dict(rec, words, level_cost, rows, n_rows) as
@@ -1517,9 +1530,36 @@ class DecodeSession:
         rec, words = np.zeros(cap, dtype=CHAIN_REC_DTYPE), np.zeros((cap, W), dtype=CHAIN_WORD_DTYPE)
         lc = np.zeros((cap, W), dtype=np.uint32)
         rows, n = np.zeros(cap, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
-        self.eng._check(self.L.sr_decode_live_end(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(lc), _vp(rows), C.byref(n)))
+        self.eng._check(self._fn("end")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(lc), _vp(rows), C.byref(n)))
         self._frames[rows[:n.value]["channel"]] = 0
         return dict(rec=rec[:n.value], words=words[:n.value], level_cost=lc[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+
+def grammar_live_geometry(gram, max_words, utt_frames, chunk_max):
+    """Host-only sr_gram_live_geometry: dict(state_bytes on the device per channel, max_tpl_rows that fit, launches one
+    feature push enqueues, columns = the boundary columns per channel: the items kept, summed over the levels)"""
+    out = (C.c_uint32 * 4)()
+    gram.eng._check(gram.L.sr_gram_live_geometry(gram.g, C.c_uint32(max_words), C.c_uint32(utt_frames), C.c_uint32(chunk_max), out))
+    return dict(state_bytes=out[0], max_tpl_rows=out[1], launches=out[2], columns=out[3])
+
+
+class GrammarSession(DecodeSession):
+    """One sr_gram_live handle (Engine.decode_grammar_live): a DecodeSession under a Grammar.  After every push the row of a
+    channel is Engine.decode_grammar on everything pushed to it as one row (include/sr_engine.h, "live grammar-constrained
+    decoding").  push, push_dev, push_pcm, push_pcm_dev, end, frames and close are DecodeSession's; set_grammar switches the
+    grammar while every channel is empty.  Close the session before its grammar."""
+
+    _PREFIX = "sr_gram_live_"
+
+    def __init__(self, eng, gram, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
+        super().__init__(eng, n_channels, chunk_max, utt_frames, max_words, n_words, skip_cost, word_cost, mid, _first=(gram.g,))
+        self.gram = gram  # kept alive: the session is closed before its grammar
+
+    def set_grammar(self, gram):
+        """sr_gram_live_set_grammar: the grammar of the next dialogue state, or a fresh one in the place of a stale one;
+        raises unless every channel is empty (freshly opened or ended)"""
+        self.eng._check(self._fn("set_grammar")(self.l, gram.g))
+        self.gram = gram
 
 
 def unpack_vad_masks(masks, n_frames=None):
