@@ -744,8 +744,8 @@ int sr_decode_live_end(sr_decode_live *l, const uint32_t *channels, uint32_t n_c
  *            word), word a label of the engine's word map (sr_set_word_map; default word = slot).  slots(w) = the valid slots
  *            with label w.  For a pair (t, w) with at least one arc, From(t, w) = { s : (s, t, w) is an arc }.
  *   limits   S 1..64 (a from-set is one 64-bit mask), n_arcs 1..4096, every word a label of the current map.  No duplicate
- *            arcs, no empty (epsilon) arcs, no arc weights.  Dead and unreachable states are allowed; a word whose slots are
- *            all invalid is allowed and contributes nothing.
+ *            arcs, no empty (epsilon) arcs.  Dead and unreachable states are allowed; a word whose slots are all invalid is
+ *            allowed and contributes nothing.  Costs on arcs and final states: sr_grammar_create_weighted below.
  * Everything not restated here is the connected-word decoding section: d, the word path, skip_cost, word_cost, the argument
  * limits, the u32 cost bound, the record formats.
  *   E_0(p,s) that section's E_0(p) for s = 0; INF for every other state.
@@ -770,7 +770,7 @@ int sr_decode_live_end(sr_decode_live *l, const uint32_t *channels, uint32_t n_c
  * therefore costs the K passes per level of the unconstrained decoder.
  * Anchor: S = 1, final_state[0] = 1 and one arc (0, 0, w) per label give, byte for byte, what sr_decode_words_dp writes
  * (reserved = 0 included).
- * Out of scope: arc weights; epsilon arcs; more than 64 states.  (The push-by-push session is the next section.) */
+ * Out of scope: epsilon arcs; more than 64 states.  (The push-by-push session is the next section.) */
 typedef struct sr_gram_arc { /* 16 bytes */
     uint32_t from;
     uint32_t to;
@@ -788,6 +788,41 @@ typedef struct sr_grammar sr_grammar;
  * fit the store, a store of more than 65 536 slots. */
 int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, uint32_t n_arcs, const uint8_t *final_state,
                       sr_grammar **out);
+/* Weighted grammars: arc weights and final costs.  A grammar above can only allow or forbid a word in a context; the grammars
+ * applications use are bigram tables, priors over commands and a price for stopping early: "this word is likely here, that
+ * one unlikely", as a cost added to the acoustic cost.  arc_cost[i] (u32) belongs to arc i, final_cost[s] (u32) to the final
+ * state s; write c(s,t,w) for the cost of arc (s,t,w).  Everything not restated is the section above.
+ *   limits   every arc cost <= 2^24 and every final cost <= 2^24; a state that is not final has final cost 0.  The cost bound of
+ *            the connected-word section still holds: 3 * 16 383 * 65 536 + 16 * 2^24 (paths and word costs) + 16 * 2^24 (arcs)
+ *            + 2^24 (final) = 3 774 676 992 < 2^32, so u32 costs stay exact.
+ *   charge   C_l(x; t, w) = min over the s in From(t, w) with E_{l-1}(x, s) finite of E_{l-1}(x, s) + c(s,t,w); INF when there
+ *            is no such s.  An unreachable E (SR_DIS_ERR) never has a cost added to it.
+ *   level, A_l, E_l  unchanged: the arc cost is part of a word's key cost and of cum.  Filler after a word stays in the word's
+ *            target state at skip_cost per frame.
+ *   L_l      min over the final f with E_l(N, f) finite of E_l(N, f) + final_cost[f].  d_level_cost[l-1] = L_l and
+ *            sr_chain_rec.cost = L_n.
+ *   count    as above, over these L_l.
+ *   end      the smallest final f with E_n(N, f) + final_cost[f] = L_n.
+ *   trace    as above, with acc = key cost - word_cost - C_l(S; t, w(k)): still the word's own path cost, without its arc
+ *            cost; cum = E_l(p,t), so the LAST word's cum excludes the final cost while sr_chain_rec.cost includes it; the
+ *            source state is the smallest s of From(t, w(k)) with E_{l-1}(S, s) finite and E_{l-1}(S, s) + c(s,t,w(k)) =
+ *            C_l(S; t, w(k)).
+ *   ties     smallest start, then slot, then fewest words, then smallest final state, then smallest source state, all judged
+ *            on the costs including arc and final costs.
+ *   pruning  unchanged: it is structural and costs are finite, so it still never changes an output byte.
+ * Why one pass per (slot, target state) still serves every arc of the word into that state: min_s (E(x,s) + c_s + path) =
+ * (min_s (E(x,s) + c_s)) + path.  A bigram grammar over W words costs K word passes per level, not W x K.
+ * The compile step keeps, per pair (t, w), its CHARGE LIST: the ascending-by-state list of (s, c(s,t,w)); distinct lists are
+ * shared as from-sets are, and sr_grammar_plan's out[3] and the "from-sets * 4" term of out[0] count distinct charge lists.
+ * Anchor: all costs zero (or both arrays NULL) gives the grammar sr_grammar_create makes -- the same plan figures, the same
+ * kernels and launches, byte for byte the same outputs in every batch and live call.
+ * arc_cost is a HOST array [n_arcs] or NULL (all 0), final_cost a HOST array [n_states] or NULL (all 0).  The grammar carries
+ * its costs: every call that takes an sr_grammar takes it unchanged (sr_decode_grammar_dp[_dev], sr_decode_grammar_batch,
+ * sr_grammar_plan, and the live session's open, set_grammar, pushes, end and geometry).  Errors as sr_grammar_create
+ * (sr_gram_arc.reserved must still be 0); SR_ERR_BAD_ARG as well, nothing created, for a cost above 2^24 or a nonzero
+ * final_cost on a state that is not final. */
+int sr_grammar_create_weighted(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, const uint32_t *arc_cost, uint32_t n_arcs,
+                               const uint8_t *final_state, const uint32_t *final_cost, sr_grammar **out);
 void sr_grammar_destroy(sr_grammar *g); /* before sr_destroy of its engine; waits for the device */
 /* Host-only.  Per-level pruning, exact (it never changes an output byte): level l of a call with max_words keeps item (slot,
  * t, from-set) only if the from-set meets the states reachable from state 0 in exactly l-1 arcs and a final state is
@@ -837,7 +872,10 @@ int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *p
  * sr_gram_live_set_grammar with a fresh grammar puts the session back to work.  Refusals, HIP failures, stream ordering and
  * the engine's one-caller-at-a-time rule as in the live connected-word decoding section.  Teardown: the session before its
  * grammar, the grammar before the engine.
- * Out of scope: a grammar per channel; arc weights; epsilon arcs; more than 64 states; a history compacted to each level's
+ * A weighted grammar (sr_grammar_create_weighted) is taken as it is by every call below, sr_gram_live_set_grammar included: the
+ * row is then what the weighted definitions give for Y_c as one row, and sr_gram_live_geometry's figures are those of the
+ * same network without costs.
+ * Out of scope: a grammar per channel; epsilon arcs; more than 64 states; a history compacted to each level's
  * target states (the dense [S] history is what sr_gram_live_geometry reports); splitting a push along time. */
 typedef struct sr_gram_live sr_gram_live;
 /* host-only, no device: out[0] = device state bytes per channel, saturating: columns * tpl_rows * 16 + (utt_frames + 1) * S *

@@ -16,6 +16,11 @@
 // from the item's C row, and the key goes to A_l of the item's target state.  A slot has one label, so a (slot, target) pair
 // is one item at most and the u64 minimum over the items of a target is the (cost, start, slot) rule.  The sweep and the
 // close are restated here and not shared with k_chain.hip: that file's kernels stay byte for byte what they were measured as.
+//
+// A WEIGHTED grammar (include/sr_engine.h, "weighted grammars": a cost on every arc and every final state) takes two kernels
+// of its own, k_gram_charge_w and k_gram_trace_w, with the costs in a second argument block; init, sweep and close serve it
+// unchanged, because the arc cost sits inside the charge: min_s (E(x, s) + c_s + path) = (min_s (E(x, s) + c_s)) + path.  A
+// grammar without a nonzero cost launches exactly what it always has.
 #include <algorithm>
 
 #include "sr_dtw_plan.h"
@@ -287,7 +292,124 @@ __global__ void __launch_bounds__(64) k_gram_trace(const GramArgs a)
     if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, SR_CH_OK};
 }
 
-void launch_gram(const GramArgs &a, hipStream_t s)
+// k_gram_charge under costs: one row of charges per distinct charge list, C(x) = min over the list's (s, c) with E_{l-1}(x, s)
+// reachable of E_{l-1}(x, s) + c.  An unreachable E takes no cost: all ones + c would wrap to c - 1 and win every minimum.
+// Same grid; restated, so that k_gram_charge stays byte for byte.
+__global__ void __launch_bounds__(256) k_gram_charge_w(const GramArgs a, const GramCosts wt, const uint32_t level)
+{
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, row = blockIdx.z, P = a.c.max_frames + 1u;
+    if (x >= P) return;
+    const uint32_t set = a.lists[a.lv[level - 1].set0 + blockIdx.y];
+    const uint32_t *E = gram_E(a, row, level - 1, 0);
+    const uint32_t *cost = wt.cost + wt.cost_off[set];
+    uint32_t c = kChainNone;
+    for (unsigned long long m = a.masks[set]; m; m &= m - 1) {  // (uniform; ascending states, as the costs are stored)
+        const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+        const uint32_t e = E[(size_t)s * P + x], v = e + *cost++;
+        c = (e != kChainNone && v < c) ? v : c;
+    }
+    gram_C(a, row, set)[x] = c;
+}
+
+// k_gram_trace under costs: L_l adds the final cost of the state it ends in, the charge of a word and its source state are
+// judged on E_{l-1} + the arc cost, both over finite E only.  Restated: k_gram_trace stays byte for byte.
+__global__ void __launch_bounds__(64) k_gram_trace_w(const GramArgs a, const GramCosts wt)
+{
+    const uint32_t row = blockIdx.x, W = a.c.max_words, S = a.n_states, lane = threadIdx.x;
+    const uint32_t N = gram_frames(a, row);
+    sr_chain_rec *rec = a.c.rec + row;
+    sr_chain_word *words = a.c.words + (size_t)row * W;
+    // L_l = the cheapest final state of level l = lane with its final cost, the smallest state among equals; then the count
+    uint32_t c = kChainNone, fin = 0;
+    if (N && lane >= 1 && lane <= W) {
+        for (uint32_t f = 0; f < S; f++) {
+            if (!a.final_state[f]) continue;
+            const uint32_t e = gram_E(a, row, lane, f)[N];
+            if (e == kChainNone) continue;  // an unreachable state takes no cost: all ones + cost would wrap
+            const uint32_t v = e + wt.final_cost[f];
+            if (v < c) c = v, fin = f;
+        }
+    }
+    if (a.c.level_cost && lane >= 1 && lane <= W) a.c.level_cost[(size_t)row * W + lane - 1] = c;
+    uint32_t n = a.c.n_words_exact;
+    if (!n) {
+        uint64_t key = ((uint64_t)c << 32) | lane;  // lanes without a level carry all-ones costs and lose to none of them
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) key = spot_min(key, spot_shfl(key, lane ^ (uint32_t)d));
+        n = (uint32_t)(key >> 32) == kChainNone ? 1u : (uint32_t)key;
+    }
+    const uint32_t total = __shfl(c, (int)n, 64);
+    uint32_t t = __shfl(fin, (int)n, 64);
+    const bool ok = total != kChainNone;
+    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    for (uint32_t i = (ok ? n : 0u) + lane; i < W; i += 64) words[i] = none;
+    if (!ok) {
+        if (lane == 0) *rec = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
+        return;
+    }
+    uint32_t p = N, in_words = 0;
+    for (uint32_t l = n; l >= 1; l--) {  // (uniform)
+        const unsigned long long *A = gram_A(a, row, l, t);
+        const uint32_t *E = gram_E(a, row, l, t);
+        // the first position at or below p whose own word closes E_l(., t) there; E_l(p, t) is finite, so there is one above 0
+        uint64_t key = kSpotInf;
+        uint32_t cum = 0;
+        while (p >= 1) {
+            const bool mine = lane < p;  // position p - lane >= 1
+            const uint64_t ky = mine ? A[p - lane] : kSpotInf;
+            const uint32_t e = mine ? E[p - lane] : kChainNone;
+            const unsigned long long hit = __ballot(mine && ky != kSpotInf && (uint32_t)(ky >> 32) == e);
+            if (hit) {
+                const uint32_t first = (uint32_t)__ffsll((long long)hit) - 1u;
+                key = spot_shfl(ky, first);
+                cum = __shfl(e, (int)first, 64);
+                p -= first;
+                break;
+            }
+            p = p > 64u ? p - 64u : 0u;
+        }
+        const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu, end = p - 1;
+        // the item (slot, t) by bisection of the items, which ascend by (slot, target): its from-set
+        uint32_t lo = 0, hi = a.n_items;
+        const uint64_t want = ((uint64_t)slot << 32) | t;
+        while (key != kSpotInf && lo < hi) {  // (uniform)
+            const uint32_t mid = lo + (hi - lo) / 2;
+            const GramItem it = a.items[mid];
+            if ((((uint64_t)it.slot << 32) | it.target) < want) lo = mid + 1;
+            else hi = mid;
+        }
+        bool found = false;
+        if (key != kSpotInf && lo < a.n_items) {
+            const GramItem it = a.items[lo];
+            found = it.slot == slot && it.target == t;
+        }
+        if (!found) {  // cannot happen while A, E and the items agree; leave a whole record that says so
+            for (uint32_t i = lane; i < W; i += 64) words[i] = none;
+            if (lane == 0) *rec = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
+            return;
+        }
+        // the charge the word started from, arc cost included, and the smallest state of the list that carries it
+        uint32_t charge = kChainNone, src = 0;
+        const uint32_t set = a.items[lo].set;
+        const uint32_t *cost = wt.cost + wt.cost_off[set];
+        for (unsigned long long m = a.masks[set]; m; m &= m - 1) {  // (uniform; ascending states)
+            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+            const uint32_t e = gram_E(a, row, l - 1, s)[start], ac = *cost++;
+            if (e != kChainNone && e + ac < charge) charge = e + ac, src = s;
+        }
+        if (lane == 0) {
+            const uint32_t acc = (uint32_t)(key >> 32) - a.c.word_cost - charge;
+            words[l - 1] = sr_chain_word{a.c.word_id[a.c.group_of_slot[slot]], slot, start, end, acc,
+                                         acc / (end - start + 1 + a.c.tpl_frames[slot]), cum, t};
+        }
+        in_words += end - start + 1;
+        p = start;
+        t = src;
+    }
+    if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, SR_CH_OK};
+}
+
+void launch_gram(const GramArgs &a, const GramCosts *w, hipStream_t s)
 {
     if (!a.c.n_rows) return;
     const size_t lds = spot_lds_bytes(a.c.tpl_len);
@@ -297,12 +419,15 @@ void launch_gram(const GramArgs &a, hipStream_t s)
     for (uint32_t l = 1; l <= a.c.max_words; l++) {
         const GramLevel &lv = a.lv[l - 1];
         if (!lv.n_items) continue;  // nothing can end here: the level stays unreachable
-        hipLaunchKernelGGL(k_gram_charge, dim3((P + 255u) / 256u, lv.n_sets, a.c.n_rows), dim3(256), 0, s, a, l);
+        const dim3 charge_grid((P + 255u) / 256u, lv.n_sets, a.c.n_rows);
+        if (w) hipLaunchKernelGGL(k_gram_charge_w, charge_grid, dim3(256), 0, s, a, *w, l);
+        else hipLaunchKernelGGL(k_gram_charge, charge_grid, dim3(256), 0, s, a, l);
         hipLaunchKernelGGL(k_gram_words, dim3(lv.n_items, a.c.n_rows, (a.c.n_chunks + kSpotWaves - 1) / kSpotWaves), dim3(64 * kSpotWaves), lds, s,
                            a, l);
         hipLaunchKernelGGL(k_gram_close, dim3(a.c.n_rows, lv.n_states), dim3(256), 0, s, a, l);
     }
-    hipLaunchKernelGGL(k_gram_trace, dim3(a.c.n_rows), dim3(64), 0, s, a);
+    if (w) hipLaunchKernelGGL(k_gram_trace_w, dim3(a.c.n_rows), dim3(64), 0, s, a, *w);
+    else hipLaunchKernelGGL(k_gram_trace, dim3(a.c.n_rows), dim3(64), 0, s, a);
 }
 const char *gram_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_gram_words, "k_gram_words"}}, bytes); }
 

@@ -404,7 +404,14 @@ struct GramArgs {
     uint32_t *C;
     GramLevel lv[16];
 };
-void launch_gram(const GramArgs &a, hipStream_t s);  // init, per level with items (charge, words, close), trace
+// A weighted grammar's costs (include/sr_engine.h, "weighted grammars"), the second argument of the weighted kernels: charge
+// list i's arc costs are cost[cost_off[i] .. cost_off[i + 1]), in the ascending order of the states of masks[i];
+// final_cost[n_states] is 0 for a state that is not final.  The unweighted kernels and their argument blocks stay as they are.
+struct GramCosts {
+    const uint32_t *cost_off, *cost, *final_cost;
+};
+// init, per level with items (charge, words, close), trace; w null: the unweighted kernels, otherwise the weighted charge and trace
+void launch_gram(const GramArgs &a, const GramCosts *w, hipStream_t s);
 
 // live connected-word decoding (k_chain_live.hip): the levels of k_chain.hip resumed from push to push.  Per channel the session
 // keeps one boundary column per (level, slot), cols[C][max_words][K][tpl_len], and the history A[C][max_words][P] /
@@ -454,8 +461,9 @@ struct GramLiveArgs {
     GramLevel lv[16];
     uint32_t col_off[16];
 };
-void launch_gram_live(const GramLiveArgs &a, hipStream_t s);        // init, per level with items (words, close), trace
-void launch_gram_live_trace(const GramLiveArgs &a, hipStream_t s);  // the trace alone (no new frame, sr_gram_live_end)
+// w null: the unweighted kernels, otherwise the weighted sweep and trace
+void launch_gram_live(const GramLiveArgs &a, const GramCosts *w, hipStream_t s);        // init, per level with items (words, close), trace
+void launch_gram_live_trace(const GramLiveArgs &a, const GramCosts *w, hipStream_t s);  // the trace alone (no new frame, sr_gram_live_end)
 
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the

@@ -13,6 +13,7 @@
 
 #include "sr_device.h"
 #include "sr_dtw_plan.h"
+#include "sr_gram_compile.h"
 #include "sr_tables.h"
 
 namespace sr {
@@ -280,20 +281,24 @@ int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, 
                       uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
                       const uint32_t *level_cost);
 // ---- grammar-constrained decoding (sr_gram.cpp) -------------------------------------------------------------------------------
-// The compiled form.  Items ascend by (slot, target).  Level l keeps the items whose from-set meets the states reachable from
-// state 0 in exactly l - 1 arcs; its lists are sorted by the distance (in arcs) from the target to a final state, so that
-// what a call with max_words keeps -- distance <= max_words - l -- is a PREFIX of each list, and a call only counts.
+// The compiled form (sr_gram_compile.h builds it on the host).  Items ascend by (slot, target); level l's lists are sorted by
+// the distance from the target to a final state, so that what a call with max_words keeps is a PREFIX of each list.
 struct sr_grammar {
     sr_engine *h = nullptr;
     uint64_t store_serial = 0, word_serial = 0;
     uint32_t n_states = 0, n_sets = 0, n_items = 0, max_frames = 0, tpl_len = 0;
-    struct Level {
-        uint32_t item0 = 0, set0 = 0, state0 = 0;                                  // where the level's lists start in `lists`
-        uint32_t items[kChainMaxWords + 1] = {}, sets[kChainMaxWords + 1] = {}, states[kChainMaxWords + 1] = {};  // [j]: entries of distance < j
-    } lv[kChainMaxWords];
-    // device: masks u64 [n_sets] | items [n_items] | lists u32 | final u8 [n_states]
+    using Level = GramLevelLists;
+    Level lv[kChainMaxWords];
+    // device: masks u64 [n_sets] | items [n_items] | lists u32 | final u8 [n_states], and behind them for a weighted grammar
+    // (some cost nonzero; every other grammar ends at `final`): cost_off u32 [n_sets + 1] | costs u32 | final_cost u32 [n_states]
     DevBuf<unsigned long long> blob;
     size_t items_at = 0, lists_at = 0, final_at = 0;  // offsets in u64 units
+    bool weighted = false;
+    size_t cost_off_at = 0, costs_at = 0, final_cost_at = 0;  // offsets in u64 units (weighted only)
+    GramCosts costs() const  // the weighted kernels' second argument
+    {
+        return GramCosts{(const uint32_t *)(blob.p + cost_off_at), (const uint32_t *)(blob.p + costs_at), (const uint32_t *)(blob.p + final_cost_at)};
+    }
 };
 // a grammar of this engine, compiled against its current store and word map
 int check_grammar(const sr_engine *h, const sr_grammar *g);

@@ -1,18 +1,13 @@
-// Grammar-constrained decoding (include/sr_engine.h, "grammar-constrained decoding"): the compile step of a grammar against
-// the engine's store and word map, the checks, the plan (which items each level keeps, the scratch of a row) and the slicing
-// of a call into launch groups.  Per group: k_gram_init, per level that keeps items (k_gram_charge, k_gram_words,
-// k_gram_close), k_gram_trace, everything on the caller's stream.  The whole-path host form is in sr_host.cpp, next to
-// sr_decode_words_batch.
+// Grammar-constrained decoding (include/sr_engine.h, "grammar-constrained decoding" and "weighted grammars"): a grammar
+// compiled against the engine's store and word map (the construction itself is host-only code, sr_gram_compile.h), the
+// checks, the plan (which items each level keeps, the scratch of a row) and the slicing of a call into launch groups.  Per
+// group: k_gram_init, per level that keeps items (k_gram_charge, k_gram_words, k_gram_close), k_gram_trace, everything on the
+// caller's stream; a grammar with a nonzero cost takes k_gram_charge_w and k_gram_trace_w in their places.  The whole-path
+// host form is in sr_host.cpp, next to sr_decode_words_batch.
+#include "sr_gram_compile.h"
 #include "sr_host_call.h"
 
-#include <map>
-#include <set>
-#include <unordered_set>
-
 using namespace sr;
-
-static constexpr uint32_t kGramMaxStates = 64, kGramMaxArcs = 4096, kGramMaxItems = 1u << 20;
-static constexpr uint32_t kFar = 0xFFFFFFFFu;  // a state from which no final state is reachable
 
 // (the compiled form, struct sr_grammar, is in sr_engine_internal.h: the live session of sr_gram_live.cpp reads it too)
 namespace {
@@ -62,32 +57,17 @@ int check_grammar(const sr_engine *h, const sr_grammar *g)
 
 extern "C" {
 
-int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, uint32_t n_arcs, const uint8_t *final_state,
-                      sr_grammar **out)
+int sr_grammar_create_weighted(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, const uint32_t *arc_cost, uint32_t n_arcs,
+                               const uint8_t *final_state, const uint32_t *final_cost, sr_grammar **out)
 {
     if (!h || !arcs || !final_state || !out) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc = check_chain(h, 1, 0, SR_DIS_ERR, 0)) return rc;  // the engine and the store, as every decode call
-    if (n_states < 1 || n_states > kGramMaxStates) return fail(SR_ERR_BAD_ARG, "n_states must be 1..64");
-    if (n_arcs < 1 || n_arcs > kGramMaxArcs) return fail(SR_ERR_BAD_ARG, "n_arcs must be 1..4096");
     const uint32_t S = n_states, K = h->K;
     std::vector<uint32_t> label(K);
     for (uint32_t k = 0; k < K; k++) label[k] = h->word_explicit ? h->word_labels[k] : k / h->word_spw;
-    const std::unordered_set<uint32_t> known(label.begin(), label.end());
-    std::map<std::pair<uint32_t, uint32_t>, uint64_t> from;  // (target, word) -> From as a mask, ordered
-    std::set<std::tuple<uint32_t, uint32_t, uint32_t>> seen;
-    for (uint32_t i = 0; i < n_arcs; i++) {
-        const sr_gram_arc &a = arcs[i];
-        const std::string at = "arc " + std::to_string(i);
-        if (a.from >= S || a.to >= S) return fail(SR_ERR_BAD_ARG, at + ": state index at or above n_states");
-        if (a.reserved) return fail(SR_ERR_BAD_ARG, at + ": reserved must be 0");
-        if (!known.count(a.word)) return fail(SR_ERR_BAD_ARG, at + ": word " + std::to_string(a.word) + " is no label of the word map");
-        if (!seen.emplace(a.from, a.to, a.word).second) return fail(SR_ERR_BAD_ARG, at + ": duplicate arc");
-        from[{a.to, a.word}] |= 1ull << a.from;
-    }
-    uint64_t finals = 0;
-    for (uint32_t s = 0; s < S; s++)
-        if (final_state[s]) finals |= 1ull << s;
-    if (!finals) return fail(SR_ERR_BAD_ARG, "no final state");
+    GramNet net;
+    std::string why;
+    if (!gram_check(n_states, arcs, arc_cost, n_arcs, final_state, final_cost, label, &net, &why)) return fail(SR_ERR_BAD_ARG, why);
 
     ENTER_DEVICE(h);
     // slots(w): the VALID slots of the store, which lives on the device
@@ -96,82 +76,42 @@ int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, 
     std::vector<uint32_t> frames(K);
     HIP_TRY(hipMemcpy(valid.data(), h->tpl_valid.p, K, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(frames.data(), h->tpl_frames.p, (size_t)K * 4, hipMemcpyDeviceToHost));
-    std::map<uint32_t, std::vector<uint32_t>> slots;
-    for (uint32_t k = 0; k < K; k++)
-        if (valid[k] && frames[k]) slots[label[k]].push_back(k);
-
-    // the distinct from-sets, and the items by ascending (slot, target)
-    std::vector<unsigned long long> masks;
-    std::map<uint64_t, uint32_t> set_of;
-    std::vector<GramItem> items;
-    for (const auto &f : from) {
-        const auto it = set_of.emplace(f.second, (uint32_t)masks.size());
-        if (it.second) masks.push_back(f.second);
-        const auto sl = slots.find(f.first.second);
-        if (sl == slots.end()) continue;  // every slot of the word is invalid: it contributes nothing
-        for (uint32_t k : sl->second) items.push_back(GramItem{k, f.first.first, it.first->second, 0u});
-    }
-    if (items.size() > kGramMaxItems) return fail(SR_ERR_BAD_ARG, "the grammar compiles to more than 2^20 (slot, state) items");
-    std::sort(items.begin(), items.end(), [](const GramItem &a, const GramItem &b) { return a.slot != b.slot ? a.slot < b.slot : a.target < b.target; });
-
-    // reach[i]: the states reachable from state 0 in exactly i arcs; dist[s]: the fewest arcs from s to a final state
-    uint64_t reach[kChainMaxWords] = {1ull};
-    for (uint32_t i = 1; i < kChainMaxWords; i++)
-        for (uint32_t a = 0; a < n_arcs; a++)
-            if (reach[i - 1] >> arcs[a].from & 1) reach[i] |= 1ull << arcs[a].to;
-    std::vector<uint32_t> dist(S, kFar);
-    for (uint32_t s = 0; s < S; s++)
-        if (finals >> s & 1) dist[s] = 0;
-    for (uint32_t round = 1; round < S; round++)
-        for (uint32_t a = 0; a < n_arcs; a++)
-            if (dist[arcs[a].to] != kFar && dist[arcs[a].to] + 1 < dist[arcs[a].from]) dist[arcs[a].from] = dist[arcs[a].to] + 1;
+    for (uint32_t k = 0; k < K; k++) valid[k] = valid[k] && frames[k];
+    GramCompiled c;
+    if (!gram_build(net, arcs, n_arcs, label, valid, &c, &why)) return fail(SR_ERR_BAD_ARG, why);
 
     sr_grammar *g = new sr_grammar();
     g->h = h;
     g->store_serial = h->store_serial;
     g->word_serial = h->word_serial;
     g->n_states = S;
-    g->n_sets = (uint32_t)masks.size();
-    g->n_items = (uint32_t)items.size();
+    g->n_sets = (uint32_t)c.masks.size();
+    g->n_items = (uint32_t)c.items.size();
     g->max_frames = h->cfg.max_frames;
     g->tpl_len = h->tpl_rows - 1;
-    std::vector<uint32_t> lists;
-    for (uint32_t l = 1; l <= kChainMaxWords; l++) {
-        sr_grammar::Level &v = g->lv[l - 1];
-        // (distance, index) of the level's items, of the from-sets they use (by their nearest item) and of their targets
-        std::vector<std::pair<uint32_t, uint32_t>> li;
-        std::map<uint32_t, uint32_t> ls, lt;
-        for (uint32_t i = 0; i < items.size(); i++) {
-            const uint32_t d = dist[items[i].target];
-            if (!(masks[items[i].set] & reach[l - 1]) || d > kChainMaxWords - l) continue;
-            li.push_back({d, i});
-            auto s = ls.emplace(items[i].set, d);
-            if (!s.second && d < s.first->second) s.first->second = d;
-            lt.emplace(items[i].target, d);
-        }
-        auto emit = [&lists](std::vector<std::pair<uint32_t, uint32_t>> e, uint32_t *start, uint32_t *below) {
-            std::sort(e.begin(), e.end());
-            *start = (uint32_t)lists.size();
-            for (const auto &x : e) lists.push_back(x.second);
-            for (uint32_t j = 0; j <= kChainMaxWords; j++)
-                below[j] = (uint32_t)(std::lower_bound(e.begin(), e.end(), std::make_pair(j, 0u)) - e.begin());
-        };
-        std::vector<std::pair<uint32_t, uint32_t>> es, et;
-        for (const auto &s : ls) es.push_back({s.second, s.first});
-        for (const auto &t : lt) et.push_back({t.second, t.first});
-        emit(li, &v.item0, v.items);
-        emit(es, &v.set0, v.sets);
-        emit(et, &v.state0, v.states);
-    }
+    g->weighted = net.weighted;
+    std::copy(c.lv, c.lv + kChainMaxWords, g->lv);
 
-    g->items_at = masks.size();
-    g->lists_at = g->items_at + items.size() * 2;
-    g->final_at = g->lists_at + (lists.size() + 1) / 2;
-    std::vector<unsigned long long> blob(g->final_at + (S + 7) / 8, 0ull);
-    std::memcpy(blob.data(), masks.data(), masks.size() * 8);
-    if (!items.empty()) std::memcpy(blob.data() + g->items_at, items.data(), items.size() * sizeof(GramItem));
-    if (!lists.empty()) std::memcpy(blob.data() + g->lists_at, lists.data(), lists.size() * 4);
+    g->items_at = c.masks.size();
+    g->lists_at = g->items_at + c.items.size() * 2;
+    g->final_at = g->lists_at + (c.lists.size() + 1) / 2;
+    size_t end = g->final_at + (S + 7) / 8;
+    if (g->weighted) {  // a grammar without a nonzero cost uploads what it always has
+        g->cost_off_at = end;
+        g->costs_at = g->cost_off_at + (c.cost_off.size() + 1) / 2;
+        g->final_cost_at = g->costs_at + (c.costs.size() + 1) / 2;
+        end = g->final_cost_at + (S + 1) / 2;
+    }
+    std::vector<unsigned long long> blob(end, 0ull);
+    std::memcpy(blob.data(), c.masks.data(), c.masks.size() * 8);
+    if (!c.items.empty()) std::memcpy(blob.data() + g->items_at, c.items.data(), c.items.size() * sizeof(GramItem));
+    if (!c.lists.empty()) std::memcpy(blob.data() + g->lists_at, c.lists.data(), c.lists.size() * 4);
     for (uint32_t s = 0; s < S; s++) ((uint8_t *)(blob.data() + g->final_at))[s] = final_state[s] ? 1 : 0;
+    if (g->weighted) {
+        std::memcpy(blob.data() + g->cost_off_at, c.cost_off.data(), c.cost_off.size() * 4);
+        if (!c.costs.empty()) std::memcpy(blob.data() + g->costs_at, c.costs.data(), c.costs.size() * 4);
+        std::memcpy(blob.data() + g->final_cost_at, net.final_cost.data(), (size_t)S * 4);
+    }
     int rc = g->blob.reserve(blob.size());
     if (!rc) {
         const hipError_t e = hipMemcpy(g->blob.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice);
@@ -184,6 +124,12 @@ int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, 
     }
     *out = g;
     return SR_OK;
+}
+
+int sr_grammar_create(sr_engine *h, uint32_t n_states, const sr_gram_arc *arcs, uint32_t n_arcs, const uint8_t *final_state,
+                      sr_grammar **out)
+{
+    return sr_grammar_create_weighted(h, n_states, arcs, nullptr, n_arcs, final_state, nullptr, out);
 }
 
 void sr_grammar_destroy(sr_grammar *g)
@@ -237,13 +183,14 @@ int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d
     a.final_state = (const uint8_t *)(g->blob.p + g->final_at);
     a.C = h->s_ch_e.p + per * p.e_row;  // behind the prefix costs of the largest group
     for (uint32_t l = 1; l <= max_words; l++) a.lv[l - 1] = gram_level_of(g, l, max_words);
+    const GramCosts w = g->costs();
     for (uint32_t r0 = 0; r0 < n_rows; r0 += per) {  // the groups follow each other on s: one scratch serves them all
         a.c = ChainArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                         std::min(per, n_rows - r0), h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,
                         g->tpl_len, p.g.chunk_cols, p.g.n_chunks, max_words, n_words_exact, skip_cost, word_cost, h->s_ch_a.p,
                         h->s_ch_e.p, t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0,
                         d_words + (size_t)r0 * max_words, d_level_cost ? d_level_cost + (size_t)r0 * max_words : nullptr};
-        launch_gram(a, s);
+        launch_gram(a, g->weighted ? &w : nullptr, s);
     }
     HIP_TRY(hipGetLastError());
     return mark_scratch_user(h, s);

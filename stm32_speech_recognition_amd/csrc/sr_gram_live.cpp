@@ -130,8 +130,9 @@ int launch_push(sr_gram_live *l, const DecodeLivePlan &pl, const int16_t *d_mfcc
 {
     if (!pl.rows) return SR_OK;
     const GramLiveArgs a = live_args(l, d_mfcc, row_stride, d_rec, d_words, d_level_cost);
-    if (pl.max_frames) launch_gram_live(a, s);
-    else launch_gram_live_trace(a, s);  // (PCM) samples, but no new frame: the parse so far again
+    const GramCosts w = l->g->costs();
+    if (pl.max_frames) launch_gram_live(a, l->g->weighted ? &w : nullptr, s);
+    else launch_gram_live_trace(a, l->g->weighted ? &w : nullptr, s);  // (PCM) samples, but no new frame: the parse so far again
     HIP_TRY(hipGetLastError());
     return SR_OK;
 }
@@ -369,7 +370,8 @@ int sr_gram_live_end(sr_gram_live *l, const uint32_t *channels, uint32_t n_ch, s
     HostOutputs o;
     if (int rc = o.reserve(n_out, l->max_words, level_cost != nullptr)) return rc;
     if (int rc = upload_chan(l, chan, nullptr)) return rc;
-    launch_gram_live_trace(live_args(l, nullptr, 0, o.rec.p, o.words.p, level_cost ? o.lc.p : nullptr), nullptr);
+    const GramCosts w = l->g->costs();
+    launch_gram_live_trace(live_args(l, nullptr, 0, o.rec.p, o.words.p, level_cost ? o.lc.p : nullptr), l->g->weighted ? &w : nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     if (int rc = o.down(n_out, l->max_words, rec, words, level_cost)) return rc;
     decode_live_reset(l->m, kGramLiveBound, order);

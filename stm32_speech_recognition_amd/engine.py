@@ -666,11 +666,13 @@ class Engine:
         return out
 
     # ---- grammar-constrained decoding ---------------------------------------------------------------------
-    def grammar(self, n_states, arcs, final):
-        """sr_grammar_create: a Grammar compiled against the current store and word map.  States 0..n_states - 1, state 0
-        the start; arcs = (from, to, word) triples, word a label of the word map; final = one flag per state.  The three
-        grammar_* helpers return exactly these arguments: eng.grammar(*grammar_sequence([...]))."""
-        return Grammar(self, n_states, arcs, final)
+    def grammar(self, n_states, arcs, final, arc_cost=None, final_cost=None):
+        """sr_grammar_create[_weighted]: a Grammar compiled against the current store and word map.  States 0..n_states - 1,
+        state 0 the start; arcs = (from, to, word label) triples; final[s] != 0 flags the final states.  arc_cost [n_arcs] and
+        final_cost [n_states] (each None = all 0, at most 2^24, final_cost 0 on a state that is not final) are added to the
+        acoustic cost of a parse: the weighted grammars of the header.  The grammar_* helpers return exactly these arguments:
+        eng.grammar(*grammar_sequence([...])), eng.grammar(*grammar_bigram(...))."""
+        return Grammar(self, n_states, arcs, final, arc_cost, final_cost)
 
     def decode_grammar(self, gram, mfcc, frames, max_words=8, n_words=0, skip_cost=None, word_cost=0):
         """decode_words() under a Grammar (sr_decode_grammar_dp): the cheapest parse among the word sequences the grammar
@@ -1349,11 +1351,35 @@ def grammar_word_pairs(labels, allowed_pairs, first=None, last=None):
     return 1 + len(labels), arcs, [0] + [int(last is None or w in last) for w in labels]
 
 
-class Grammar:
-    """One sr_grammar handle: a word network compiled against its engine's store and word map (Engine.grammar).  Setting
-    the templates or the word map again makes it stale: decode calls then raise until a new one is compiled."""
+def grammar_bigram(labels, cost, first_cost=None, last_cost=None):
+    """A weighted word-pair (bigram) grammar: one state per word (1 + its index in labels) plus the start.  cost[a][b] is the
+    cost of word b after word a, None = forbidden; first_cost[w] the cost of starting with w, None = forbidden; last_cost[w]
+    the final cost after w, None = the parse may not end there.  All three are indexed by label (nested sequences or dicts);
+    first_cost / last_cost None: every word may start / end at cost 0.
+    Returns (n_states, arcs, final, arc_cost, final_cost) for Engine.grammar()."""
+    labels = list(dict.fromkeys(int(w) for w in labels))
+    st = {w: 1 + i for i, w in enumerate(labels)}
+    arcs, arc_cost = [], []
+    for w in labels:
+        if first_cost is None or first_cost[w] is not None:
+            arcs.append((0, st[w], w))
+            arc_cost.append(0 if first_cost is None else int(first_cost[w]))
+    for a in labels:
+        for b in labels:
+            if cost[a][b] is not None:
+                arcs.append((st[a], st[b], b))
+                arc_cost.append(int(cost[a][b]))
+    final = [0] + [int(last_cost is None or last_cost[w] is not None) for w in labels]
+    final_cost = [0] + [0 if last_cost is None or last_cost[w] is None else int(last_cost[w]) for w in labels]
+    return 1 + len(labels), arcs, final, arc_cost, final_cost
 
-    def __init__(self, eng, n_states, arcs, final):
+
+class Grammar:
+    """One sr_grammar handle: a word network, with or without costs on its arcs and final states, compiled against its
+    engine's store and word map (Engine.grammar).  Setting the templates or the word map again makes it stale: decode calls
+    then raise until a new one is compiled."""
+
+    def __init__(self, eng, n_states, arcs, final, arc_cost=None, final_cost=None):
         self.eng, self.L, self.g = eng, eng.L, None
         a = np.zeros(len(arcs), dtype=GRAM_ARC_DTYPE)
         for i, arc in enumerate(arcs):
@@ -1361,7 +1387,14 @@ class Grammar:
         final = np.ascontiguousarray(final, dtype=np.uint8)
         assert len(final) == n_states
         g = C.c_void_p()
-        eng._check(self.L.sr_grammar_create(eng.h, C.c_uint32(n_states), _vp(a), C.c_uint32(len(a)), _vp(final), C.byref(g)))
+        if arc_cost is None and final_cost is None:
+            eng._check(self.L.sr_grammar_create(eng.h, C.c_uint32(n_states), _vp(a), C.c_uint32(len(a)), _vp(final), C.byref(g)))
+        else:
+            ac = None if arc_cost is None else np.ascontiguousarray(arc_cost, dtype=np.uint32)
+            fc = None if final_cost is None else np.ascontiguousarray(final_cost, dtype=np.uint32)
+            assert (ac is None or len(ac) == len(a)) and (fc is None or len(fc) == n_states)
+            eng._check(self.L.sr_grammar_create_weighted(eng.h, C.c_uint32(n_states), _vp(a), None if ac is None else _vp(ac), C.c_uint32(len(a)),
+                                                         _vp(final), None if fc is None else _vp(fc), C.byref(g)))
         self.g, self.n_states = g, n_states
 
     def plan(self, max_words=8):
