@@ -920,6 +920,66 @@ int sr_gram_live_push_pcm(sr_gram_live *l, const uint16_t *pcm, uint64_t pcm_str
 int sr_gram_live_end(sr_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
                      uint32_t *level_cost, sr_chain_live_row *rows, uint32_t *n_rows);
 
+/* ------------------------------------------------------------------ word alternatives: every template over a decoded span
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The decoders above say which word they chose for a stretch of frames, not how
+ * close the second-best word was on it: A_l(p) keeps one candidate per end frame.  This section scores EVERY template over a
+ * fixed span of frames, start and end pinned; the score rows are sr_nbest_batch_dev's input, so word map, N-best and count
+ * apply per decoded word: a runner-up and a rejection margin, a correction list.  No existing call, record or score changes.
+ * For a feature row in[0..N) (N clamped to max_frames), a span (S, e) and a valid slot k of M frames:
+ *   F_k(S,e)  the minimum over the word paths of the connected-word section from (S, 0) to (e, M-1) -- steps (+1,+1), (+1,0),
+ *             (0,+1), every horizontal or vertical step directly after a diagonal one, the start cell of the non-diagonal
+ *             kind -- of the sum of d = get_dis (DTW.C:45-62): the spotter's recurrence with the one start column S.
+ *   reach     with L = e - S + 1, F is finite exactly when M/2 + 1 <= L <= 2M - 1 (integer division; M = 1: L = 1 only).
+ *   q_k(S,e)  F / (L + M): the spotter's q, the decoder's sr_chain_word.dis.
+ *   score row scores[k] = F_k in mode SR_SPAN_ACC, q_k in mode SR_SPAN_DIS; SR_DIS_ERR for an invalid slot, an unreachable
+ *             (L, M) and an invalid span: start or end all ones, start > end, or end >= N.  Nothing outside rows [0, N) of the
+ *             feature record is read.  Costs stay below 2^31: d <= 65 536 and a path has at most 2M - 1 cells.
+ * Three facts (tests/test_span_ref.py, tests/test_span.py):
+ *   1. For every word row ANY decoder of this library emits -- unconstrained, grammar, weighted grammar, live -- F_slot(start,
+ *      end) == acc and q_slot == dis: acc is the word's own path cost, and the tuple minimum keeps the cheapest path from its
+ *      start.
+ *   2. For the unconstrained decoder the decoded slot is the first minimum in slot order of F_k(start, end) over the valid
+ *      slots: another slot with a smaller F, or an equal F and a smaller index, would have won A_l(end + 1) under the (cost,
+ *      start, slot) rule.  So entry 0 of sr_nbest_batch over the span's SR_SPAN_ACC row has slot == words[i].slot and dis ==
+ *      words[i].acc, under any word map.
+ *   3. Under a grammar fact 2 need not hold: the grammar may forbid the acoustically best word.  Entry 0 is then the best word
+ *      REGARDLESS of syntax.
+ * Out of scope: alternatives restricted to a grammar's arcs; sessions that score spans themselves (they do not keep the
+ * feature history: a live or grammar caller who keeps its feature rows runs the stage call on the emitted word rows); free
+ * span ends; N-best sequences. */
+#define SR_SPAN_ACC 0u
+#define SR_SPAN_DIS 1u
+/* Stage level, DEVICE buffers: d_mfcc / d_in_frames / frames_stride as for sr_decode_words_dp_dev.  d_words[n_rows]
+ * [words_per_row]: entry [r][i] is a span of feature row r and only its start and end are read -- any decoder's word rows
+ * unchanged (entries at or beyond n_words are all ones: invalid spans), or spans of the caller's own making.  d_scores
+ * [n_rows * words_per_row][K] u32 (required): every row is written whole, every score exactly once; two runs give the same
+ * bytes.  words_per_row 1..16.  One asynchronous operation on `stream`; the host knows every count, nothing is read back.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_NO_TEMPLATES; SR_ERR_BAD_ARG
+ * for a null pointer, frames_stride 0, words_per_row outside 1..16, a mode other than the two above, more than 2^31 - 1
+ * spans, a store of more than 65 536 slots or one whose longest template exceeds sr_decode_geometry's out[2], d_words and
+ * d_scores that overlap. */
+int sr_score_word_spans_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                            uint32_t words_per_row, const sr_chain_word *d_words, uint32_t mode, uint32_t *d_scores, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_score_word_spans(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                        uint32_t words_per_row, const sr_chain_word *words, uint32_t mode, uint32_t *scores);
+/* The unconstrained decoder with alternatives, DEVICE buffers: sr_decode_words_dp_dev as it stands (its arguments, its rules,
+ * the same bytes in d_rec / d_words / d_level_cost), then the span scores of its d_words in `mode`, then sr_nbest_batch_dev's
+ * reduction over those n_rows * max_words score rows.  d_alts[n_rows][max_words][n_best] (required), d_n_matched[n_rows]
+ * [max_words] (optional), d_span_scores[n_rows * max_words][K] (optional; NULL: the scores live in the engine's scratch).
+ * Word positions at or beyond n_words get sr_nbest_batch's "no candidate" entries and n_matched 0.  n_best 1..SR_NBEST_MAX.
+ * ONE asynchronous operation on `stream`.  Errors, before anything is launched or written: those of sr_decode_words_dp_dev,
+ * of sr_score_word_spans_dev and of sr_nbest_batch_dev, and SR_ERR_BAD_ARG for outputs that overlap. */
+int sr_decode_words_alts_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                             uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *d_rec,
+                             sr_chain_word *d_words, uint32_t *d_level_cost, uint32_t n_best, uint32_t mode, sr_nbest_entry *d_alts,
+                             uint32_t *d_n_matched, uint32_t *d_span_scores, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_decode_words_alts(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                         uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec,
+                         sr_chain_word *words, uint32_t *level_cost, uint32_t n_best, uint32_t mode, sr_nbest_entry *alts,
+                         uint32_t *n_matched, uint32_t *span_scores);
+
 /* ------------------------------------------------------------------ full-DP alignment and word models from many examples
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  sr_dtw_dp_batch_dev says how far a feature row is from a template; this
  * section says HOW the two were aligned, and builds word models from many examples on top of that (DTW barycentre
@@ -1112,6 +1172,8 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "chain_rows"                     rows per launch group of the connected-word decoder (default: what 256 MiB of scratch
  *                                    hold); read per call and by sr_decode_geometry; the grammar decoder and sr_grammar_plan
  *                                    read it likewise
+ *   "span_groups"                    groups of four spans per launch of the span scorer (default 65 535, the grid's limit;
+ *                                    a launch holds one feature row's spans at least); read per call
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

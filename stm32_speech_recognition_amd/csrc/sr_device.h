@@ -31,6 +31,7 @@ enum DevHook {
     kHookAlignGlobal,     // "align_marks_global": the aligner keeps its predecessor marks in global scratch whatever fits the LDS
     kHookChainChunk,      // "chain_chunk_cols": columns per chunk of the connected-word decoder (1..16383; read per call)
     kHookChainRows,       // "chain_rows": rows per launch group of the connected-word decoder (read per call and by sr_decode_geometry)
+    kHookSpanGroups,      // "span_groups": groups of spans per launch of the span scorer (default 65 535, the grid's limit; read per call)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -382,6 +383,28 @@ struct ChainArgs {
     uint32_t *level_cost;       // optional [n_rows][max_words]
 };
 void launch_chain(const ChainArgs &a, hipStream_t s);  // init, max_words x (k_chain_words, k_chain_close), k_chain_trace
+
+// word alternatives (k_span.hip): the best path of every template over fixed spans of frames, start and end pinned.  Span i
+// = words[i] (only start and end are read) lies in feature row i / words_per_row; one wave per (span, slot).
+struct SpanArgs {
+    const int16_t *mfcc;        // [n_rows][max_frames][12]
+    const uint32_t *in_frames;  // frame count of row r at in_frames[r * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t max_frames;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a boundary column
+    const sr_chain_word *words; // [n_spans]
+    uint32_t words_per_row;     // >= 1
+    uint32_t n_spans;           // n_rows * words_per_row
+    uint32_t mode;              // SR_SPAN_ACC / SR_SPAN_DIS
+    uint32_t max_groups;        // groups of kSpotWaves spans per launch, 1..65 535
+    uint32_t *scores;           // [n_spans][K]
+};
+void launch_span(const SpanArgs &a, hipStream_t s);
 
 // grammar-constrained decoding (k_gram.hip): k_chain's levels over a word network of n_states states.  c is the decoder's
 // argument block with the scratch in the grammar's layout: c.A[row][level 1..max_words][state][max_frames + 1], c.E[row][level

@@ -157,6 +157,7 @@ const char *chain_allow_lds(uint32_t bytes);
 const char *chain_live_allow_lds(uint32_t bytes);
 const char *gram_allow_lds(uint32_t bytes);
 const char *gram_live_allow_lds(uint32_t bytes);
+const char *span_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

@@ -217,6 +217,10 @@ struct sr_engine {
     // connected-word decoding (sr_chain.cpp): the keys and prefix costs of one launch group
     DevBuf<unsigned long long> s_ch_a;
     DevBuf<uint32_t> s_ch_e;
+    // word alternatives (sr_span.cpp): the span score rows of a call that was handed no buffer for them, and the host-buffer
+    // forms' device copies of their word rows
+    DevBuf<uint32_t> s_span_scores;
+    DevBuf<sr_chain_word> s_span_words;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant

@@ -47,6 +47,8 @@ CH_OK, CH_NONE = 0, 1
 VAD_MASK_WORDS, VAD_MASK_FRAMES = 16, 63
 # sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
 CHAIN_LIVE_ROW_DTYPE = np.dtype([("channel", "<u4"), ("frames", "<u4")])
+# sr_score_word_spans / sr_decode_words_alts modes: a span score row holds path costs, or costs / (L + M)
+SPAN_ACC, SPAN_DIS = 0, 1
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
 assert CHAIN_REC_DTYPE.itemsize == 16 and CHAIN_WORD_DTYPE.itemsize == 32 and CHAIN_LIVE_ROW_DTYPE.itemsize == 8
 assert ALIGN_DTYPE.itemsize == 16 and TRAIN_STAT_DTYPE.itemsize == 16
@@ -664,6 +666,81 @@ class Engine:
                                                  _vp(out["words"]), _vp(out["level_cost"]), _vp(out["mfcc"]), _vp(out["frm_num"]),
                                                  _vp(out["status"])))
         return out
+
+    # ---- word alternatives ----------------------------------------------------------------------------------
+    def score_word_spans(self, mfcc, frames, words, mode=0):
+        """OPT-IN span scorer (sr_score_word_spans): the best path of EVERY template over fixed spans of frames, start and end
+        pinned.  mfcc int16 [n_rows, max_frames, 12], frames uint32 [n_rows], words CHAIN_WORD_DTYPE [n_rows, words_per_row]
+        (any decoder's word rows, or spans of the caller's making: only start and end are read; all ones = no span); mode
+        SPAN_ACC = path costs, SPAN_DIS = cost / (L + M).  Returns scores uint32 [n_rows, words_per_row, K], DIS_ERR where
+        the slot has no path over the span: the layout nbest() takes."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        words = np.ascontiguousarray(words, dtype=CHAIN_WORD_DTYPE)
+        n = mfcc.shape[0]
+        assert len(frames) == n and words.ndim == 2 and words.shape[0] == n
+        sc = np.zeros((n, words.shape[1], self.n_templates), dtype=np.uint32)
+        self._check(self.L.sr_score_word_spans(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), C.c_uint32(words.shape[1]),
+                                               _vp(words), C.c_uint32(mode), _vp(sc)))
+        return sc
+
+    def score_word_spans_dev(self, mfcc, frames, words, scores, mode=0, frames_stride=1, stream=None):
+        """sr_score_word_spans_dev on device tensors: mfcc int16 [n_rows, max_frames, 12]; frames as for spot_dev; words int32
+        [n_rows, words_per_row, 8] (decode_words_dev's, decode_grammar_dev's or a session's word rows as they are); scores
+        int32 [n_rows, words_per_row, K].  Asynchronous on `stream`; returns scores."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and words.is_contiguous() and scores.is_contiguous()
+        n = mfcc.shape[0]
+        wpr = words.numel() // (8 * max(n, 1))
+        assert words.numel() == n * wpr * 8 and scores.numel() == n * wpr * self.n_templates
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_score_word_spans_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                   C.c_uint32(wpr), _vp(words), C.c_uint32(mode), _vp(scores), C.c_void_p(stream)))
+        return scores
+
+    def decode_words_alts(self, mfcc, frames, max_words=8, n_best=4, mode=0, n_words=0, skip_cost=None, word_cost=0, want_scores=False):
+        """decode_words() with alternatives (sr_decode_words_alts): per decoded word the n_best best words of the store over
+        that word's frames, under the engine's word map.  Returns decode_words()'s (rec, words, level_cost) -- the same
+        bytes -- plus alts NBEST_DTYPE [n_rows, max_words, n_best] and n_matched uint32 [n_rows, max_words], and with
+        want_scores the span scores uint32 [n_rows, max_words, K].  In mode SPAN_ACC entry 0 of a word is the decoded slot
+        at its `acc`; alts[.., 1]["dis"] - alts[.., 0]["dis"] is the word's margin over the runner-up."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, max_words), dtype=CHAIN_WORD_DTYPE)
+        lc = np.zeros((n, max_words), dtype=np.uint32)
+        alts, nm = np.zeros((n, max_words, max(n_best, 0)), dtype=NBEST_DTYPE), np.zeros((n, max_words), dtype=np.uint32)
+        sc = np.zeros((n, max_words, self.n_templates), dtype=np.uint32) if want_scores else None
+        self._check(self.L.sr_decode_words_alts(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), C.c_uint32(max_words),
+                                                C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(rec),
+                                                _vp(words), _vp(lc), C.c_uint32(n_best), C.c_uint32(mode), _vp(alts), _vp(nm), _vp(sc)))
+        return (rec, words, lc, alts, nm, sc) if want_scores else (rec, words, lc, alts, nm)
+
+    def decode_words_alts_dev(self, mfcc, frames, rec, words, alts, level_cost=None, n_matched=None, span_scores=None, max_words=8,
+                              mode=0, n_words=0, skip_cost=None, word_cost=0, frames_stride=1, stream=None):
+        """sr_decode_words_alts_dev on device tensors: decode_words_dev()'s tensors plus alts int32 [n_rows, max_words, n_best,
+        4], n_matched (optional) int32 [n_rows, max_words] and span_scores (optional) int32 [n_rows, max_words, K].  One
+        asynchronous operation on `stream`; returns (rec, words, level_cost, alts, n_matched, span_scores)."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous() and alts.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and words.numel() == n * max_words * 8
+        assert level_cost is None or (level_cost.is_contiguous() and level_cost.numel() == n * max_words)
+        n_best = alts.numel() // (4 * max(n * max_words, 1))
+        assert alts.numel() == n * max_words * n_best * 4
+        assert n_matched is None or (n_matched.is_contiguous() and n_matched.numel() == n * max_words)
+        assert span_scores is None or (span_scores.is_contiguous() and span_scores.numel() == n * max_words * self.n_templates)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_decode_words_alts_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                    C.c_uint32(max_words), C.c_uint32(n_words), C.c_uint32(self._skip(skip_cost)),
+                                                    C.c_uint32(word_cost), _vp(rec), _vp(words), _vp(level_cost), C.c_uint32(n_best),
+                                                    C.c_uint32(mode), _vp(alts), _vp(n_matched), _vp(span_scores), C.c_void_p(stream)))
+        return rec, words, level_cost, alts, n_matched, span_scores
 
     # ---- grammar-constrained decoding ---------------------------------------------------------------------
     def grammar(self, n_states, arcs, final, arc_cost=None, final_cost=None):
