@@ -286,6 +286,33 @@ __device__ __forceinline__ void lds_rows2(uint32_t row_off, uint32_t nrm_off, Ro
     r0 = row_from2(a0, a1, a2, np[0]);
     r1 = row_from2(b0, b1, b2, np[1]);
 }
+// ---- both advances of a step of k_dtw_lds as exec-masked blocks, without a test around either (F::advance) ----
+// Under the lanes that advance y (k_dg | k_up) the next template row becomes the current one, y1 and the row offset step and
+// the row after it is fetched from L2; under the lanes that advance x (every live lane but k_up) the cursors into the LDS
+// image step, ub(x+1) becomes ub(x) and rows x-1 / x are read again.  Lanes that do not advance load nothing.  Whatever runs
+// under a narrowed exec is ONE asm statement (nothing else may be scheduled between its first write of exec and its last;
+// exec is `live` on entry and on exit), and the loads are inside it because they need the masks -- so the compiler does
+// not count them: the kernel waits for them itself (F::wait_lds / F::wait_tpl at the top of the step, once more behind
+// the loop).  s_or / s_andn2 write SCC: clobbered.  The pieces both row formats share:
+#define SR_DTW_ADV_Y                                                                                                    \
+    "v_add_u32 %[t_off], %[t_stride], %[t_off]\n\t"
+#define SR_DTW_ADV_X(ROWBYTES)                                                                                          \
+    "v_add_u32 %[y1], 1, %[y1]\n\t"                                                                                    \
+    "s_andn2_b64 exec, %[live], %[k_up]\n\t"                                                                           \
+    "v_add_u32 %[in_off], " ROWBYTES ", %[in_off]\n\t"                                                                 \
+    "v_add_u32 %[nrm_off], 4, %[nrm_off]\n\t"
+#define SR_DTW_ADV_END                                                                                                  \
+    "ds_read2_b32 %[an], %[nrm_off] offset1:1\n\t"                                                                     \
+    "v_add_u32 %[xB], 1, %[xB]\n\t"                                                                                    \
+    "v_mov_b32 %[ubA1], %[ubB1]\n\t"                                                                                   \
+    "s_mov_b64 exec, %[live]"
+#define SR_DTW_ADV_OPS                                                                                                  \
+    [t_off] "+v"(t_off), [y1] "+v"(y1), [in_off] "+v"(in_off), [nrm_off] "+v"(nrm_off), [xB] "+v"(xB), [ubA1] "+v"(ubA1)
+#define SR_DTW_ADV_INS                                                                                                  \
+    [t_stride] "s"(t_stride), [ubB1] "v"(ubB1), [k_dg] "s"(k_dg), [k_up] "s"(k_up), [live] "s"(live), [tbase] "s"(tbase)
+#define SR_DTW_ADV_ARGS                                                                                                 \
+    Row &cm, Row &nm, Row &ci, Row &ni, const char *tbase, uint32_t &t_off, uint32_t t_stride, int &y1, uint32_t &in_off,     \
+        uint32_t &nrm_off, int &xB, int &ubA1, int ubB1, uint64_t k_dg, uint64_t k_up, uint64_t live
 // ---- the row formats of k_dtw_lds: 12 coefficients (the reference, and narrower GENERIC rows zero-padded) or 16 (GENERIC
 // front end, n_coef 13..16, zero-padded).  LDS image of an utterance: kWords packed pairs per row + a separate array of norms;
 // store rows in HBM / L2: -2*coef in kWords words, the squared norm in the next word, padded to kTplBytes.
@@ -300,7 +327,57 @@ struct Dtw12 {
     }
     static __device__ __forceinline__ void rows2(uint32_t row_off, uint32_t nrm_off, Row &r0, Row &r1) { lds_rows2(row_off, nrm_off, r0, r1); }
     static __device__ __forceinline__ int dot_acc(const Row &a, const Row &b, int c) { return dot_rows_acc(a, b, c); }
-    static __device__ __forceinline__ void copy(Row &d, const Row &s) { copy_row(d, s); }
+    // (two statements: a register can be handed to an asm statement as part of a pair or as part of a quad, not as both; the
+    // 64-bit moves read the next template row as pairs, the loads fill it as quads)
+    static __device__ __forceinline__ void advance(SR_DTW_ADV_ARGS)
+    {
+        u32x2 c0 = {cm.w[0], cm.w[1]}, c1 = {cm.w[2], cm.w[3]}, c2 = {cm.w[4], cm.w[5]}, c3 = {cm.w[6], cm.w[7]};
+        const u32x2 n0 = {nm.w[0], nm.w[1]}, n1 = {nm.w[2], nm.w[3]}, n2 = {nm.w[4], nm.w[5]}, n3 = {nm.w[6], nm.w[7]};
+        asm volatile("s_or_b64 exec, %[k_dg], %[k_up]\n\t"
+                     "v_pk_mov_b32 %[c0], %[n0], %[n0] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c1], %[n1], %[n1] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c2], %[n2], %[n2] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c3], %[n3], %[n3] op_sel:[0,1]\n\t"
+                     "s_mov_b64 exec, %[live]"
+                     : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3)
+                     : [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [n3] "v"(n3), [k_dg] "s"(k_dg), [k_up] "s"(k_up), [live] "s"(live)
+                     : "scc");
+        cm.w[0] = c0.x, cm.w[1] = c0.y, cm.w[2] = c1.x, cm.w[3] = c1.y, cm.w[4] = c2.x, cm.w[5] = c2.y, cm.w[6] = c3.x, cm.w[7] = c3.y;
+        u32x4 q0 = {nm.w[0], nm.w[1], nm.w[2], nm.w[3]}, q1 = {nm.w[4], nm.w[5], nm.w[6], nm.w[7]};
+        u32x2 a0 = {ci.w[0], ci.w[1]}, a1 = {ci.w[2], ci.w[3]}, a2 = {ci.w[4], ci.w[5]}, b0 = {ni.w[0], ni.w[1]}, b1 = {ni.w[2], ni.w[3]},
+              b2 = {ni.w[4], ni.w[5]}, an = {ci.w[6], ni.w[6]};
+        asm volatile("s_or_b64 exec, %[k_dg], %[k_up]\n\t" SR_DTW_ADV_Y
+                     "global_load_dwordx4 %[q1], %[t_off], %[tbase] offset:16\n\t"
+                     "global_load_dwordx4 %[q0], %[t_off], %[tbase]\n\t" SR_DTW_ADV_X("24")
+                     "ds_read_b64 %[a0], %[in_off]\n\t"
+                     "ds_read_b64 %[a1], %[in_off] offset:8\n\t"
+                     "ds_read_b64 %[a2], %[in_off] offset:16\n\t"
+                     "ds_read_b64 %[b0], %[in_off] offset:24\n\t"
+                     "ds_read_b64 %[b1], %[in_off] offset:32\n\t"
+                     "ds_read_b64 %[b2], %[in_off] offset:40\n\t" SR_DTW_ADV_END
+                     : [q0] "+v"(q0), [q1] "+v"(q1), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [b0] "+v"(b0), [b1] "+v"(b1), [b2] "+v"(b2),
+                       [an] "+v"(an), SR_DTW_ADV_OPS
+                     : SR_DTW_ADV_INS
+                     : "memory", "scc");
+        nm.w[0] = q0.x, nm.w[1] = q0.y, nm.w[2] = q0.z, nm.w[3] = q0.w, nm.w[4] = q1.x, nm.w[5] = q1.y, nm.w[6] = q1.z, nm.w[7] = q1.w;
+        ci.w[0] = a0.x, ci.w[1] = a0.y, ci.w[2] = a1.x, ci.w[3] = a1.y, ci.w[4] = a2.x, ci.w[5] = a2.y, ci.w[6] = an.x;
+        ni.w[0] = b0.x, ni.w[1] = b0.y, ni.w[2] = b1.x, ni.w[3] = b1.y, ni.w[4] = b2.x, ni.w[5] = b2.y, ni.w[6] = an.y;
+    }
+    // the waits for what advance() loaded: the rows of the LDS image, the template row
+    static __device__ __forceinline__ void wait_lds(Row &ci, Row &ni)
+    {
+        u32x2 a0 = {ci.w[0], ci.w[1]}, a1 = {ci.w[2], ci.w[3]}, a2 = {ci.w[4], ci.w[5]}, b0 = {ni.w[0], ni.w[1]}, b1 = {ni.w[2], ni.w[3]},
+              b2 = {ni.w[4], ni.w[5]}, an = {ci.w[6], ni.w[6]};
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(an));
+        ci.w[0] = a0.x, ci.w[1] = a0.y, ci.w[2] = a1.x, ci.w[3] = a1.y, ci.w[4] = a2.x, ci.w[5] = a2.y, ci.w[6] = an.x;
+        ni.w[0] = b0.x, ni.w[1] = b0.y, ni.w[2] = b1.x, ni.w[3] = b1.y, ni.w[4] = b2.x, ni.w[5] = b2.y, ni.w[6] = an.y;
+    }
+    static __device__ __forceinline__ void wait_tpl(Row &nm)
+    {
+        u32x4 q0 = {nm.w[0], nm.w[1], nm.w[2], nm.w[3]}, q1 = {nm.w[4], nm.w[5], nm.w[6], nm.w[7]};
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(q0), "+v"(q1));
+        nm.w[0] = q0.x, nm.w[1] = q0.y, nm.w[2] = q0.z, nm.w[3] = q0.w, nm.w[4] = q1.x, nm.w[5] = q1.y, nm.w[6] = q1.z, nm.w[7] = q1.w;
+    }
 };
 struct Row48 {
     uint32_t w[10];  // w[0..7] coefficients, w[8] norm, w[9] unused
@@ -335,16 +412,65 @@ struct Dtw16 {
         for (int i = 1; i < 8; i++) acc = sdot2(a.w[i], b.w[i], acc);
         return acc;
     }
-    static __device__ __forceinline__ void copy(Row &d, const Row &s)
+    // (two statements, as in Dtw12)
+    static __device__ __forceinline__ void advance(SR_DTW_ADV_ARGS)
     {
-#pragma unroll
-        for (int i = 0; i < 10; i += 2) {
-            u32x2 t;
-            const u32x2 v = {s.w[i], s.w[i + 1]};
-            asm("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(t) : "v"(v));
-            d.w[i] = t.x;
-            d.w[i + 1] = t.y;
-        }
+        u32x2 c0 = {cm.w[0], cm.w[1]}, c1 = {cm.w[2], cm.w[3]}, c2 = {cm.w[4], cm.w[5]}, c3 = {cm.w[6], cm.w[7]}, c4 = {cm.w[8], cm.w[9]};
+        const u32x2 n0 = {nm.w[0], nm.w[1]}, n1 = {nm.w[2], nm.w[3]}, n2 = {nm.w[4], nm.w[5]}, n3 = {nm.w[6], nm.w[7]}, n4 = {nm.w[8], nm.w[9]};
+        asm volatile("s_or_b64 exec, %[k_dg], %[k_up]\n\t"
+                     "v_pk_mov_b32 %[c0], %[n0], %[n0] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c1], %[n1], %[n1] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c2], %[n2], %[n2] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c3], %[n3], %[n3] op_sel:[0,1]\n\t"
+                     "v_pk_mov_b32 %[c4], %[n4], %[n4] op_sel:[0,1]\n\t"
+                     "s_mov_b64 exec, %[live]"
+                     : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3), [c4] "+v"(c4)
+                     : [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [n3] "v"(n3), [n4] "v"(n4), [k_dg] "s"(k_dg), [k_up] "s"(k_up), [live] "s"(live)
+                     : "scc");
+        cm.w[0] = c0.x, cm.w[1] = c0.y, cm.w[2] = c1.x, cm.w[3] = c1.y, cm.w[4] = c2.x, cm.w[5] = c2.y, cm.w[6] = c3.x, cm.w[7] = c3.y;
+        cm.w[8] = c4.x, cm.w[9] = c4.y;
+        u32x4 q0 = {nm.w[0], nm.w[1], nm.w[2], nm.w[3]}, q1 = {nm.w[4], nm.w[5], nm.w[6], nm.w[7]};
+        u32x2 q2 = {nm.w[8], nm.w[9]};
+        u32x2 a0 = {ci.w[0], ci.w[1]}, a1 = {ci.w[2], ci.w[3]}, a2 = {ci.w[4], ci.w[5]}, a3 = {ci.w[6], ci.w[7]}, b0 = {ni.w[0], ni.w[1]},
+              b1 = {ni.w[2], ni.w[3]}, b2 = {ni.w[4], ni.w[5]}, b3 = {ni.w[6], ni.w[7]}, an = {ci.w[8], ni.w[8]};
+        asm volatile("s_or_b64 exec, %[k_dg], %[k_up]\n\t" SR_DTW_ADV_Y
+                     "global_load_dwordx4 %[q0], %[t_off], %[tbase]\n\t"
+                     "global_load_dwordx4 %[q1], %[t_off], %[tbase] offset:16\n\t"
+                     "global_load_dwordx2 %[q2], %[t_off], %[tbase] offset:32\n\t" SR_DTW_ADV_X("32")
+                     "ds_read_b64 %[a0], %[in_off]\n\t"
+                     "ds_read_b64 %[a1], %[in_off] offset:8\n\t"
+                     "ds_read_b64 %[a2], %[in_off] offset:16\n\t"
+                     "ds_read_b64 %[a3], %[in_off] offset:24\n\t"
+                     "ds_read_b64 %[b0], %[in_off] offset:32\n\t"
+                     "ds_read_b64 %[b1], %[in_off] offset:40\n\t"
+                     "ds_read_b64 %[b2], %[in_off] offset:48\n\t"
+                     "ds_read_b64 %[b3], %[in_off] offset:56\n\t" SR_DTW_ADV_END
+                     : [q0] "+v"(q0), [q1] "+v"(q1), [q2] "+v"(q2), [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3), [b0] "+v"(b0),
+                       [b1] "+v"(b1), [b2] "+v"(b2), [b3] "+v"(b3), [an] "+v"(an), SR_DTW_ADV_OPS
+                     : SR_DTW_ADV_INS
+                     : "memory", "scc");
+        nm.w[0] = q0.x, nm.w[1] = q0.y, nm.w[2] = q0.z, nm.w[3] = q0.w, nm.w[4] = q1.x, nm.w[5] = q1.y, nm.w[6] = q1.z, nm.w[7] = q1.w;
+        nm.w[8] = q2.x, nm.w[9] = q2.y;
+        ci.w[0] = a0.x, ci.w[1] = a0.y, ci.w[2] = a1.x, ci.w[3] = a1.y, ci.w[4] = a2.x, ci.w[5] = a2.y, ci.w[6] = a3.x, ci.w[7] = a3.y;
+        ni.w[0] = b0.x, ni.w[1] = b0.y, ni.w[2] = b1.x, ni.w[3] = b1.y, ni.w[4] = b2.x, ni.w[5] = b2.y, ni.w[6] = b3.x, ni.w[7] = b3.y;
+        ci.w[8] = an.x, ni.w[8] = an.y;
+    }
+    static __device__ __forceinline__ void wait_lds(Row &ci, Row &ni)
+    {
+        u32x2 a0 = {ci.w[0], ci.w[1]}, a1 = {ci.w[2], ci.w[3]}, a2 = {ci.w[4], ci.w[5]}, a3 = {ci.w[6], ci.w[7]}, b0 = {ni.w[0], ni.w[1]},
+              b1 = {ni.w[2], ni.w[3]}, b2 = {ni.w[4], ni.w[5]}, b3 = {ni.w[6], ni.w[7]}, an = {ci.w[8], ni.w[8]};
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(an));
+        ci.w[0] = a0.x, ci.w[1] = a0.y, ci.w[2] = a1.x, ci.w[3] = a1.y, ci.w[4] = a2.x, ci.w[5] = a2.y, ci.w[6] = a3.x, ci.w[7] = a3.y;
+        ni.w[0] = b0.x, ni.w[1] = b0.y, ni.w[2] = b1.x, ni.w[3] = b1.y, ni.w[4] = b2.x, ni.w[5] = b2.y, ni.w[6] = b3.x, ni.w[7] = b3.y;
+        ci.w[8] = an.x, ni.w[8] = an.y;
+    }
+    static __device__ __forceinline__ void wait_tpl(Row &nm)
+    {
+        u32x4 q0 = {nm.w[0], nm.w[1], nm.w[2], nm.w[3]}, q1 = {nm.w[4], nm.w[5], nm.w[6], nm.w[7]};
+        u32x2 q2 = {nm.w[8], nm.w[9]};
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(q0), "+v"(q1), "+v"(q2));
+        nm.w[0] = q0.x, nm.w[1] = q0.y, nm.w[2] = q0.z, nm.w[3] = q0.w, nm.w[4] = q1.x, nm.w[5] = q1.y, nm.w[6] = q1.z, nm.w[7] = q1.w;
+        nm.w[8] = q2.x, nm.w[9] = q2.y;
     }
 };
 #ifdef SR_DTW_STATS
@@ -474,19 +600,28 @@ __global__ void __launch_bounds__(1024) k_dtw_lds(const DtwLdsArgs a)
         // count lives on the scalar unit and a lane picks it up once, in the trip it leaves in (round 6; a per-lane v_add per
         // step before)
         uint32_t trips = 1, step = 1;
-        bool cont;
+        // Control flow of the walk (round 10).  The loop is WAVE-UNIFORM: it runs until the last lane of the wave has left, and
+        // a lane that has left (DTW.C:188) is kept out through exec, which the loop itself narrows -- in the trips in which a
+        // lane leaves, and nowhere else -- and restores behind its exit.  `live` is that mask.  What a finished lane still
+        // needs, dis and step, is only ever updated in place (tied asm operands), so its registers keep their values while
+        // the lane is masked out.  The common trip is one straight run of code up to the single branch at its end; the rare
+        // cases (a root that needs care, a lane that leaves) stand out of line.
+        const uint64_t entry = __builtin_amdgcn_ballot_w64(true);
+        uint64_t live = entry, mc;
         do {
+          do {
             // all three candidate squared distances, unconditionally: |m|^2 + |i|^2 + (-2m).i, the norm sum seeds
             // the dot2 accumulator (template rows are stored as -2m, see upload_templates)
             // (x+1, y) first: it needs neither the template row that may still be in flight from the previous step's y advance
+            F::wait_lds(ci, ni);
             const uint32_t d_rt = (uint32_t)F::dot_acc(cm, ni, (int)(F::nrm(cm) + F::nrm(ni)));  // (x+1, y):   get_dis(mdl, in+12)
             __builtin_amdgcn_sched_barrier(0);
+            F::wait_tpl(nm);
             const uint32_t d_up = (uint32_t)F::dot_acc(nm, ci, (int)(F::nrm(nm) + F::nrm(ci)));  // (x, y+1):   get_dis(mdl+12, in)
             const uint32_t d_dg = (uint32_t)F::dot_acc(nm, ni, (int)(F::nrm(nm) + F::nrm(ni)));  // (x+1, y+1)
             // (x+1, y) can only leave through the LOWER bound: the current point is inside, y1 <= ub(x) + 1 = ubA1, and ub is
             // non-decreasing in x (within each piece, and across the junction: ((X1 + c1s2) >> 1) >= 2 X1 + 2 because
             // 3 X1 <= 2 mdl - in), so y1 <= ubB1 always holds for a lane that is not `lost` (round 6: one compare less)
-            bool in_up = (y1 < ubA1), in_rt = (lbB < y1), in_dg = (lbB <= y1) & (y1 < ubB1);
             // DTW.C:152-184 on the SQUARED candidates.  g(d) = (u32)sqrtf((float)d) is monotone, so the step cost is
             // g(min of the admissible candidates) -- one root instead of three -- and "min == right_up" / "min == up"
             // (the tie order of DTW.C:168-184) become g(q) == g(min)  <=>  q < T, T = first d with g(d) = g(min)+1.
@@ -500,22 +635,18 @@ __global__ void __launch_bounds__(1024) k_dtw_lds(const DtwLdsArgs a)
                            m_rt = __builtin_amdgcn_ballot_w64(lbB < y1),
                            m_dg = __builtin_amdgcn_ballot_w64(lbB <= y1) & __builtin_amdgcn_ballot_w64(y1 < ubB1);
             uint32_t m2;
-            {
-                uint64_t ex;
-                // m_dg is the result of an s_and_b64, i.e. SALU-written: no VALU-write -> VALU-read SGPR hazard on the select
-                asm volatile("v_cndmask_b32_e64 %0, -1, %5, %2\n\t"
-                             "s_mov_b64 %1, exec\n\t"
-                             "s_and_b64 exec, %1, %3\n\t"
-                             "v_min_u32 %0, %0, %6\n\t"
-                             "s_and_b64 exec, %1, %4\n\t"
-                             "v_min_u32 %0, %0, %7\n\t"
-                             "s_mov_b64 exec, %1"
-                             : "=&v"(m2), "=&s"(ex)
-                             : "s"(m_dg), "s"(m_rt), "s"(m_up), "v"(d_dg), "v"(d_rt), "v"(d_up)
-                             : "scc");
-            }
-            // the conditions that send the wave down the literal path are collected as LANE MASKS (ballots of the plain
-            // compares, combined on the scalar unit): a bool OR-ed together and balloted afterwards costs two extra VALU ops
+            // m_dg is the result of an s_and_b64, i.e. SALU-written: no VALU-write -> VALU-read SGPR hazard on the select
+            asm volatile("v_cndmask_b32_e64 %0, -1, %5, %2\n\t"
+                         "s_and_b64 exec, %1, %3\n\t"
+                         "v_min_u32 %0, %0, %6\n\t"
+                         "s_and_b64 exec, %1, %4\n\t"
+                         "v_min_u32 %0, %0, %7\n\t"
+                         "s_mov_b64 exec, %1"
+                         : "=&v"(m2)
+                         : "s"(live), "s"(m_dg), "s"(m_rt), "s"(m_up), "v"(d_dg), "v"(d_rt), "v"(d_up)
+                         : "scc");
+            // Every condition of the step is a LANE MASK (the ballot of a plain compare, combined on the scalar unit): a bool
+            // OR-ed together and balloted afterwards costs two extra VALU ops.
             // Root of the step: v_sqrt_f32 is within one ulp of the correctly rounded root r of (float)m2, so floor(pred(s0)) is
             // g = floor(r) or g - 1 (never above: pred(s0) <= r), and it is g - 1 exactly when m2 >= T(mn) -- the threshold the
             // tie tests need anyway.  Round 6: replaces the two-sided bracket floor(succ(s0)) + "s0 > (float)mn" (a convert and a
@@ -531,91 +662,98 @@ __global__ void __launch_bounds__(1024) k_dtw_lds(const DtwLdsArgs a)
                 const uint32_t mp2 = mn + 2;
                 asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(T) : "v"(mn), "v"(mp2), "v"(dl));
             }
-            const bool tie_dg = in_dg & (d_dg < T), tie_up = in_up & (d_up < T);
-            // hard = the lanes that need the literal form (the root, or the root plus one, beyond the staged table); a root that
-            // came out one short (m2 >= T: squares and their close neighbours, about 5e-4 of the lane-steps) is settled inside the branch
-            const uint64_t hard = __builtin_amdgcn_ballot_w64(mn >= tie_g1) | lost;
-            const uint64_t unsafe = __builtin_amdgcn_ballot_w64(m2 >= T) | hard;
-            bool mv_diag = tie_dg, mv_up = tie_up & !tie_dg;
+            // the move (DTW.C:168-184) as two disjoint lane masks: k_dg = the diagonal, k_up = up; neither = right
+            uint64_t k_dg = m_dg & __builtin_amdgcn_ballot_w64(d_dg < T);
+            uint64_t k_up = m_up & __builtin_amdgcn_ballot_w64(d_up < T) & ~k_dg;
+            // ONE test for everything rare: a root that came out one short (m2 >= T: squares and their close neighbours, about
+            // 5e-4 of the lane-steps), a root -- or the root plus one -- beyond the staged table, a lost lane
+            const uint64_t rare = __builtin_amdgcn_ballot_w64(m2 >= T) | __builtin_amdgcn_ballot_w64(mn >= tie_g1) | lost;
 #ifdef SR_DTW_STATS
             {
-                const uint64_t mb = __builtin_amdgcn_ballot_w64(m2 >= T), mr = __builtin_amdgcn_ballot_w64(mn >= tie_g1),
-                               act = __builtin_amdgcn_ballot_w64(true);
+                const uint64_t mb = __builtin_amdgcn_ballot_w64(m2 >= T), mr = __builtin_amdgcn_ballot_w64(mn >= tie_g1);
                 if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)) == 0) {  // first active lane
                     atomicAdd(&g_dtw_stats[0], 1ull);
-                    atomicAdd(&g_dtw_stats[5], (unsigned long long)__builtin_popcountll(act));
-                    if (unsafe) atomicAdd(&g_dtw_stats[1], 1ull);
+                    atomicAdd(&g_dtw_stats[5], (unsigned long long)__builtin_popcountll(live));
+                    if (rare) atomicAdd(&g_dtw_stats[1], 1ull);
                     if (mb) atomicAdd(&g_dtw_stats[2], 1ull);
                     if (mr) atomicAdd(&g_dtw_stats[3], 1ull);
                     if (lost) atomicAdd(&g_dtw_stats[4], 1ull);
                 }
             }
 #endif
-            if (unsafe != 0ull && hard == 0ull) {
-                // the root came out one short on some lanes (m2 >= T(mn) <=> g = mn + 1, exact: T is the first squared distance
-                // whose root is mn + 1): step it, look the next threshold up (mn + 1 < tie_g by the test above), the two tie tests
-                // once more.  Lanes with m2 < T keep everything.
-                const bool shrt = m2 >= T;
-                mn += shrt ? 1u : 0u;
-                const int dl = *(lds_c_i8 *)(uintptr_t)mn;
-                const uint32_t T2 = mn * (mn + 2) + (uint32_t)dl;
-                mv_diag = in_dg & (d_dg < T2);
-                mv_up = in_up & (d_up < T2) & !mv_diag;
-            } else if (unsafe != 0ull) {  // wave-uniform; the literal form: dtw_limit on the three points, three roots, min, equality tests
-                const int x = xB - 1, y = y1 - 1;
-                in_up = !dtw_out(x, y1, X1, X2, (int)in_n, (int)mdl_n);
-                in_rt = !dtw_out(xB, y, X1, X2, (int)in_n, (int)mdl_n);
-                in_dg = !dtw_out(xB, y1, X1, X2, (int)in_n, (int)mdl_n);
-                const uint32_t up = in_up ? cvt_u32(sqrt_rn_int((float)d_up)) : SR_DIS_ERR,
-                               right = in_rt ? cvt_u32(sqrt_rn_int((float)d_rt)) : SR_DIS_ERR,
-                               diag = in_dg ? cvt_u32(sqrt_rn_int((float)d_dg)) : SR_DIS_ERR;
-                mn = diag;  // DTW.C:156-164
-                if (mn > right) mn = right;
-                if (mn > up) mn = up;
-                mv_diag = (mn == diag);  // DTW.C:168-184
-                mv_up = !mv_diag && (mn == up);
-                lost |= __builtin_amdgcn_ballot_w64(!(in_up | in_rt | in_dg));
-            }
-            dis += mn;
-            const bool adv_y = mv_diag || mv_up, adv_x = mv_diag || !mv_up;
-            // the y advance goes first: its template-row loads come from L2 and have the longest way to go before the next
-            // step's distances need them (the kernel runs close to where a wave's serial latency, not the issue port, sets
-            // the pace: 6 waves per SIMD, LDS-limited; this order alone is worth 6 % of the kernel's time)
-            if (adv_y) {
-                y1++;
-                F::copy(cm, nm);
-                asm volatile("v_add_u32 %0, %1, %0" : "+v"(t_off) : "s"(t_stride));
-                nm = tpl_row(t_off);
-            }
-            if (adv_x) {
-                // in-place updates (tied asm operands): without them the compiler builds the new values in fresh
-                // registers and copies them into the loop-carried ones at the end of the block (three v_mov per step)
-                asm volatile("v_add_u32 %0, 1, %0" : "+v"(xB));
-                asm volatile("v_add_u32 %0, %1, %0" : "+v"(in_off) : "n"(F::kLdsRowBytes));
-                asm volatile("v_add_u32 %0, 4, %0" : "+v"(nrm_off));
-                F::rows2(in_off, nrm_off, ci, ni);
-                asm volatile("v_mov_b32 %0, %1" : "+v"(ubA1) : "v"(ubB1));
-                {
-                    int ua, lb;  // (xB << 1) + constant as ONE v_lshl_add_u32 each (the compiler shares 2*xB and spends two adds)
-                    asm("v_lshl_add_u32 %0, %1, 1, 2" : "=v"(ua) : "v"(xB));
-                    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(lb) : "v"(xB), "v"(c2s));
-                    const int ub = (xB + c1s2) >> 1, la = xB >> 1;
-                    const uint64_t m1 = __builtin_amdgcn_ballot_w64(xB < X1), m2x = __builtin_amdgcn_ballot_w64(xB < X2);
-                    // s_nop 1: the masks come straight from v_cmp, and a VALU read of an SGPR written by the VALU needs two
-                    // wait states (the compiler pads its own v_cmp -> v_cndmask pairs the same way)
-                    asm volatile("s_nop 1\n\tv_cndmask_b32_e64 %0, %1, %2, %3" : "+v"(ubB1) : "v"(ub), "v"(ua), "s"(m1));
-                    asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "+v"(lbB) : "v"(lb), "v"(la), "s"(m2x));
+            if (__builtin_expect(rare != 0ull, 0)) {
+                if (((__builtin_amdgcn_ballot_w64(mn >= tie_g1) | lost) == 0ull)) {
+                    // the root came out one short on some lanes (m2 >= T(mn) <=> g = mn + 1, exact: T is the first squared distance
+                    // whose root is mn + 1): step it, look the next threshold up (mn + 1 < tie_g by the test above), the two tie tests
+                    // once more.  Lanes with m2 < T keep everything.
+                    // (in place, here and in the literal form: a new value would cost the common path a copy of the root)
+                    const uint32_t inc = (m2 >= T) ? 1u : 0u;
+                    asm volatile("v_add_u32 %0, %1, %0" : "+v"(mn) : "v"(inc));
+                    const int dl = *(lds_c_i8 *)(uintptr_t)mn;
+                    const uint32_t T2 = mn * (mn + 2) + (uint32_t)dl;
+                    k_dg = m_dg & __builtin_amdgcn_ballot_w64(d_dg < T2);
+                    k_up = m_up & __builtin_amdgcn_ballot_w64(d_up < T2) & ~k_dg;
+                } else {  // the literal form: dtw_limit on the three points, three roots, min, equality tests
+                    const int x = xB - 1, y = y1 - 1;
+                    const bool in_up = !dtw_out(x, y1, X1, X2, (int)in_n, (int)mdl_n), in_rt = !dtw_out(xB, y, X1, X2, (int)in_n, (int)mdl_n),
+                               in_dg = !dtw_out(xB, y1, X1, X2, (int)in_n, (int)mdl_n);
+                    const uint32_t up = in_up ? cvt_u32(sqrt_rn_int((float)d_up)) : SR_DIS_ERR,
+                                   right = in_rt ? cvt_u32(sqrt_rn_int((float)d_rt)) : SR_DIS_ERR,
+                                   diag = in_dg ? cvt_u32(sqrt_rn_int((float)d_dg)) : SR_DIS_ERR;
+                    uint32_t mnl = diag;  // DTW.C:156-164
+                    if (mnl > right) mnl = right;
+                    if (mnl > up) mnl = up;
+                    asm volatile("v_mov_b32 %0, %1" : "+v"(mn) : "v"(mnl));
+                    k_dg = __builtin_amdgcn_ballot_w64(mnl == diag);  // DTW.C:168-184
+                    k_up = __builtin_amdgcn_ballot_w64(mnl == up) & ~k_dg;
+                    lost |= __builtin_amdgcn_ballot_w64(!(in_up | in_rt | in_dg));
                 }
             }
-            trips++;
-            const bool cx = xB <= (int)in_n, cy = y1 <= (int)mdl_n;  // DTW.C:188 (x < in && y < mdl)
-            cont = cx && cy;
-            // (the ballots of the two plain compares, combined on the scalar unit: a ballot of `cont` costs a select and a compare)
-            if ((__builtin_amdgcn_ballot_w64(cx) & __builtin_amdgcn_ballot_w64(cy)) != __builtin_amdgcn_ballot_w64(true)) {  // wave-uniform: only trips in which a lane leaves
-                asm volatile("" : "+v"(step));  // (keeps the block a branch target: if-converted, it is three selects in EVERY trip)
-                if (!cont) step = trips;
+#ifdef SR_DTW_STATS
+            if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)) == 0) {
+                if (!(k_dg | k_up)) atomicAdd(&g_dtw_stats[6], 1ull);       // trips in which no lane advances y
+                if (!(live & ~k_up)) atomicAdd(&g_dtw_stats[7], 1ull);      // ... no lane advances x
             }
-        } while (cont);
+#endif
+            asm volatile("v_add_u32 %0, %1, %0" : "+v"(dis) : "v"(mn));
+            // The advances, without a skip test around either: in the throughput shapes some lane of the wave advances y, and some
+            // lane x, in practically every trip (dtw_stats.py counts the others), so a test costs a scalar round trip in every
+            // trip and saves next to nothing.  y goes first: its template-row loads come from L2 and have the longest way to go
+            // before the next step's distances need them (the kernel runs close to where a wave's serial latency, not the issue
+            // port, sets the pace: 6 waves per SIMD, LDS-limited; this order alone is worth 6 % of the kernel's time).  The
+            // register updates of both sides are one masked block (F::advance), the loads follow under the same masks.
+            F::advance(cm, nm, ci, ni, tbase, t_off, t_stride, y1, in_off, nrm_off, xB, ubA1, ubB1, k_dg, k_up, live);
+            // lb and ub + 1 of the new column x+1.  Both are functions of xB alone, so they are evaluated for every lane: a lane
+            // that did not advance gets the values it had.
+            {
+                int ua, lb;  // (xB << 1) + constant as ONE v_lshl_add_u32 each (the compiler shares 2*xB and spends two adds)
+                asm("v_lshl_add_u32 %0, %1, 1, 2" : "=v"(ua) : "v"(xB));
+                asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(lb) : "v"(xB), "v"(c2s));
+                const int ub = (xB + c1s2) >> 1, la = xB >> 1;
+                const uint64_t m1 = __builtin_amdgcn_ballot_w64(xB < X1), m2x = __builtin_amdgcn_ballot_w64(xB < X2);
+                // s_nop 1: the masks come straight from v_cmp, and a VALU read of an SGPR written by the VALU needs two
+                // wait states (the compiler pads its own v_cmp -> v_cndmask pairs the same way)
+                asm volatile("s_nop 1\n\tv_cndmask_b32_e64 %0, %1, %2, %3" : "+v"(ubB1) : "v"(ub), "v"(ua), "s"(m1));
+                asm volatile("v_cndmask_b32_e64 %0, %1, %2, %3" : "+v"(lbB) : "v"(lb), "v"(la), "s"(m2x));
+            }
+            trips++;
+            // DTW.C:188 (x < in && y < mdl) as the ballots of the two plain compares, combined on the scalar unit
+            mc = __builtin_amdgcn_ballot_w64(xB <= (int)in_n) & __builtin_amdgcn_ballot_w64(y1 <= (int)mdl_n);
+          } while (__builtin_expect(mc == live, 1));
+          // only trips in which a lane leaves come here: the leaving lanes pick their step count up, then exec is narrowed to
+          // the lanes that go on
+          asm volatile("s_andn2_b64 exec, %2, %3\n\t"
+                       "v_mov_b32 %0, %1\n\t"
+                       "s_mov_b64 exec, %3"
+                       : "+v"(step)
+                       : "s"(trips), "s"(live), "s"(mc)
+                       : "scc");
+          lost &= mc;
+          live = mc;
+        } while (live != 0ull);
+        // every lane of the wave is back (the operands tie the division below to this point)
+        // (and nothing that advance() loaded is in flight any more: the registers are free for what follows)
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_mov_b64 exec, %2" : "+v"(dis), "+v"(step) : "s"(entry) : "memory");
         score = dis / step;
     }
     a.d.scores[(size_t)b * K + a.tpl_orig[ks]] = score;
