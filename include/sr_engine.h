@@ -1062,6 +1062,76 @@ int sr_train_models_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_fra
  * out[1] = pairs per launch, out[2] = SR_ALIGN_MAX_FRAMES. */
 int sr_align_geometry(uint32_t max_frames, uint32_t ref_rows, uint32_t out[3]);
 
+/* ------------------------------------------------------------------ word models: clustering a word's examples into templates
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The store holds several templates per word (sr_set_word_map); this section
+ * produces them from a corpus: k-means under DTW -- assign every example to the nearest centroid OF ITS WORD, re-average
+ * each centroid from the examples it received (one DBA iteration of sr_train_models_dp), repeat.  Neither call reads or
+ * writes the engine's template store; no existing call, record or score changes.  pair, d, gate, cells, D, acc, dis, path
+ * and status are those of the section above, verbatim.
+ *   inputs   W words.  Word w owns the example rows [word_start[w], word_start[w+1]) of mfcc[E][max_frames][12] and the
+ *            models [mdl_start[w], mdl_start[w+1]) of cen[M][cen_rows][12] with cen_frames[M].  word_start[W+1] and
+ *            mdl_start[W+1] are HOST arrays, as ex_start is, and ascend from 0; E = word_start[W], M = mdl_start[W].  Every
+ *            word has 1..SR_CLUSTER_MAX models; a word may have no examples.
+ *   score    for example e of word w and model m of w: s(e,m) = the aligner's dis of the pair (row e as input, centroid m as
+ *            reference) -- exactly what sr_dtw_dp_align_dev and sr_dtw_dp_batch_dev give for it -- and SR_DIS_ERR when the
+ *            pair is not SR_AL_OK: an empty row, a failed gate, an unreachable end cell, an invalid centroid (frame count 0
+ *            or above cen_rows), or N above SR_ALIGN_MAX_FRAMES.
+ *   assign   assign[e] = the first minimum in model order of s(e,m) over the models of e's word (the key is (dis, m)), as
+ *            the model's index in [0, M).  If every score is SR_DIS_ERR: assign[e] = SR_CLUSTER_NONE (unassigned) and
+ *            best[e] = SR_DIS_ERR; otherwise best[e] = s(e, assign[e]).
+ *   iteration  assign against the centroid set that ENTERS it, then ONE DBA iteration of sr_train_models_dp's definition
+ *            with model_of = assign: same sums, same s32 division truncating toward zero; rows nobody matched stay, F_m
+ *            never changes, rows past F_m are zero, an invalid centroid is copied through.  A model that received no
+ *            example stays as it is; unassigned examples contribute nothing.  Iterations chain.
+ *   per iteration  stats[n_iter][M] (sr_train_stat): n_ok = the examples assigned to m, acc = the sum of their acc against
+ *            the entering centroid, n_fail = 0.  iter[n_iter] (sr_cluster_iter): n_assigned + n_unassigned = E; n_moved =
+ *            the examples whose assignment differs from the previous iteration's (before the first, every example is
+ *            unassigned); n_empty = the models with n_ok == 0; acc = the sum of stats[.].acc.
+ *   final    assign_out[E] = the assignment of the LAST iteration (made against the set that entered it, not against
+ *            cen_out); cen_out[M][cen_rows][12] in sr_set_templates_dense's layout.
+ *   exact    checked on the host before anything is launched: (examples of WORD w) x min(max_frames, SR_ALIGN_MAX_FRAMES)
+ *            <= 65 535 for every word -- any one model of the word may receive all of them.  All sums are integers and
+ *            all counters integer atomics: two runs give identical bytes.
+ * Out of scope: choosing the number of clusters, splitting or merging clusters, changing a centroid's length, clustering
+ * across words. */
+#define SR_CLUSTER_MAX 16u
+#define SR_CLUSTER_NONE 0xFFFFFFFFu
+typedef struct sr_cluster_iter { /* 24 bytes */
+    uint32_t n_assigned;
+    uint32_t n_unassigned;
+    uint32_t n_moved;
+    uint32_t n_empty;
+    uint64_t acc;
+} sr_cluster_iter;
+/* The stage: which model of its word every example is closest to.  DEVICE buffers as sr_train_models_dp_dev's (d_mfcc,
+ * d_in_frames / frames_stride, d_cen, d_cen_frames); d_assign[E] (required), d_best[E] (optional), d_scores[E]
+ * [SR_CLUSTER_MAX] (optional): s(e, mdl_start[w] + c) in column c, SR_DIS_ERR at and beyond the word's model count.  Every
+ * output row is written whole.  ONE asynchronous operation on `stream`: nothing is read back, no host synchronisation; the
+ * per-example tables (and the scores when d_scores is NULL) live in the engine's scratch.
+ * Errors, before anything is launched or written: those of sr_train_models_dp_dev that apply (SR_ERR_BAD_CONFIG unless
+ * n_coef == 12; SR_ERR_BAD_ARG for a null required pointer, frames_stride 0, cen_rows 0 or above SR_ALIGN_MAX_FRAMES), and
+ * SR_ERR_BAD_ARG for W 0, a word_start or mdl_start that does not ascend from 0, a word with 0 or more than SR_CLUSTER_MAX
+ * models, the bound above, overlapping outputs. */
+int sr_cluster_assign_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride,
+                          const uint32_t *word_start, const uint32_t *mdl_start, uint32_t W, const int16_t *d_cen,
+                          const uint32_t *d_cen_frames, uint32_t cen_rows, uint32_t *d_assign, uint32_t *d_best, uint32_t *d_scores,
+                          void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_cluster_assign(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, const uint32_t *word_start,
+                      const uint32_t *mdl_start, uint32_t W, const int16_t *cen, const uint32_t *cen_frames, uint32_t cen_rows,
+                      uint32_t *assign, uint32_t *best, uint32_t *scores);
+/* The full operation: n_iter (1..16) iterations as ONE asynchronous operation on `stream`.  d_cen_out (required) must not
+ * overlap d_cen_in; d_assign[E], d_stats[n_iter][M] and d_iter[n_iter] are optional, and leaving one out changes nothing
+ * else.  Scores, assignment maps, accumulators and the intermediate centroid set live in the engine's scratch.  Errors as
+ * above, and SR_ERR_BAD_ARG for n_iter outside 1..16. */
+int sr_cluster_models_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride,
+                             const uint32_t *word_start, const uint32_t *mdl_start, uint32_t W, const int16_t *d_cen_in,
+                             const uint32_t *d_cen_frames, uint32_t cen_rows, uint32_t n_iter, int16_t *d_cen_out, uint32_t *d_assign,
+                             sr_train_stat *d_stats, sr_cluster_iter *d_iter, void *stream);
+int sr_cluster_models_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, const uint32_t *word_start,
+                         const uint32_t *mdl_start, uint32_t W, const int16_t *cen_in, const uint32_t *cen_frames, uint32_t cen_rows,
+                         uint32_t n_iter, int16_t *cen_out, uint32_t *assign, sr_train_stat *stats, sr_cluster_iter *iter);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -1174,6 +1244,7 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    read it likewise
  *   "span_groups"                    groups of four spans per launch of the span scorer (default 65 535, the grid's limit;
  *                                    a launch holds one feature row's spans at least); read per call
+ *   "cluster_pairs"                  (example, model) pairs per launch of the clustering score pass (default 2^20); read per call
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

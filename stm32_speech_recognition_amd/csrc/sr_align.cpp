@@ -5,6 +5,15 @@
 
 using namespace sr;
 
+int check_align_common(const sr_engine *h, const AlignIn &in, const void *ref, const void *ref_frames, uint32_t ref_rows, const char *what)
+{
+    if (!h || !in.mfcc || !in.frames || !ref || !ref_frames) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (h->nc != (uint32_t)kCoef) return fail(SR_ERR_BAD_CONFIG, "the full-DP aligner is built for 12-coefficient records");
+    if (!in.frames_stride) return fail(SR_ERR_BAD_ARG, "frames_stride must be at least 1");
+    if (!ref_rows || ref_rows > SR_ALIGN_MAX_FRAMES) return fail(SR_ERR_BAD_ARG, std::string(what) + " must be 1..SR_ALIGN_MAX_FRAMES");
+    return SR_OK;
+}
+
 namespace {
 
 AlignPlan plan_for(uint32_t max_frames, uint32_t ref_rows, const LdsBudget &lds, size_t extra)
@@ -20,25 +29,10 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb)
     return a && b && x < y + nb && y < x + na;
 }
 
-struct AlignIn {  // what both calls take
-    const int16_t *mfcc;
-    const uint32_t *frames;
-    uint32_t frames_stride, n_rows;
-};
-
-int check_common(const sr_engine *h, const AlignIn &in, const void *ref, const void *ref_frames, uint32_t ref_rows, const char *what)
-{
-    if (!h || !in.mfcc || !in.frames || !ref || !ref_frames) return fail(SR_ERR_BAD_ARG, "null argument");
-    if (h->nc != (uint32_t)kCoef) return fail(SR_ERR_BAD_CONFIG, "the full-DP aligner is built for 12-coefficient records");
-    if (!in.frames_stride) return fail(SR_ERR_BAD_ARG, "frames_stride must be at least 1");
-    if (!ref_rows || ref_rows > SR_ALIGN_MAX_FRAMES) return fail(SR_ERR_BAD_ARG, std::string(what) + " must be 1..SR_ALIGN_MAX_FRAMES");
-    return SR_OK;
-}
-
 int check_align(const sr_engine *h, const AlignIn &in, const void *ref, const void *ref_frames, uint32_t ref_rows, uint32_t n_ref,
                 const void *ref_of_row, const sr_align_rec *rec, const uint32_t *span)
 {
-    if (int rc = check_common(h, in, ref, ref_frames, ref_rows, "ref_rows")) return rc;
+    if (int rc = check_align_common(h, in, ref, ref_frames, ref_rows, "ref_rows")) return rc;
     if (!rec) return fail(SR_ERR_BAD_ARG, "null argument");
     if (!n_ref || (!ref_of_row && n_ref < in.n_rows)) return fail(SR_ERR_BAD_ARG, "fewer references than rows and no d_ref_of_row");
     if (overlap(rec, (size_t)in.n_rows * sizeof *rec, span, (size_t)in.n_rows * h->cfg.max_frames * 4))
@@ -73,7 +67,7 @@ int reserve_marks(sr_engine *h, const AlignPlan &p, uint32_t n_rows)
 int check_train(const sr_engine *h, const AlignIn &in, const uint32_t *ex_start, uint32_t M, const int16_t *cen_in, const uint32_t *cen_frames,
                 uint32_t cen_rows, uint32_t n_iter, const int16_t *cen_out, const sr_train_stat *stats, uint32_t *n_ex)
 {
-    if (int rc = check_common(h, in, cen_in, cen_frames, cen_rows, "cen_rows")) return rc;
+    if (int rc = check_align_common(h, in, cen_in, cen_frames, cen_rows, "cen_rows")) return rc;
     if (!ex_start || !cen_out) return fail(SR_ERR_BAD_ARG, "null argument");
     if (!M) return fail(SR_ERR_BAD_ARG, "no models");
     if (n_iter < 1 || n_iter > 16) return fail(SR_ERR_BAD_ARG, "n_iter must be 1..16");
@@ -97,41 +91,57 @@ int check_train(const sr_engine *h, const AlignIn &in, const uint32_t *ex_start,
 int run_train(sr_engine *h, const AlignIn &in, const uint32_t *ex_start, uint32_t M, const int16_t *d_cen_in, const uint32_t *d_cen_frames,
               uint32_t cen_rows, uint32_t n_iter, int16_t *d_cen_out, sr_train_stat *d_stats, hipStream_t s)
 {
-    const uint32_t E = in.n_rows, maxf = h->cfg.max_frames;
-    const AlignPlan p = plan_for(maxf, cen_rows, h->lds, (size_t)maxf * 4 + sizeof(sr_align_rec));
-    const size_t n_cen = (size_t)M * cen_rows, per = std::min(p.pairs, std::max(E, 1u));
+    const uint32_t E = in.n_rows;
+    AlignPlan p;
     int rc;
-    if ((rc = reserve_marks(h, p, E)) || (rc = h->s_al_span.reserve(per * maxf)) || (rc = h->s_al_rec.reserve(per)) ||
-        (rc = h->s_al_map.reserve(std::max(E, 1u))) || (rc = h->s_al_sum.reserve(n_cen * kCoef)) || (rc = h->s_al_cnt.reserve(n_cen)) ||
-        (n_iter > 1 && (rc = h->s_al_cen.reserve(n_cen * kCoef))))
-        return rc;
+    if ((rc = dba_begin(h, E, M, cen_rows, n_iter, &p, s)) || (rc = h->s_al_map.reserve(std::max(E, 1u)))) return rc;
     if (E) {  // (a pageable source is staged before the call returns)
         std::vector<uint32_t> model_of(E);
         for (uint32_t m = 0; m < M; m++) std::fill(model_of.begin() + ex_start[m], model_of.begin() + ex_start[m + 1], m);
         HIP_TRY(hipMemcpyAsync(h->s_al_map.p, model_of.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipMemsetAsync(h->s_al_sum.p, 0, n_cen * kCoef * 4, s));
-    HIP_TRY(hipMemsetAsync(h->s_al_cnt.p, 0, n_cen * 4, s));
     if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_iter * M * sizeof(sr_train_stat), s));
     const int16_t *cur = d_cen_in;
     for (uint32_t it = 0; it < n_iter; it++) {
         // the outputs alternate between the scratch set and d_cen_out so that the last one lands in d_cen_out
         int16_t *next = (n_iter - 1 - it) % 2 == 0 ? d_cen_out : h->s_al_cen.p;
-        sr_train_stat *st = d_stats ? d_stats + (size_t)it * M : nullptr;
-        rc = run_align(h, in, cur, d_cen_frames, cen_rows, M, h->s_al_map.p, nullptr, nullptr, true, p, s, [&](uint32_t r0, uint32_t n) {
-            launch_align_accum(AlignAccumArgs{in.mfcc, in.frames, in.frames_stride, maxf, h->s_al_rec.p, h->s_al_span.p, h->s_al_map.p,
-                                              d_cen_frames, cen_rows, h->s_al_sum.p, h->s_al_cnt.p, st, r0, n},
-                               s);
-        });
-        if (rc) return rc;
-        launch_align_finalise(AlignFinalArgs{cur, next, d_cen_frames, cen_rows, M, h->s_al_sum.p, h->s_al_cnt.p}, s);
-        HIP_TRY(hipGetLastError());
+        if ((rc = dba_iteration(h, in, h->s_al_map.p, M, cur, d_cen_frames, cen_rows, next, d_stats ? d_stats + (size_t)it * M : nullptr, p, s)))
+            return rc;
         cur = next;
     }
     return SR_OK;
 }
 
 }  // namespace
+
+int dba_begin(sr_engine *h, uint32_t E, uint32_t M, uint32_t cen_rows, uint32_t n_iter, AlignPlan *p, hipStream_t s)
+{
+    const uint32_t maxf = h->cfg.max_frames;
+    *p = plan_for(maxf, cen_rows, h->lds, (size_t)maxf * 4 + sizeof(sr_align_rec));
+    const size_t n_cen = (size_t)M * cen_rows, per = std::min(p->pairs, std::max(E, 1u));
+    int rc;
+    if ((rc = reserve_marks(h, *p, E)) || (rc = h->s_al_span.reserve(per * maxf)) || (rc = h->s_al_rec.reserve(per)) ||
+        (rc = h->s_al_sum.reserve(n_cen * kCoef)) || (rc = h->s_al_cnt.reserve(n_cen)) || (n_iter > 1 && (rc = h->s_al_cen.reserve(n_cen * kCoef))))
+        return rc;
+    HIP_TRY(hipMemsetAsync(h->s_al_sum.p, 0, n_cen * kCoef * 4, s));
+    HIP_TRY(hipMemsetAsync(h->s_al_cnt.p, 0, n_cen * 4, s));
+    return SR_OK;
+}
+
+int dba_iteration(sr_engine *h, const AlignIn &in, const uint32_t *d_model_of, uint32_t M, const int16_t *cur, const uint32_t *d_cen_frames,
+                  uint32_t cen_rows, int16_t *next, sr_train_stat *st, const AlignPlan &p, hipStream_t s)
+{
+    const uint32_t maxf = h->cfg.max_frames;
+    int rc = run_align(h, in, cur, d_cen_frames, cen_rows, M, d_model_of, nullptr, nullptr, true, p, s, [&](uint32_t r0, uint32_t n) {
+        launch_align_accum(AlignAccumArgs{in.mfcc, in.frames, in.frames_stride, maxf, h->s_al_rec.p, h->s_al_span.p, d_model_of, d_cen_frames,
+                                          cen_rows, h->s_al_sum.p, h->s_al_cnt.p, st, r0, n},
+                           s);
+    });
+    if (rc) return rc;
+    launch_align_finalise(AlignFinalArgs{cur, next, d_cen_frames, cen_rows, M, h->s_al_sum.p, h->s_al_cnt.p}, s);
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
 
 extern "C" {
 

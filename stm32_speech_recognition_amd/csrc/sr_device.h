@@ -32,6 +32,7 @@ enum DevHook {
     kHookChainChunk,      // "chain_chunk_cols": columns per chunk of the connected-word decoder (1..16383; read per call)
     kHookChainRows,       // "chain_rows": rows per launch group of the connected-word decoder (read per call and by sr_decode_geometry)
     kHookSpanGroups,      // "span_groups": groups of spans per launch of the span scorer (default 65 535, the grid's limit; read per call)
+    kHookClusterPairs,    // "cluster_pairs": (example, model) pairs per launch of the clustering score pass (default 2^20; read per call)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -536,6 +537,40 @@ struct AlignFinalArgs {
     uint32_t *cnt;
 };
 void launch_align_finalise(const AlignFinalArgs &a, hipStream_t s);
+
+// word-model clustering (k_cluster.hip).  The score pass: the cost-only full DP of every (example, model of its word) pair;
+// workgroup i of a launch is entry wg0 + i of the host's list (sr_cluster_plan.h): one model, up to kClusterWaves examples.
+struct ClusterScoreArgs {
+    const int16_t *mfcc;         // [E][max_frames][12]
+    const uint32_t *in_frames;   // frame count of example e at in_frames[e * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t max_frames;
+    const int16_t *cen;          // [M][cen_rows][12]
+    const uint32_t *cen_frames;  // [M]; 0 or above cen_rows: an invalid centroid
+    uint32_t cen_rows;
+    const uint32_t *wg;          // [..][3]: model, first example, examples
+    const uint32_t *ex_mdl0;     // [E] first model of the example's word
+    const uint32_t *ex_nm;       // [E] models of the example's word (1..16)
+    uint32_t *dis;               // [E][16]: column c = the model ex_mdl0[e] + c; SR_DIS_ERR from ex_nm[e] on
+    uint32_t *acc;               // optional [E][16]: the pairs' accumulated costs, 0xFFFFFFFF where dis is SR_DIS_ERR
+    uint32_t wg0, n_wg;
+};
+void launch_cluster_score(const ClusterScoreArgs &a, size_t lds_bytes, hipStream_t s);
+// one thread per example: the first minimum of its score row, the counters of the iteration, the map the update reads
+struct ClusterAssignArgs {
+    const uint32_t *dis;         // [E][16]
+    const uint32_t *acc;         // [E][16], read when stats or iter is given
+    const uint32_t *ex_mdl0, *ex_nm;
+    uint32_t E;
+    const uint32_t *prev;        // optional [E]: the previous iteration's assignment (n_moved)
+    uint32_t *cur;               // optional [E]: this iteration's, for the update and the next iteration
+    uint32_t *assign;            // optional [E]: the caller's
+    uint32_t *best;              // optional [E]
+    sr_train_stat *stats;        // optional [M]: this iteration's row, zero on entry
+    sr_cluster_iter *iter;       // optional: this iteration's record, zero on entry
+};
+void launch_cluster_assign(const ClusterAssignArgs &a, hipStream_t s);
+void launch_cluster_tally(const sr_train_stat *stats, uint32_t M, sr_cluster_iter *iter, hipStream_t s);  // n_empty and acc
 
 // get_mdl (DTW.C:217-296): P independent pairs
 struct GetMdlArgs {

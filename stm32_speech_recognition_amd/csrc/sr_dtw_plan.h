@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 
+#include "sr_cluster_plan.h"
 #include "sr_device.h"
 
 namespace sr {
@@ -144,6 +145,13 @@ inline AlignPlan align_plan(uint32_t max_frames, uint32_t ref_rows, const LdsBud
     return p;
 }
 
+// Word-model clustering (k_cluster.hip): a workgroup of kClusterWaves waves (sr_cluster_plan.h) shares one centroid image
+// (32-byte rows) and gives every wave a boundary column (one word per row).  At SR_ALIGN_MAX_FRAMES rows that is 48 KiB,
+// within every device's per-workgroup LDS the engine accepts; at word-sized centroids (100 rows: 4 granules) the LDS never
+// limits the waves of a CU.
+inline uint32_t cluster_lds_bytes(uint32_t cen_rows) { return cen_rows * (32u + kClusterWaves * 4u); }
+inline bool cluster_fits(uint32_t cen_rows, const LdsBudget &lds) { return cluster_lds_bytes(cen_rows) <= lds.stage_cap; }
+
 // sr_create: let every instance of the file's kernels take up to `bytes` of dynamic LDS (the default limit is 64 KiB);
 // returns the name of an instance that was refused, or nullptr
 const char *dtw_lds_allow_lds(uint32_t bytes);
@@ -158,6 +166,7 @@ const char *chain_live_allow_lds(uint32_t bytes);
 const char *gram_allow_lds(uint32_t bytes);
 const char *gram_live_allow_lds(uint32_t bytes);
 const char *span_allow_lds(uint32_t bytes);
+const char *cluster_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

@@ -22,7 +22,8 @@ int64_t dev_hook(DevHook h) { return g_hooks[h].load(std::memory_order_relaxed);
 static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc", "mfcc_grid", "perturb_log_thr",
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
                                                    "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols",
-                                                   "align_pairs", "align_marks_global", "chain_chunk_cols", "chain_rows", "span_groups"};
+                                                   "align_pairs", "align_marks_global", "chain_chunk_cols", "chain_rows", "span_groups",
+                                                   "cluster_pairs"};
 #endif
 }  // namespace sr
 
@@ -265,7 +266,7 @@ int sr_create(const sr_config *cfg, sr_engine **out)
     }
     // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
     for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, spot_live_allow_lds, align_allow_lds,
-                       chain_allow_lds, chain_live_allow_lds, gram_allow_lds, gram_live_allow_lds, span_allow_lds}) {
+                       chain_allow_lds, chain_live_allow_lds, gram_allow_lds, gram_live_allow_lds, span_allow_lds, cluster_allow_lds}) {
         if (const char *kernel = allow(h->lds.per_wg)) {
             delete h;
             return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));
@@ -439,6 +440,11 @@ void sr_destroy(sr_engine *h)
     h->s_ch_e.release();
     h->s_span_scores.release();
     h->s_span_words.release();
+    h->s_cl_tab.release();
+    h->s_cl_dis.release();
+    h->s_cl_acc.release();
+    h->s_cl_map.release();
+    h->s_cl_stat.release();
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     for (auto &e : h->ev_call) (void)hipEventDestroy(e);
     for (auto &e : h->ev_chunk) (void)hipEventDestroy(e);

@@ -221,6 +221,11 @@ struct sr_engine {
     // forms' device copies of their word rows
     DevBuf<uint32_t> s_span_scores;
     DevBuf<sr_chain_word> s_span_words;
+    // word-model clustering (sr_cluster.cpp): the plan's tables (each example's model range, the score pass's workgroups), the
+    // score and accumulated-cost rows [E][16], the assignment maps of the previous and the current iteration [2][E], and one
+    // iteration's statistics when the caller asked for the iteration records only
+    DevBuf<uint32_t> s_cl_tab, s_cl_dis, s_cl_acc, s_cl_map;
+    DevBuf<sr_train_stat> s_cl_stat;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant
@@ -277,6 +282,21 @@ int check_spot(const sr_engine *h, uint32_t n_rows, uint32_t win_frames, SpotGeo
 // the stage over n_rows rows, enqueued on s (d_scores may be nullptr); reserves the partial records it needs
 int launch_spot_stage(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride, uint32_t n_rows,
                       const SpotGeom &g, sr_spot_hit *d_hits, uint32_t *d_scores, hipStream_t s);
+// ---- full-DP alignment and DBA training (sr_align.cpp), shared with the clustering calls (sr_cluster.cpp) ---------------------
+struct AlignIn {  // the feature rows every aligner call takes
+    const int16_t *mfcc;
+    const uint32_t *frames;
+    uint32_t frames_stride, n_rows;
+};
+// what every aligner call checks: the engine's configuration, the required pointers, frames_stride, ref_rows (named `what`)
+int check_align_common(const sr_engine *h, const AlignIn &in, const void *ref, const void *ref_frames, uint32_t ref_rows, const char *what);
+// room for the DBA iterations of a call over E examples and M models (marks, spans, records, accumulators, and the
+// intermediate centroid set when n_iter > 1), the accumulators cleared on s; *p = the launch plan dba_iteration takes
+int dba_begin(sr_engine *h, uint32_t E, uint32_t M, uint32_t cen_rows, uint32_t n_iter, AlignPlan *p, hipStream_t s);
+// one DBA iteration on s: every row aligned against the centroid d_model_of names (an entry that names none is gated), the
+// OK rows' path points summed, `cur` divided into `next`; st (optional): this iteration's statistics row, or nullptr
+int dba_iteration(sr_engine *h, const AlignIn &in, const uint32_t *d_model_of, uint32_t M, const int16_t *cur, const uint32_t *d_cen_frames,
+                  uint32_t cen_rows, int16_t *next, sr_train_stat *st, const AlignPlan &p, hipStream_t s);
 // ---- connected-word decoding (sr_chain.cpp) -----------------------------------------------------------------------------------
 // the conditions of sr_decode_words_dp_dev on the engine, the store and the parameters (not on the buffers)
 int check_chain(const sr_engine *h, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost);

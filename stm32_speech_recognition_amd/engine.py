@@ -38,6 +38,10 @@ SPOT_WIN_DTYPE = np.dtype([("channel", "<u4"), ("window", "<u4")])
 ALIGN_DTYPE = np.dtype([("dis", "<u4"), ("acc", "<u4"), ("path_len", "<u4"), ("status", "<u4")])
 TRAIN_STAT_DTYPE = np.dtype([("n_ok", "<u4"), ("n_fail", "<u4"), ("acc", "<u8")])
 AL_OK, AL_GATED, AL_TOO_LONG, ALIGN_MAX_FRAMES = 0, 1, 2, 1024
+# word-model clustering (sr_cluster_iter): one iteration's counters; CLUSTER_NONE = an example no model of its word admits
+CLUSTER_ITER_DTYPE = np.dtype([("n_assigned", "<u4"), ("n_unassigned", "<u4"), ("n_moved", "<u4"), ("n_empty", "<u4"), ("acc", "<u8")])
+CLUSTER_MAX, CLUSTER_NONE = 16, 0xFFFFFFFF
+assert CLUSTER_ITER_DTYPE.itemsize == 24
 # connected-word decoding (sr_chain_rec / sr_chain_word): a row's parse and its words in spoken order
 CHAIN_REC_DTYPE = np.dtype([("cost", "<u4"), ("n_words", "<u4"), ("skipped", "<u4"), ("status", "<u4")])
 CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4"), ("dis", "<u4"),
@@ -907,6 +911,127 @@ class Engine:
             assert cen.shape[0] == len(word_ids) == len(cen_frames)
         out, _ = self.train_models(mfcc[order], frames[order], ex_start, cen, cen_frames, n_iter)
         return out, cen_frames.copy(), word_ids.astype(np.uint32)
+
+    # ---- word models: clustering a word's examples into several templates ----------------------------------
+    def _cluster_in(self, mfcc, frames, word_start, mdl_start, cen, cen_frames):
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        word_start = np.ascontiguousarray(word_start, dtype=np.uint32)
+        mdl_start = np.ascontiguousarray(mdl_start, dtype=np.uint32)
+        cen = np.ascontiguousarray(cen, dtype=np.int16)
+        cen_frames = np.ascontiguousarray(cen_frames, dtype=np.uint32)
+        assert len(word_start) == len(mdl_start) >= 2 and cen.shape[2] == N_COEF and len(cen_frames) == cen.shape[0]
+        assert int(word_start[-1]) <= mfcc.shape[0] == len(frames) and int(mdl_start[-1]) <= cen.shape[0]
+        return mfcc, frames, word_start, mdl_start, cen, cen_frames
+
+    def cluster_assign(self, mfcc, frames, word_start, mdl_start, cen, cen_frames, want_scores=True):
+        """OPT-IN (sr_cluster_assign): which model of its word every example is closest to under the full-DP aligner's dis.
+        Word w owns the rows [word_start[w], word_start[w + 1]) of mfcc int16 [E, max_frames, 12] and the models
+        [mdl_start[w], mdl_start[w + 1]) of cen int16 [M, cen_rows, 12] (cen_frames uint32 [M]).  Returns (assign uint32 [E]
+        -- a model index, CLUSTER_NONE where no model admits the example --, best uint32 [E], scores uint32 [E, 16] or None:
+        column c = the word's model c, DIS_ERR past its model count)."""
+        mfcc, frames, word_start, mdl_start, cen, cen_frames = self._cluster_in(mfcc, frames, word_start, mdl_start, cen, cen_frames)
+        E = int(word_start[-1])
+        assign, best = np.zeros(E, np.uint32), np.zeros(E, np.uint32)
+        scores = np.zeros((E, CLUSTER_MAX), np.uint32) if want_scores else None
+        self._check(self.L.sr_cluster_assign(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), _vp(word_start), _vp(mdl_start),
+                                             C.c_uint32(len(word_start) - 1), _vp(cen), _vp(cen_frames), C.c_uint32(cen.shape[1]),
+                                             _vp(assign), _vp(best), _vp(scores)))
+        return assign, best, scores
+
+    def cluster_assign_dev(self, mfcc, frames, word_start, mdl_start, cen, cen_frames, assign, best=None, scores=None, frames_stride=1,
+                           stream=None):
+        """sr_cluster_assign_dev on device tensors (word_start / mdl_start: HOST sequences of W + 1 counts): assign int32 [E],
+        best (optional) int32 [E], scores (optional) int32 [E, 16].  One asynchronous operation on `stream`; returns assign."""
+        import torch
+        word_start = np.ascontiguousarray(word_start, dtype=np.uint32)
+        mdl_start = np.ascontiguousarray(mdl_start, dtype=np.uint32)
+        E = int(word_start[-1])
+        assert mfcc.is_cuda and mfcc.is_contiguous() and cen.is_contiguous() and assign.is_contiguous() and assign.numel() == E
+        assert len(word_start) == len(mdl_start) and E <= mfcc.shape[0] and int(mdl_start[-1]) <= cen.shape[0]
+        assert best is None or (best.is_contiguous() and best.numel() == E)
+        assert scores is None or (scores.is_contiguous() and scores.numel() == E * CLUSTER_MAX)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_cluster_assign_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), _vp(word_start), _vp(mdl_start),
+                                                 C.c_uint32(len(word_start) - 1), _vp(cen), _vp(cen_frames), C.c_uint32(cen.shape[1]),
+                                                 _vp(assign), _vp(best), _vp(scores), C.c_void_p(stream)))
+        return assign
+
+    def cluster_models(self, mfcc, frames, word_start, mdl_start, cen, cen_frames, n_iter=4):
+        """OPT-IN (sr_cluster_models_dp): k-means under DTW.  Per iteration every example goes to the nearest model of its word
+        (cluster_assign's rule) and every model is re-averaged from the examples it received (one train_models iteration).
+        Returns (centroids int16 like cen, assign uint32 [E] of the last iteration, stats TRAIN_STAT_DTYPE [n_iter, M], iter
+        CLUSTER_ITER_DTYPE [n_iter])."""
+        mfcc, frames, word_start, mdl_start, cen, cen_frames = self._cluster_in(mfcc, frames, word_start, mdl_start, cen, cen_frames)
+        E, M = int(word_start[-1]), int(mdl_start[-1])
+        assert M == cen.shape[0]
+        out, assign = np.zeros_like(cen), np.zeros(E, np.uint32)
+        stats, it = np.zeros((n_iter, M), TRAIN_STAT_DTYPE), np.zeros(n_iter, CLUSTER_ITER_DTYPE)
+        self._check(self.L.sr_cluster_models_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), _vp(word_start), _vp(mdl_start),
+                                                C.c_uint32(len(word_start) - 1), _vp(cen), _vp(cen_frames), C.c_uint32(cen.shape[1]),
+                                                C.c_uint32(n_iter), _vp(out), _vp(assign), _vp(stats), _vp(it)))
+        return out, assign, stats, it
+
+    def cluster_models_dev(self, mfcc, frames, word_start, mdl_start, cen_in, cen_frames, cen_out, n_iter=4, assign=None, stats=None,
+                           iters=None, frames_stride=1, stream=None):
+        """sr_cluster_models_dp_dev on device tensors (word_start / mdl_start: HOST sequences): cen_in / cen_out int16
+        [M, cen_rows, 12], assign (optional) int32 [E], stats (optional) n_iter * M * 16 bytes, iters (optional) n_iter * 24
+        bytes.  One asynchronous operation on `stream`; returns cen_out."""
+        import torch
+        word_start = np.ascontiguousarray(word_start, dtype=np.uint32)
+        mdl_start = np.ascontiguousarray(mdl_start, dtype=np.uint32)
+        E, M = int(word_start[-1]), int(mdl_start[-1])
+        assert mfcc.is_cuda and mfcc.is_contiguous() and cen_in.is_contiguous() and cen_out.is_contiguous()
+        assert len(word_start) == len(mdl_start) and E <= mfcc.shape[0] and M == cen_in.shape[0] and cen_out.shape == cen_in.shape
+        assert assign is None or (assign.is_contiguous() and assign.numel() == E)
+        assert stats is None or (stats.is_contiguous() and stats.numel() * stats.element_size() == n_iter * M * 16)
+        assert iters is None or (iters.is_contiguous() and iters.numel() * iters.element_size() == n_iter * 24)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_cluster_models_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), _vp(word_start),
+                                                    _vp(mdl_start), C.c_uint32(len(word_start) - 1), _vp(cen_in), _vp(cen_frames),
+                                                    C.c_uint32(cen_in.shape[1]), C.c_uint32(n_iter), _vp(cen_out), _vp(assign), _vp(stats),
+                                                    _vp(iters), C.c_void_p(stream)))
+        return cen_out
+
+    def cluster_words(self, mfcc, frames, labels, n_clusters=4, n_iter=4, init=None):
+        """Several templates per word from labelled examples.  The rows are grouped by label (ascending label, rows of a word in
+        their order); word w gets min(n_clusters, its example count) models.  Cluster c of C starts from the word's example at
+        position ((2c + 1) * n) // (2C) of its n examples in stable ascending order of frame count -- duration is the variation
+        the 1/2..2x gate cannot bridge, so the seeds span it -- or from init = (centroids int16 [M, rows, 12], frames [M]) in
+        that model order; cluster_models refines them.  Returns (centroids int16 [M, rows, 12], frames uint32 [M], word_ids
+        uint32 [M], valid uint8 [M] = received an example in the last iteration, assign uint32 [E] in INPUT order):
+        set_templates_dense(centroids, frames, valid) and set_word_map(word_ids) make them the store."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        frames = np.minimum(np.ascontiguousarray(frames, dtype=np.uint32), self.max_frames)
+        labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        assert len(labels) == len(frames) == mfcc.shape[0] and 1 <= n_clusters <= CLUSTER_MAX
+        words, counts = np.unique(labels, return_counts=True)
+        order = np.argsort(labels, kind="stable")
+        word_start = np.concatenate(([0], np.cumsum(counts))).astype(np.uint32)
+        n_mdl = np.minimum(counts, n_clusters)
+        mdl_start = np.concatenate(([0], np.cumsum(n_mdl))).astype(np.uint32)
+        word_ids = np.repeat(words, n_mdl).astype(np.uint32)
+        if init is None:
+            seeds = []
+            for w in range(len(words)):
+                rows = order[word_start[w]:word_start[w + 1]]
+                by_len = rows[np.argsort(frames[rows], kind="stable")]
+                n, Cw = len(rows), int(n_mdl[w])
+                seeds += [int(by_len[((2 * c + 1) * n) // (2 * Cw)]) for c in range(Cw)]
+            cen_frames = frames[seeds]
+            cen = np.zeros((len(seeds), max(int(cen_frames.max()), 1) + 1, N_COEF), np.int16)  # (one row of slack, as a store has)
+            for m, e in enumerate(seeds):
+                cen[m, :cen_frames[m]] = mfcc[e, :cen_frames[m]]
+        else:
+            cen, cen_frames = np.ascontiguousarray(init[0], dtype=np.int16), np.ascontiguousarray(init[1], dtype=np.uint32)
+            assert cen.shape[0] == len(word_ids) == len(cen_frames)
+        out, assign, stats, _ = self.cluster_models(mfcc[order], frames[order], word_start, mdl_start, cen, cen_frames, n_iter)
+        by_input = np.empty_like(assign)
+        by_input[order] = assign
+        return out, cen_frames.copy(), word_ids, (stats[-1]["n_ok"] > 0).astype(np.uint8), by_input
 
     def get_mdl(self, in1, n1, in2, n2, mdl_rows):
         """get_mdl (DTW.C:217-296) on P pairs: in1 int16 [P, rows1, 12], in2 int16 [P, rows2, 12].
