@@ -1132,6 +1132,71 @@ int sr_cluster_models_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_f
                          const uint32_t *mdl_start, uint32_t W, const int16_t *cen_in, const uint32_t *cen_frames, uint32_t cen_rows,
                          uint32_t n_iter, int16_t *cen_out, uint32_t *assign, sr_train_stat *stats, sr_cluster_iter *iter);
 
+/* ------------------------------------------------------------------ forced alignment against a transcript:
+ * word models trained on connected speech
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The trainers above learn from one word per feature row; the decoders hold the
+ * result against words spoken without pauses.  This section aligns a corpus of connected recordings to their KNOWN
+ * transcripts, one transcript per row, and cuts the rows at the word boundaries into the trainers' example layout.  Neither
+ * call reads a grammar or writes the template store; no existing call, record or score changes.
+ *
+ * THE RULE.  Row r has the transcript t[r][0..n_r), labels of the engine's word map (sr_set_word_map), n_r = n_words[r] in
+ * 0..words_per_row, words_per_row in 1..16.  Everything is the connected-word decoding section's: d, the word path, E_0, the
+ * charged start, the key (cost, start, slot), E_l, the trace, skip_cost, word_cost, every limit.  Two things change:
+ *   level    at level l the minimum of A_l runs only over the VALID slots whose label is t[r][l-1];
+ *   count    it is exactly n_r.
+ *   status   SR_CH_NONE (cost SR_DIS_ERR, n_words 0, skipped 0, every word row all ones) when n_r = 0, when a transcript word
+ *            has no valid slot, or when E_{n_r}(N) is not finite; SR_CH_OK otherwise.
+ *   outputs  d_rec[n_rows]; d_words[n_rows][words_per_row], entries at and beyond n_r all ones; sr_chain_word.reserved is the
+ *            word's 1-based position.  There is no level_cost output, and the levels below n_r are not part of the contract.
+ * Anchor: for a row with n_r >= 1, the record and the n_r word rows are byte for byte what sr_decode_grammar_dp writes for it
+ * under the sequence grammar (state i --t[r][i]--> state i+1, the last state final) with max_words = n_words_exact = n_r.  A
+ * grammar belongs to a call, so that route costs one grammar and one one-row call per recording; this call takes R rows with R
+ * transcripts at once.
+ *
+ * EXACT COLUMN PRUNING, which only a linear transcript allows.  minlen(w) = the minimum of M/2 + 1 over the valid slots of w
+ * (M frames of template need M/2 + 1 frames of input at least -- the span section's reach rule; 1 for M = 1).  tail_l = the sum
+ * of minlen over the positions after l.  Level l of row r is swept only over the end frames e with e + 1 <= N - tail_l.  Record
+ * and word rows do not change: a word of level l+1 that starts after N - tail_l ends after N - tail_{l+1}, which is itself
+ * pruned; E_l(p) for p <= N - tail_l depends only on A_l(j <= p); the trace enters level l at a start <= N - tail_l; and level
+ * n_r has tail 0.  The host uploads tail per (row, level); N is a device value, so the kernel forms the bound itself.  A sweep
+ * that no reachable start has entered yet exits as well (E_{l-1} is unreachable in the early columns of a late level).
+ *
+ * Arguments: d_mfcc, d_in_frames / frames_stride, n_rows as for sr_decode_words_dp_dev.  transcript[n_rows][words_per_row] and
+ * n_words[n_rows] are HOST arrays in both forms, as ex_start is: the host knows every item and count, builds the per-level
+ * lists of (row, slot) word passes the kernel's grid runs over and uploads them once per call (a pageable source is staged
+ * before the call returns).  ONE asynchronous operation on `stream`: nothing is read back; two runs give identical bytes;
+ * every record and every word row is written whole.  Scratch is the decoder's at max_words = words_per_row, and a call is cut
+ * into launch groups by the same rule (sr_decode_geometry).
+ * Errors, before anything is launched or written: those of sr_decode_words_dp_dev; SR_ERR_BAD_ARG for words_per_row outside
+ * 1..16, an n_words[r] above words_per_row, a transcript label that no slot of the word map carries (sr_last_error names row
+ * and position), d_rec overlapping d_words.
+ *
+ * Out of scope: alternatives per position in a transcript; optional words; live sessions; a device-side store update (the
+ * store is set from host memory: a training loop reads its centroids back once per iteration); changing template lengths. */
+int sr_align_transcripts_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride,
+                                uint32_t n_rows, const uint32_t *transcript, const uint32_t *n_words, uint32_t words_per_row,
+                                uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *d_rec, sr_chain_word *d_words, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_align_transcripts_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                            const uint32_t *transcript, const uint32_t *n_words, uint32_t words_per_row, uint32_t skip_cost,
+                            uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words);
+/* Word spans to example rows.  d_words[n_rows][words_per_row] (1..16) are ANY decoder's word rows over the feature rows
+ * d_mfcc / d_in_frames; only start and end are read.  dst_of_span[n_rows * words_per_row] is a HOST array: the example index
+ * (below n_ex) span i is copied to, or all ones for "not wanted"; the indices are distinct.  d_ex[n_ex][ex_rows][12] and
+ * d_ex_frames[n_ex] are written whole: a valid span (start <= end < N, N clamped to max_frames) of L = end - start + 1 <=
+ * ex_rows frames puts the frames start..end into rows 0..L-1, zero behind them, and ex_frames = L; an invalid span, L above
+ * ex_rows and an example no span names give a zero row with ex_frames = 0, which the trainers gate as an empty row.  Nothing
+ * outside the rows [0, N) is read.  ONE asynchronous operation on `stream`; the table derived from dst_of_span lives in the
+ * engine's scratch.  Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_BAD_ARG for
+ * a null pointer, frames_stride 0, words_per_row outside 1..16, ex_rows 0 or above SR_ALIGN_MAX_FRAMES, a destination at or
+ * above n_ex or named twice, feature rows or d_ex not 4-byte aligned, d_ex overlapping d_ex_frames. */
+int sr_gather_word_spans_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                             const sr_chain_word *d_words, uint32_t words_per_row, const uint32_t *dst_of_span, uint32_t n_ex,
+                             uint32_t ex_rows, int16_t *d_ex, uint32_t *d_ex_frames, void *stream);
+int sr_gather_word_spans(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                         const sr_chain_word *words, uint32_t words_per_row, const uint32_t *dst_of_span, uint32_t n_ex, uint32_t ex_rows,
+                         int16_t *ex, uint32_t *ex_frames);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -1245,6 +1310,9 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "span_groups"                    groups of four spans per launch of the span scorer (default 65 535, the grid's limit;
  *                                    a launch holds one feature row's spans at least); read per call
  *   "cluster_pairs"                  (example, model) pairs per launch of the clustering score pass (default 2^20); read per call
+ *   "forced_prune_off"               sr_align_transcripts_dp sweeps every end frame of every level (tail = 0: no column bound;
+ *                                    the same bytes come out); read per call.  The call also reads "chain_chunk_cols" (or,
+ *                                    when that is 0, "spot_chunk_cols") and "chain_rows" as the decoder does
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

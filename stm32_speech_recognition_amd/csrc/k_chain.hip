@@ -184,6 +184,11 @@ void launch_chain(const ChainArgs &a, hipStream_t s)
     }
     hipLaunchKernelGGL(k_chain_trace, dim3(a.n_rows), dim3(64), 0, s, a);
 }
+void launch_chain_init(const ChainArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_chain_init, dim3(a.n_rows), dim3(256), 0, s, a); }
+void launch_chain_close(const ChainArgs &a, uint32_t level, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_chain_close, dim3(a.n_rows), dim3(256), 0, s, a, level);
+}
 const char *chain_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_chain_words, "k_chain_words"}}, bytes); }
 
 }  // namespace sr

@@ -33,6 +33,7 @@ enum DevHook {
     kHookChainRows,       // "chain_rows": rows per launch group of the connected-word decoder (read per call and by sr_decode_geometry)
     kHookSpanGroups,      // "span_groups": groups of spans per launch of the span scorer (default 65 535, the grid's limit; read per call)
     kHookClusterPairs,    // "cluster_pairs": (example, model) pairs per launch of the clustering score pass (default 2^20; read per call)
+    kHookForcedPruneOff,  // "forced_prune_off": the forced aligner sweeps every end frame of every level (no column bound; read per call)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -384,6 +385,36 @@ struct ChainArgs {
     uint32_t *level_cost;       // optional [n_rows][max_words]
 };
 void launch_chain(const ChainArgs &a, hipStream_t s);  // init, max_words x (k_chain_words, k_chain_close), k_chain_trace
+// k_chain_init and one level's k_chain_close alone, for the forced aligner, whose scratch is the decoder's (k_forced.hip)
+void launch_chain_init(const ChainArgs &a, hipStream_t s);
+void launch_chain_close(const ChainArgs &a, uint32_t level, hipStream_t s);
+
+// transcript-forced alignment (k_forced.hip): the decoder's levels with a grid over a host-built item list.  c is the decoder's
+// argument block for one launch group with max_words = words_per_row (n_words_exact and level_cost are not read); an item is
+// (row of the CALL, slot); tail and count are the group's rows of the host's tables (sr_forced_plan.h).
+struct ForcedArgs {
+    ChainArgs c;
+    const uint2 *items;     // the call's list
+    const uint32_t *tail;   // [n_rows][max_words]: level l of a row sweeps the end frames e with e + 1 <= N - tail[l - 1]
+    const uint32_t *count;  // [n_rows]: words of each transcript, 0..max_words
+    uint32_t row0;          // the group's first row in the call
+};
+// init, per level 1..levels (k_forced_words over the items [item0[l - 1], item0[l]) when there are any, k_chain_close), k_forced_trace
+void launch_forced(const ForcedArgs &a, const uint32_t *item0, uint32_t levels, hipStream_t s);
+// span gather (k_forced.hip): example e = the frames of span src_of_ex[e] of the word rows, or an empty row
+struct GatherArgs {
+    const int16_t *mfcc;         // [n_rows][max_frames][12]
+    const uint32_t *in_frames;   // frame count of row r at in_frames[r * frames_stride] (clamped to max_frames)
+    uint32_t frames_stride;
+    uint32_t max_frames;
+    const sr_chain_word *words;  // [n_rows][words_per_row]; only start and end are read
+    uint32_t words_per_row;
+    const uint32_t *src_of_ex;   // [n_ex]: a span index, or all ones
+    uint32_t n_ex, ex_rows;
+    int16_t *ex;                 // [n_ex][ex_rows][12]
+    uint32_t *ex_frames;         // [n_ex]
+};
+void launch_gather_spans(const GatherArgs &a, hipStream_t s);
 
 // word alternatives (k_span.hip): the best path of every template over fixed spans of frames, start and end pinned.  Span i
 // = words[i] (only start and end are read) lies in feature row i / words_per_row; one wave per (span, slot).

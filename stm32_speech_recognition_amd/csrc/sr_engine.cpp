@@ -23,7 +23,7 @@ static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
                                                    "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols",
                                                    "align_pairs", "align_marks_global", "chain_chunk_cols", "chain_rows", "span_groups",
-                                                   "cluster_pairs"};
+                                                   "cluster_pairs", "forced_prune_off"};
 #endif
 }  // namespace sr
 
@@ -266,7 +266,8 @@ int sr_create(const sr_config *cfg, sr_engine **out)
     }
     // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
     for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, spot_live_allow_lds, align_allow_lds,
-                       chain_allow_lds, chain_live_allow_lds, gram_allow_lds, gram_live_allow_lds, span_allow_lds, cluster_allow_lds}) {
+                       chain_allow_lds, chain_live_allow_lds, gram_allow_lds, gram_live_allow_lds, span_allow_lds, cluster_allow_lds,
+                       forced_allow_lds}) {
         if (const char *kernel = allow(h->lds.per_wg)) {
             delete h;
             return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));
@@ -445,6 +446,8 @@ void sr_destroy(sr_engine *h)
     h->s_cl_acc.release();
     h->s_cl_map.release();
     h->s_cl_stat.release();
+    h->s_fc_tab.release();
+    h->s_fc_src.release();
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     for (auto &e : h->ev_call) (void)hipEventDestroy(e);
     for (auto &e : h->ev_chunk) (void)hipEventDestroy(e);
@@ -559,6 +562,8 @@ static int upload_templates(sr_engine *h, const std::vector<int16_t> &m, const s
     h->tpl_rows = rows;
     h->tpl_stride = rows * nc;
     h->store_serial++;
+    h->tpl_len_host.resize(K);  // what the device's kernels take as a slot's rows: the forced aligner plans from it on the host
+    for (uint32_t k = 0; k < K; k++) h->tpl_len_host[k] = v[k] ? std::min(f[k], rows - 1) : 0u;
     plan_dtw(h, f.data(), v.data());
     // Chunk count of the device-resident pipeline by store size (round-4 sweeps, profiles/experiments/RESULTS.md): with
     // 100 templates 3 streams x 6..15 chunks are equivalent (22.3 ms per 65 536 utterances); with 500 templates the DTW

@@ -226,6 +226,10 @@ struct sr_engine {
     // iteration's statistics when the caller asked for the iteration records only
     DevBuf<uint32_t> s_cl_tab, s_cl_dis, s_cl_acc, s_cl_map;
     DevBuf<sr_train_stat> s_cl_stat;
+    // transcript-forced alignment and the span gather (sr_forced.cpp): the rows a valid slot holds (0: an invalid slot), kept on
+    // the host with every store, so that a call can plan without reading the store back; the plan's tables of a call in flight
+    std::vector<uint32_t> tpl_len_host;
+    DevBuf<uint32_t> s_fc_tab, s_fc_src;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant

@@ -262,6 +262,7 @@ class Engine:
             words = np.ascontiguousarray(words, dtype=np.uint32)
         self._check(self.L.sr_set_word_map(self.h, _vp(words), C.c_uint32(0 if words is None else len(words)),
                                            C.c_uint32(slots_per_word)))
+        self._wmap = (None if words is None else words.copy(), int(slots_per_word))  # (train_connected groups its examples by it)
 
     @staticmethod
     def word_groups(words=None, n_slots=None, slots_per_word=1):
@@ -1032,6 +1033,148 @@ class Engine:
         by_input = np.empty_like(assign)
         by_input[order] = assign
         return out, cen_frames.copy(), word_ids, (stats[-1]["n_ok"] > 0).astype(np.uint8), by_input
+
+    # ---- forced alignment against a transcript: word models trained on connected speech ------------------------
+    @staticmethod
+    def _transcripts(transcripts, n_rows):
+        """a list of label lists -> (labels uint32 [n_rows, words_per_row] padded with NO_WORD, counts uint32 [n_rows])"""
+        assert len(transcripts) == n_rows
+        counts = np.array([len(t) for t in transcripts], np.uint32)
+        W = max(1, int(counts.max(initial=0)))
+        labels = np.full((n_rows, W), NO_WORD, np.uint32)
+        for r, t in enumerate(transcripts):
+            labels[r, :len(t)] = np.asarray(t, np.uint32)
+        return labels, counts
+
+    def align_transcripts(self, mfcc, frames, transcripts, skip_cost=None, word_cost=0):
+        """OPT-IN (sr_align_transcripts_dp): every feature row aligned to ITS OWN transcript, transcripts = one list of word
+        labels (of the word map) per row, up to 16 words; the connected-word decoder's parse with the word sequence given.
+        mfcc int16 [n_rows, max_frames, 12], frames uint32 [n_rows].  Returns (rec CHAIN_REC_DTYPE [n_rows], words
+        CHAIN_WORD_DTYPE [n_rows, words_per_row]) with words_per_row = the longest transcript (1 at least); `reserved` of a
+        word row is the word's 1-based position; a row without a parse (or with an empty transcript) has status CH_NONE."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        labels, counts = self._transcripts(transcripts, n)
+        W = labels.shape[1]
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, W), dtype=CHAIN_WORD_DTYPE)
+        self._check(self.L.sr_align_transcripts_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), _vp(labels), _vp(counts),
+                                                   C.c_uint32(W), C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(rec),
+                                                   _vp(words)))
+        return rec, words
+
+    def align_transcripts_dev(self, mfcc, frames, transcripts, rec, words, skip_cost=None, word_cost=0, frames_stride=1, stream=None):
+        """sr_align_transcripts_dp_dev on device tensors (transcripts: a HOST list of label lists): mfcc int16 [n_rows,
+        max_frames, 12]; frames as for decode_words_dev; rec int32 [n_rows, 4]; words int32 [n_rows, words_per_row, 8] with
+        words_per_row = the size of `words` (the longest transcript at least).  One asynchronous operation on `stream`;
+        returns (rec, words)."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous()
+        n = mfcc.shape[0]
+        labels, counts = self._transcripts(transcripts, n)
+        W = words.numel() // (n * 8) if n else labels.shape[1]
+        assert rec.numel() == n * 4 and words.numel() == n * W * 8 and W >= labels.shape[1]
+        if W > labels.shape[1]:
+            labels = np.concatenate([labels, np.full((n, W - labels.shape[1]), NO_WORD, np.uint32)], axis=1)
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_align_transcripts_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                       _vp(np.ascontiguousarray(labels)), _vp(counts), C.c_uint32(W),
+                                                       C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(rec), _vp(words),
+                                                       C.c_void_p(stream)))
+        return rec, words
+
+    def gather_word_spans(self, mfcc, frames, words, dst_of_span, n_ex, ex_rows):
+        """OPT-IN (sr_gather_word_spans): word spans cut out of feature rows into the trainers' example layout.  words
+        CHAIN_WORD_DTYPE [n_rows, words_per_row] (any decoder's; start and end are read); dst_of_span uint32 [n_rows *
+        words_per_row] = the example each span goes to (distinct indices below n_ex) or NO_WORD for "not wanted".  Returns (ex
+        int16 [n_ex, ex_rows, 12], ex_frames uint32 [n_ex]); an invalid or too long span and an unnamed example are empty rows."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        words = np.ascontiguousarray(words, dtype=CHAIN_WORD_DTYPE).reshape(n, -1) if n else np.zeros((0, 1), CHAIN_WORD_DTYPE)
+        dst = np.ascontiguousarray(dst_of_span, dtype=np.uint32)
+        assert len(frames) == n and dst.size == words.size
+        ex, ex_frames = np.zeros((n_ex, max(ex_rows, 0), N_COEF), np.int16), np.zeros(n_ex, np.uint32)
+        self._check(self.L.sr_gather_word_spans(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), _vp(words),
+                                                C.c_uint32(words.shape[1]), _vp(dst), C.c_uint32(n_ex), C.c_uint32(ex_rows), _vp(ex),
+                                                _vp(ex_frames)))
+        return ex, ex_frames
+
+    def gather_word_spans_dev(self, mfcc, frames, words, dst_of_span, ex, ex_frames, frames_stride=1, stream=None):
+        """sr_gather_word_spans_dev on device tensors (dst_of_span: a HOST sequence): words int32 [n_rows, words_per_row, 8];
+        ex int16 [n_ex, ex_rows, 12]; ex_frames int32 [n_ex].  One asynchronous operation on `stream`; returns (ex, ex_frames)."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and words.is_contiguous() and ex.is_contiguous() and ex_frames.is_contiguous()
+        n, n_ex = mfcc.shape[0], ex.shape[0]
+        dst = np.ascontiguousarray(dst_of_span, dtype=np.uint32)
+        assert n and words.numel() % (n * 8) == 0 and dst.size * 8 == words.numel() and ex_frames.numel() == n_ex and ex.shape[2] == N_COEF
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_gather_word_spans_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n), _vp(words),
+                                                    C.c_uint32(words.numel() // (n * 8)), _vp(dst), C.c_uint32(n_ex), C.c_uint32(ex.shape[1]),
+                                                    _vp(ex), _vp(ex_frames), C.c_void_p(stream)))
+        return ex, ex_frames
+
+    def train_connected(self, mfcc, frames, transcripts, n_iter=4, skip_cost=None, word_cost=0, ex_rows=None):
+        """Embedded re-estimation of the word models from CONNECTED recordings with known transcripts.  The current store
+        (set_templates_dense) and word map are the starting models.  Per iteration: align_transcripts against the store; gather
+        every transcript word as an example (grouped by word in word_groups order, inside a word by (row, position)); one
+        cluster_models iteration with all slots of a word as that word's models (an invalid slot is a centroid of 0 frames,
+        copied through; a word with one slot is plain DBA); set_templates_dense with the new centroids -- valid flags, frame
+        counts and the word map stay.  The store is set from host memory, so the centroids are read back once per iteration.
+        ex_rows: rows of an example (None: min(max_frames, ALIGN_MAX_FRAMES)); a longer span is dropped.  A word with more
+        than CLUSTER_MAX slots is refused.  Returns (centroids int16 [K, rows, 12], frames uint32 [K], iters = a list of (OK
+        rows, the sum of their rec.cost) per iteration, words = the last alignment's word rows)."""
+        if self._tpl is None or self._tpl[0] != "set_templates_dense":
+            raise SrError("train_connected needs a store set with set_templates_dense")
+        tm, tf, valid = self._tpl[1]
+        K = tm.shape[0]
+        wmap = getattr(self, "_wmap", (None, 1))
+        lab = np.arange(K, dtype=np.uint32) // wmap[1] if wmap[0] is None else wmap[0]
+        assert len(lab) == K, "the word map does not fit the template store"
+        grp = self.word_groups(words=lab)
+        order, gstart, ids = grp["order"], grp["group_start"], grp["word_id"]
+        if int(np.diff(gstart.astype(np.int64)).max()) > CLUSTER_MAX:
+            raise SrError(f"train_connected: a word with more than {CLUSTER_MAX} slots")
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        labels, counts = self._transcripts(transcripts, n)
+        W = labels.shape[1]
+        # the example layout: the host knows it from the transcripts alone
+        dst = np.full(n * W, NO_WORD, np.uint32)
+        word_start, e = [0], 0
+        for w in ids:
+            at = np.nonzero((labels == w) & (np.arange(W)[None, :] < counts[:, None]))
+            for r, i in zip(*at):  # (row-major: ascending row, then position)
+                dst[r * W + i] = e
+                e += 1
+            word_start.append(e)
+        word_start = np.array(word_start, np.uint32)
+        ex_rows = min(self.max_frames, ALIGN_MAX_FRAMES) if ex_rows is None else int(ex_rows)
+        trainer = self  # the clustering calls take example rows of THEIR engine's max_frames; they touch no store
+        if ex_rows != self.max_frames:
+            trainer = Engine(max_frames=ex_rows, device=self.cfg.device, testing=self._testing, **self._kw)
+        cen_frames = np.where(valid[order] != 0, tf[order], 0).astype(np.uint32) if valid is not None else tf[order].astype(np.uint32)
+        iters, words = [], None
+        try:
+            for _ in range(n_iter):
+                rec, words = self.align_transcripts(mfcc, frames, transcripts, skip_cost, word_cost)
+                ok = rec["status"] == 0
+                iters.append((int(ok.sum()), int(rec["cost"][ok].astype(np.int64).sum())))
+                ex, ex_frames = self.gather_word_spans(mfcc, frames, words, dst, e, ex_rows)
+                cen, _, _, _ = trainer.cluster_models(ex, ex_frames, word_start, gstart, tm[order], cen_frames, 1)
+                tm = tm.copy()
+                tm[order] = cen
+                self.set_templates_dense(tm, tf, valid)
+        finally:
+            if trainer is not self:
+                trainer.close()
+        return tm, tf.copy(), iters, words
 
     def get_mdl(self, in1, n1, in2, n2, mdl_rows):
         """get_mdl (DTW.C:217-296) on P pairs: in1 int16 [P, rows1, 12], in2 int16 [P, rows2, 12].
