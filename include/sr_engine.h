@@ -1197,6 +1197,68 @@ int sr_gather_word_spans(sr_engine *h, const int16_t *mfcc, const uint32_t *in_f
                          const sr_chain_word *words, uint32_t words_per_row, const uint32_t *dst_of_span, uint32_t n_ex, uint32_t ex_rows,
                          int16_t *ex, uint32_t *ex_frames);
 
+/* ------------------------------------------------------------------ one-pass connected-word decoding: no word cap
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  Level building (the connected-word decoding section) keeps one prefix-cost
+ * array per word count: a row holds at most 16 words and a call pays max_words x K x M x N cells.  This section keeps ONE
+ * prefix-cost array E(p) over all word counts: a row holds as many words as its frames allow, and a call pays 2 x K x M x N
+ * cells whatever that number is.  No existing call, record or byte changes.
+ * Everything not restated here is the connected-word decoding section: d, the word path, skip_cost, word_cost, the key
+ * cost << 32 | start << 16 | slot, sr_chain_rec, sr_chain_word.
+ *   E(0)     0.
+ *   D_k      per valid slot k the spotter's recurrence with a charged start, D_k(x,0) = E(x) + d(x,0), S = x, the start
+ *            unreachable where E(x) is.
+ *   A(p)     p >= 1: the minimum over the valid slots of (D_k(p-1, M_k-1) + word_cost, S, k), compared as (cost, start, slot).
+ *   E(p)     min(A(p).cost, E(p-1) + skip_cost), the second term only when skipping is on.
+ *   result   E(N) unreachable, or N = 0: status SR_CH_NONE, with the decoder's NONE record (cost SR_DIS_ERR, n_words 0,
+ *            skipped 0, every word row all ones).  Otherwise SR_CH_OK, cost = E(N), n_words = the words on the trace.  That may
+ *            be 0: with skipping on a row that is cheaper as filler than as any word is a legitimate "nothing was said", with
+ *            cost = N * skip_cost and skipped = N.
+ *   trace    p = N; while p > 0: if A(p) is unreachable or A(p).cost != E(p), frame p-1 is skipped and p -= 1; else the word
+ *            is A(p): end = p-1, cum = E(p), acc = A(p).cost - word_cost - E(start), and p = start.  A word is preferred to
+ *            filler at equal cost, as in the level decoder's trace.
+ *   output   d_words[n_rows][words_cap], words_cap >= 1 of any size, words in spoken order, entries at or beyond n_words all
+ *            ones, reserved = 0.  When n_words > words_cap the FIRST words_cap words are written, sr_chain_rec.n_words is the
+ *            true count and status is SR_CH_TRUNCATED (cost and skipped as for SR_CH_OK).
+ *   levels   E(N) = min(N * skip_cost when skipping is on, min over n >= 1 of E_n(N)) with n unbounded.  Where that minimum
+ *            is unique and has at most 16 words, the word rows equal sr_decode_words_dp's at max_words 16, cum included.
+ *            Under ties the two decoders may choose differently: level building prefers the fewest words globally, this
+ *            decoder traces locally (a word before filler at every position).  Byte equality with the level decoder is NOT
+ *            promised.
+ *   blocks   a word over a template of M frames spans at least M / 2 + 1 input frames, so with L = the minimum of M_k / 2 + 1
+ *            over the valid slots, A and E over a block of L positions depend only on E at or before the block's first
+ *            frame.  The call runs as ceil(frames_cap / L) blocks ordered by the stream alone; inside a block all rows and
+ *            slots run in parallel and every column is swept twice.
+ *   limits   skip_cost <= 65 535 or SR_DIS_ERR; word_cost <= 2^24 and (frames_cap / L) * word_cost <= 2^30: a row holds at
+ *            most N / L words, and 3 * 16 383 * 65 536 + 2^30 < 2^32 - 1, so u32 costs stay exact; a store of at most 65 536
+ *            slots.  Arguments outside these limits are refused.
+ * Out of scope: a live (push) form, grammars, n_words_exact, N-best sequences. */
+#define SR_CH_TRUNCATED 2u
+/* Stage level, DEVICE buffers: d_mfcc / d_in_frames / frames_stride as for sr_decode_words_dp_dev.  frames_cap is a HOST-side
+ * bound on the frames of every row, 0 = max_frames: N is clamped to min(max_frames, frames_cap), and frames_cap fixes the
+ * number of blocks -- the host never reads the device counts.  d_rec[n_rows] and d_words[n_rows][words_cap] are written whole
+ * on every call.  ONE asynchronous operation on `stream` (keys, prefix costs and one saved column per (row, slot) live in the
+ * engine's scratch, sr_decode_onepass_geometry), no host synchronisation, no read-back; two runs give the same bytes.
+ * Errors, before anything is launched or written: SR_ERR_BAD_CONFIG unless n_coef == 12; SR_ERR_NO_TEMPLATES; SR_ERR_BAD_ARG
+ * for a null pointer, frames_stride 0, words_cap 0, an argument outside the limits above, a word map that does not fit the
+ * store, a store whose longest template exceeds sr_decode_geometry's out[2], outputs that overlap. */
+int sr_decode_onepass_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,
+                             uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *d_rec,
+                             sr_chain_word *d_words, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_decode_onepass_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows,
+                         uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec,
+                         sr_chain_word *words);
+/* Whole path on HOST buffers: sr_mfcc_batch_status (its arguments, its per-record failure rules; mfcc, frm_num and status
+ * may be NULL here) followed by the stage over those rows with frames_cap = max_frames; a failed record has no parse. */
+int sr_decode_onepass_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
+                            const int32_t *end, const uint32_t *mid, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost,
+                            sr_chain_rec *rec, sr_chain_word *words, int16_t *mfcc, uint32_t *frm_num, uint32_t *status);
+/* Host-only: a store of K slots whose longest template has tpl_rows rows and whose shortest valid one has min_tpl_frames
+ * frames.  out[0] = state bytes per row (keys, prefix costs, saved columns), out[1] = rows per launch group (what 256 MiB of
+ * scratch hold, 65 535 at most), out[2] = the block length L = min_tpl_frames / 2 + 1, out[3] = launches per group,
+ * 2 * ceil(max_frames / L) + 2. */
+int sr_decode_onepass_geometry(uint32_t tpl_rows, uint32_t K, uint32_t max_frames, uint32_t min_tpl_frames, uint32_t out[4]);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -1313,6 +1375,11 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *   "forced_prune_off"               sr_align_transcripts_dp sweeps every end frame of every level (tail = 0: no column bound;
  *                                    the same bytes come out); read per call.  The call also reads "chain_chunk_cols" (or,
  *                                    when that is 0, "spot_chunk_cols") and "chain_rows" as the decoder does
+ *   "onepass_block"                  frames per block of the one-pass decoder, clamped to 1..L (a longer block would be wrong;
+ *                                    the same bytes come out of every admissible length); read per call and by
+ *                                    sr_decode_onepass_geometry
+ *   "onepass_rows"                   rows per launch group of the one-pass decoder (default: what 256 MiB of scratch hold);
+ *                                    read per call and by sr_decode_onepass_geometry
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

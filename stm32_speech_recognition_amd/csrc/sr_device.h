@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/sr_engine.h"
+#include "sr_onepass_plan.h"
 
 namespace sr {
 
@@ -34,6 +35,8 @@ enum DevHook {
     kHookSpanGroups,      // "span_groups": groups of spans per launch of the span scorer (default 65 535, the grid's limit; read per call)
     kHookClusterPairs,    // "cluster_pairs": (example, model) pairs per launch of the clustering score pass (default 2^20; read per call)
     kHookForcedPruneOff,  // "forced_prune_off": the forced aligner sweeps every end frame of every level (no column bound; read per call)
+    kHookOnePassBlock,    // "onepass_block": frames per block of the one-pass decoder, clamped to 1..L (read per call and by sr_decode_onepass_geometry)
+    kHookOnePassRows,     // "onepass_rows": rows per launch group of the one-pass decoder (read per call and by sr_decode_onepass_geometry)
     kHookCount
 };
 #ifdef SR_TESTING
@@ -437,6 +440,37 @@ struct SpanArgs {
     uint32_t *scores;           // [n_spans][K]
 };
 void launch_span(const SpanArgs &a, hipStream_t s);
+
+// one-pass connected-word decoding (k_onepass.hip): ONE prefix-cost array over all word counts, built in blocks of at most
+// L = min_k(M_k / 2 + 1) frames.  One launch group covers n_rows rows whose scratch is A[row][max_frames + 1] (ChainArgs' keys),
+// E[row][max_frames + 1] and cols[row][K][tpl_len]: per (row, slot) ONE saved column in k_chain_live_words' (Dd, min(Dd, Dn))
+// layout -- the exact column at the first frame of the block swept last.  Every pointer is the group's first row.
+struct OnePassArgs {
+    const int16_t *mfcc;        // [n_rows][max_frames][12]
+    const uint32_t *in_frames;  // frame count of row r at in_frames[r * frames_stride] (clamped to frames_cap)
+    uint32_t frames_stride;
+    uint32_t n_rows;
+    uint32_t max_frames;
+    uint32_t frames_cap;        // 1..max_frames: the host's bound on every row's frames; it fixes the blocks
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;                 // <= 65 536: the slot is 16 bits of a key
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a saved column
+    uint32_t words_cap;         // word rows per row of d_words, >= 1
+    uint32_t skip_cost;         // SR_DIS_ERR: no skipping
+    uint32_t word_cost;
+    unsigned long long *A;
+    uint32_t *E;
+    ulonglong2 *cols;
+    const uint32_t *group_of_slot;
+    const uint32_t *word_id;
+    sr_chain_rec *rec;          // [n_rows]
+    sr_chain_word *words;       // [n_rows][words_cap]
+};
+// init, per block of the host's list (sr_onepass_plan.h) (k_onepass_words, k_onepass_close), k_onepass_trace
+void launch_onepass(const OnePassArgs &a, const OnePassBlock *blocks, uint32_t n_blocks, hipStream_t s);
 
 // grammar-constrained decoding (k_gram.hip): k_chain's levels over a word network of n_states states.  c is the decoder's
 // argument block with the scratch in the grammar's layout: c.A[row][level 1..max_words][state][max_frames + 1], c.E[row][level

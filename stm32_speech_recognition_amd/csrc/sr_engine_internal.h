@@ -230,6 +230,9 @@ struct sr_engine {
     // the host with every store, so that a call can plan without reading the store back; the plan's tables of a call in flight
     std::vector<uint32_t> tpl_len_host;
     DevBuf<uint32_t> s_fc_tab, s_fc_src;
+    // one-pass connected-word decoding (sr_onepass.cpp): the saved columns of one launch group (its keys and prefix costs are
+    // s_ch_a / s_ch_e)
+    DevBuf<ulonglong2> s_op_cols;
 };
 
 // what an N-best form adds to the call it extends (device pointers); nullptr where the plain call is meant
@@ -308,6 +311,9 @@ int check_chain(const sr_engine *h, uint32_t max_words, uint32_t n_words_exact, 
 int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
                       uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
                       const uint32_t *level_cost);
+// ---- one-pass connected-word decoding (sr_onepass.cpp) ------------------------------------------------------------------------
+// the conditions of sr_decode_onepass_dp_dev on the engine, the store and the parameters (not on the buffers)
+int check_onepass(const sr_engine *h, uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost);
 // ---- grammar-constrained decoding (sr_gram.cpp) -------------------------------------------------------------------------------
 // The compiled form (sr_gram_compile.h builds it on the host).  Items ascend by (slot, target); level l's lists are sorted by
 // the distance from the target to a final state, so that what a call with max_words keeps is a PREFIX of each list.

@@ -47,6 +47,7 @@ CHAIN_REC_DTYPE = np.dtype([("cost", "<u4"), ("n_words", "<u4"), ("skipped", "<u
 CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"), ("end", "<u4"), ("acc", "<u4"), ("dis", "<u4"),
                              ("cum", "<u4"), ("reserved", "<u4")])
 CH_OK, CH_NONE = 0, 1
+CH_TRUNCATED = 2  # sr_decode_onepass_*: more words than words_cap, the first words_cap are written
 # sr_vad_debug_masks: 16 words per capture, 63 frames (one round of the VAD kernel) per 64-bit word
 VAD_MASK_WORDS, VAD_MASK_FRAMES = 16, 63
 # sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
@@ -670,6 +671,57 @@ class Engine:
                                                  C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost), _vp(out["rec"]),
                                                  _vp(out["words"]), _vp(out["level_cost"]), _vp(out["mfcc"]), _vp(out["frm_num"]),
                                                  _vp(out["status"])))
+        return out
+
+    # ---- one-pass connected-word decoding ---------------------------------------------------------------------
+    def decode_onepass(self, mfcc, frames, words_cap=64, skip_cost=None, word_cost=0, frames_cap=0):
+        """OPT-IN one-pass connected-word decoder (sr_decode_onepass_dp): decode_words() without a word cap and at a cost
+        that does not grow with the word count -- one prefix-cost array over all word counts.  mfcc int16 [n_rows, max_frames,
+        12], frames uint32 [n_rows]; frames_cap = a bound on every row's frames (0 = max_frames; fewer blocks are launched for a
+        smaller one); skip_cost None = every frame belongs to a word.  Returns (rec CHAIN_REC_DTYPE [n_rows], words
+        CHAIN_WORD_DTYPE [n_rows, words_cap] in spoken order); a row with more than words_cap words has status CH_TRUNCATED,
+        its true n_words and its first words_cap words."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, max(words_cap, 1)), dtype=CHAIN_WORD_DTYPE)
+        self._check(self.L.sr_decode_onepass_dp(self.h, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n), C.c_uint32(frames_cap),
+                                                C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)), C.c_uint32(word_cost),
+                                                _vp(rec), _vp(words)))
+        return rec, words
+
+    def decode_onepass_dev(self, mfcc, frames, rec, words, words_cap=64, skip_cost=None, word_cost=0, frames_cap=0, frames_stride=1,
+                           stream=None):
+        """sr_decode_onepass_dp_dev on device tensors: mfcc int16 [n_rows, max_frames, 12]; frames as for spot_dev; rec int32
+        [n_rows, 4]; words int32 [n_rows, words_cap, 8].  Asynchronous on `stream`; returns (rec, words)."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and words.numel() == n * words_cap * 8
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_decode_onepass_dp_dev(self.h, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                    C.c_uint32(frames_cap), C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)),
+                                                    C.c_uint32(word_cost), _vp(rec), _vp(words), C.c_void_p(stream)))
+        return rec, words
+
+    def decode_onepass_pcm(self, pcm, start, end, mid, words_cap=64, skip_cost=None, word_cost=0):
+        """sr_decode_onepass_batch, the host whole path: mfcc_status() of segment [start[b], end[b]) of row b, then
+        decode_onepass() over those rows.  Returns dict(rec, words, mfcc, frm_num, status); a failed record has no parse."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        out = dict(rec=np.zeros(B, dtype=CHAIN_REC_DTYPE), words=np.zeros((B, max(words_cap, 1)), dtype=CHAIN_WORD_DTYPE),
+                   mfcc=np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16), frm_num=np.zeros(B, dtype=np.uint32),
+                   status=np.zeros(B, dtype=np.uint32))
+        self._check(self.L.sr_decode_onepass_batch(self.h, _vp(pcm), C.c_uint64(S), C.c_uint32(S), C.c_uint32(B), _vp(start), _vp(end),
+                                                   _vp(mid), C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)),
+                                                   C.c_uint32(word_cost), _vp(out["rec"]), _vp(out["words"]), _vp(out["mfcc"]),
+                                                   _vp(out["frm_num"]), _vp(out["status"])))
         return out
 
     # ---- word alternatives ----------------------------------------------------------------------------------
@@ -1378,6 +1430,18 @@ def decode_geometry(tpl_rows, max_frames, max_words=8, testing=False):
     if rc != 0:
         raise SrError(f"sr_decode_geometry error {rc}: {L.sr_last_error().decode()}")
     return dict(scratch_bytes=out[0], rows=out[1], max_tpl_rows=out[2], chunk_cols=out[3])
+
+
+def decode_onepass_geometry(tpl_rows, n_templates, max_frames, min_tpl_frames, testing=False):
+    """Host-only sr_decode_onepass_geometry for a store of n_templates slots whose longest template has tpl_rows rows and whose
+    shortest valid one min_tpl_frames frames: dict(state_bytes per row for keys, prefix costs and saved columns, rows per
+    launch group, block = frames per block (min_tpl_frames // 2 + 1), launches per group)."""
+    L = load_library(testing)
+    out = (C.c_uint32 * 4)()
+    rc = L.sr_decode_onepass_geometry(C.c_uint32(tpl_rows), C.c_uint32(n_templates), C.c_uint32(max_frames), C.c_uint32(min_tpl_frames), out)
+    if rc != 0:
+        raise SrError(f"sr_decode_onepass_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(state_bytes=out[0], rows=out[1], block=out[2], launches=out[3])
 
 
 def align_geometry(max_frames, ref_rows, testing=False):
