@@ -1380,6 +1380,16 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    sr_decode_onepass_geometry
  *   "onepass_rows"                   rows per launch group of the one-pass decoder (default: what 256 MiB of scratch hold);
  *                                    read per call and by sr_decode_onepass_geometry
+ *   "live_origin"                    samples (an int64 multiple of the hop) a fresh sr_live channel behaves as having consumed
+ *                                    before: received = the value, next frame = value / hop, in the device state and the host
+ *                                    mirror; nothing in the push path knows of it.  Read where a channel is made fresh
+ *                                    (sr_live_open, sr_live_end), which return SR_ERR_BAD_ARG and change nothing when the value
+ *                                    is negative, no multiple of the hop, or the session was opened without atap_in (a noise
+ *                                    head is defined from position 0).  Puts positions past 2^31 / 2^32 within a test's reach
+ *   "spot_live_origin"               frames (up to 0xFFFF0000) a fresh sr_spot_live channel stands at, with nothing reachable
+ *                                    before them: every saved column entry unreachable, no carry.  Read where a channel is made
+ *                                    fresh (sr_spot_live_open, sr_spot_live_end; SR_ERR_BAD_ARG above 0xFFFF0000), feature and
+ *                                    PCM sessions alike.  Puts columns up to the frame cap within a test's reach
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
  * Unknown names return SR_ERR_BAD_ARG. */

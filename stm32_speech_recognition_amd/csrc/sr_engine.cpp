@@ -23,7 +23,8 @@ static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc
                                                    "log_thr_from_host", "multi_allow_dup", "dtw_debug", "cells_literal",
                                                    "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols",
                                                    "align_pairs", "align_marks_global", "chain_chunk_cols", "chain_rows", "span_groups",
-                                                   "cluster_pairs", "forced_prune_off", "onepass_block", "onepass_rows"};
+                                                   "cluster_pairs", "forced_prune_off", "onepass_block", "onepass_rows", "live_origin",
+                                                   "spot_live_origin"};
 #endif
 }  // namespace sr
 

@@ -60,14 +60,34 @@ ConfigFraming framing_of(const sr_engine *h)
     return ConfigFraming{h->frame_len, h->hop, h->v_durmin, h->s_durmax, h->noise_len, h->cfg.max_frames};
 }
 
-LiveChan fresh_chan(const sr_live *l, uint32_t c)
+// development hook "live_origin" (testing build; 0 otherwise): the position a fresh channel starts at.  Refused unless it is a
+// whole number of hops in a session with given thresholds (a noise head is defined from position 0).
+int live_origin(const sr_live *l, uint64_t *origin)
+{
+    const int64_t v = dev_hook(kHookLiveOrigin);
+    if (v && (v < 0 || v % l->h->hop != 0 || !l->given))
+        return fail(SR_ERR_BAD_ARG, "development hook live_origin: a positive multiple of hop, in a session opened with atap_in");
+    *origin = (uint64_t)v;
+    return SR_OK;
+}
+
+LiveChan fresh_chan(const sr_live *l, uint32_t c, uint64_t origin)
 {
     LiveChan s{};
     if (l->given) {
         s.atap = l->atap0[c];
         s.atap_set = 1;
     }
+    s.received = origin;  // as if `origin` samples had been consumed in silence
+    s.next_frame = origin / l->h->hop;
     return s;
+}
+
+void fresh_mirror(sr_live *l, uint32_t c, uint64_t origin)
+{
+    l->received[c] = origin;
+    l->frames[c] = origin / l->h->hop;
+    l->head_done[c] = l->given ? 1 : 0;
 }
 
 // new whole frames of channel c after cnt more samples (0 while its noise head is incomplete)
@@ -274,10 +294,14 @@ int sr_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, const sr
     if (atap_in) l->atap0.assign(atap_in, atap_in + n_channels);
     l->received.assign(n_channels, 0);
     l->frames.assign(n_channels, 0);
-    l->head_done.assign(n_channels, l->given ? 1 : 0);
+    l->head_done.assign(n_channels, 0);
+    uint64_t origin = 0;
+    int rc = live_origin(l, &origin);
     std::vector<LiveChan> init(n_channels);
-    for (uint32_t c = 0; c < n_channels; c++) init[c] = fresh_chan(l, c);
-    int rc = SR_OK;
+    for (uint32_t c = 0; c < n_channels && !rc; c++) {
+        init[c] = fresh_chan(l, c, origin);
+        fresh_mirror(l, c, origin);
+    }
     if (!rc) rc = l->chan.reserve(n_channels);
     if (!rc) rc = l->ring.reserve((size_t)n_channels * l->ring_stride);
     if (!rc) rc = l->events.reserve((size_t)n_channels * l->ev_slots);
@@ -398,6 +422,8 @@ int sr_live_end(sr_live *l, const uint32_t *channels, uint32_t n_ch, sr_live_seg
     if (!l || (n_ch && (!channels || !segs))) return fail(SR_ERR_BAD_ARG, "null argument");
     for (uint32_t i = 0; i < n_ch; i++)
         if (channels[i] >= l->C) return fail(SR_ERR_BAD_ARG, "channel " + std::to_string(channels[i]) + " is past the session's last");
+    uint64_t origin = 0;
+    if (int rc = live_origin(l, &origin)) return rc;
     if (n_segs) *n_segs = 0;
     if (!n_ch) return SR_OK;
     sr_engine *h = l->h;
@@ -413,15 +439,10 @@ int sr_live_end(sr_live *l, const uint32_t *channels, uint32_t n_ch, sr_live_seg
     for (uint32_t i = 0; i < n_ch; i++) {
         const uint32_t c = channels[i];
         if (st[c].state >= sp) open.push_back(sr_live_seg{c, 0u, st[c].open_start, -1});
-        st[c] = fresh_chan(l, c);
+        st[c] = fresh_chan(l, c, origin);
     }
     COPY_UP(l->chan.p, st.data(), (size_t)l->C * sizeof(LiveChan));
-    for (uint32_t i = 0; i < n_ch; i++) {
-        const uint32_t c = channels[i];
-        l->received[c] = 0;
-        l->frames[c] = 0;
-        l->head_done[c] = l->given ? 1 : 0;
-    }
+    for (uint32_t i = 0; i < n_ch; i++) fresh_mirror(l, channels[i], origin);
     if (!open.empty()) std::memcpy(segs, open.data(), open.size() * sizeof(sr_live_seg));
     if (n_segs) *n_segs = (uint32_t)open.size();
     return SR_OK;

@@ -63,6 +63,23 @@ int relayout(sr_spot_live *l)
     return SR_OK;
 }
 
+// development hook "spot_live_origin" (testing build; 0 otherwise): the frame count a fresh channel stands at
+int spot_live_origin(uint32_t *origin)
+{
+    const int64_t v = dev_hook(kHookSpotLiveOrigin);
+    if (v < 0 || v > (int64_t)kSpotLiveMaxFrames) return fail(SR_ERR_BAD_ARG, "development hook spot_live_origin: 0..0xFFFF0000 frames");
+    *origin = (uint32_t)v;
+    return SR_OK;
+}
+
+// channel c fresh at a nonzero origin: nothing before it is reachable -- every saved column entry kSpotInf, no carry, the
+// carry's window 0xFFFFFFFF, which is what all-ones bytes say (the kernel reads the saved column whenever x0 != 0)
+int unreachable_before_origin(sr_spot_live *l, uint32_t c, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(l->state.p + (uint64_t)c * l->chan_stride, 0xFF, l->chan_stride, s));
+    return SR_OK;
+}
+
 struct PushPlan {
     std::vector<SpotLiveChan> chan;
     uint32_t rows = 0, max_n = 0, max_frames = 0, max_row = 0;  // windows completed; the largest count, frame count and [kept | chunk] row
@@ -229,6 +246,8 @@ int sr_spot_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uin
     } else if (chunk_max > R) {
         return fail(SR_ERR_BAD_ARG, "chunk_max not in 1..max_frames");
     }
+    uint32_t origin = 0;
+    if (int rc = spot_live_origin(&origin)) return rc;
     ENTER_DEVICE(h);
     sr_spot_live *l = new sr_spot_live();
     l->h = h;
@@ -237,9 +256,11 @@ int sr_spot_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uin
     l->win = win_frames;
     l->pcm = mid != nullptr;
     l->bound.assign(n_channels, h->store_serial);
-    l->frames.assign(n_channels, 0);
+    l->frames.assign(n_channels, origin);
     l->kept.assign(n_channels, 0);
     int rc = relayout(l);
+    for (uint32_t c = 0; c < n_channels && origin && !rc; c++) rc = unreachable_before_origin(l, c, nullptr);
+    if (!rc && origin && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SR_ERR_HIP, "hipStreamSynchronize failed");
     if (!rc) rc = l->d_chan.reserve(n_channels);
     if (!rc && mid) {
         l->mid.assign(mid, mid + n_channels);
@@ -405,6 +426,8 @@ int sr_spot_live_end(sr_spot_live *l, const uint32_t *channels, uint32_t n_ch, s
     for (uint32_t i = 0; i < n_ch; i++)
         if (channels[i] >= l->C) return fail(SR_ERR_BAD_ARG, "channel " + std::to_string(channels[i]) + " is past the session's last");
     sr_engine *h = l->h;
+    uint32_t origin = 0;
+    if (int rc = spot_live_origin(&origin)) return rc;
     const bool changed = l->layout_serial != h->store_serial;  // then every channel that holds state is bound to a store that is gone
     if (changed)
         if (int rc = check_store(h)) return rc;
@@ -441,9 +464,14 @@ int sr_spot_live_end(sr_spot_live *l, const uint32_t *channels, uint32_t n_ch, s
     else HIP_TRY(hipStreamSynchronize(nullptr));
     if (changed)
         if (int rc = relayout(l)) return rc;
+    if (origin) {  // behind the flush on the null stream; complete before a push on any stream can follow
+        for (const SpotLiveFlush &f : list)
+            if (int rc = unreachable_before_origin(l, f.channel, nullptr)) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+    }
     for (const SpotLiveFlush &f : list) {
         if (f.row != 0xFFFFFFFFu) wins[f.row] = sr_spot_win{f.channel, f.wid};
-        l->frames[f.channel] = 0;
+        l->frames[f.channel] = origin;
         l->kept[f.channel] = 0;
         l->bound[f.channel] = h->store_serial;
     }

@@ -7,6 +7,8 @@ resumed from one column, and the window records of a recording of any length.
   end_records     window records from the packed end-row values of a whole recording.
   window_records  the same for feature frames, through spot_ref.dp_end_row over the recording as ONE row: what a session must
                   emit for a channel, whatever the chunking.
+Both reductions take an `origin`: the records of the same frames when the first of them is frame `origin` of its channel and
+nothing before it is reachable (the development hook "spot_live_origin"): starts, ends and window cuts move, nothing else.
 Plain module: no fixtures, no pytest settings.
 """
 import numpy as np
@@ -43,35 +45,49 @@ def resume(d_chunk, state=None):
     return end, (pd, pm, x0 + n)
 
 
-def end_records(end, M, win):
-    """packed end-row values of columns 0..N-1 -> SPOT_DTYPE [ceil(N / win)]: per window the first minimum of q(e) over its
-    reachable end frames"""
-    end = np.asarray(end, np.uint64)
-    N = len(end)
-    ok = end != INF64
-    cost = np.where(ok, (end >> np.uint64(32)).astype(np.int64), -1)
-    start = np.where(ok, (end & np.uint64(0xFFFFFFFF)).astype(np.int64), 0)
-    q = ref.end_scores(cost, start, M)
-    out = np.empty(-(-N // win), ref.SPOT_DTYPE)
-    for w in range(len(out)):
-        out[w] = ref.window_hit(cost, start, q, w * win, (w + 1) * win)
+def n_window_rows(N, win, origin=0):
+    """windows that hold one of the frames [origin, origin + N), or stand open at origin: origin // win .. ceil((origin + N) / win) - 1"""
+    return -(-(int(origin) + int(N)) // int(win)) - int(origin) // int(win)
+
+
+def _reduce(cost, start, q, win, origin):
+    """per-end-frame results of the pushed frames AS THEIR OWN RECORDING (relative starts, q from relative figures: a path's
+    length does not move with it) -> SPOT_DTYPE [n_window_rows]: the windows cut at ABSOLUTE multiples of win when the first
+    pushed frame is frame `origin` of its channel, starts and ends absolute.  Row i is window origin // win + i; the first is
+    partial when origin % win != 0.  All in Python ints: positions reach 0xFFFF0000."""
+    N, win, origin = len(cost), int(win), int(origin)
+    w0 = origin // win
+    out = np.empty(n_window_rows(N, win, origin), ref.SPOT_DTYPE)
+    for i in range(len(out)):
+        lo, hi = max((w0 + i) * win - origin, 0), (w0 + i + 1) * win - origin
+        hit = ref.window_hit(cost, start, q, lo, hi)
+        out[i] = hit if hit == ref.NO_HIT else (hit[0], hit[1] + origin, hit[2] + origin, hit[3])
     return out
 
 
-def window_records(feat, tm, tf, valid, win):
-    """feat int16 [N, 12]: everything pushed to a channel; templates as spot_ref.spot_hits -> SPOT_DTYPE [ceil(N / win), K]; the
-    last window is the open one when N % win != 0"""
+def end_records(end, M, win, origin=0):
+    """packed end-row values of the pushed columns 0..N-1 (relative starts) -> SPOT_DTYPE [n_window_rows(N, win, origin)]: per
+    window the first minimum of q(e) over its reachable end frames; origin: see _reduce"""
+    end = np.asarray(end, np.uint64)
+    ok = end != INF64
+    cost = np.where(ok, (end >> np.uint64(32)).astype(np.int64), -1)
+    start = np.where(ok, (end & np.uint64(0xFFFFFFFF)).astype(np.int64), 0)
+    return _reduce(cost, start, ref.end_scores(cost, start, M), win, origin)
+
+
+def window_records(feat, tm, tf, valid, win, origin=0):
+    """feat int16 [N, 12]: everything pushed to a channel; templates as spot_ref.spot_hits -> SPOT_DTYPE [n_window_rows, K]
+    (ceil(N / win) rows for origin 0); the last window is the open one when (origin + N) % win != 0.  origin: the channel's
+    frame count before the first pushed frame, nothing before it reachable (see _reduce)"""
     N, K = len(feat), len(tm)
-    out = np.empty((-(-N // win), K), ref.SPOT_DTYPE)
+    out = np.empty((n_window_rows(N, win, origin), K), ref.SPOT_DTYPE)
     out[...] = ref.NO_HIT
     for k in range(K):
         M = int(tf[k]) if valid is None or valid[k] else 0
         if M == 0 or N == 0:
             continue
         cost, start = ref.dp_end_row(ref.local_dis(feat, tm[k, :M]))
-        q = ref.end_scores(cost, start, M)
-        for w in range(out.shape[0]):
-            out[w, k] = ref.window_hit(cost, start, q, w * win, (w + 1) * win)
+        out[:, k] = _reduce(cost, start, ref.end_scores(cost, start, M), win, origin)
     return out
 
 
