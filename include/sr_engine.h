@@ -1231,7 +1231,7 @@ int sr_gather_word_spans(sr_engine *h, const int16_t *mfcc, const uint32_t *in_f
  *   limits   skip_cost <= 65 535 or SR_DIS_ERR; word_cost <= 2^24 and (frames_cap / L) * word_cost <= 2^30: a row holds at
  *            most N / L words, and 3 * 16 383 * 65 536 + 2^30 < 2^32 - 1, so u32 costs stay exact; a store of at most 65 536
  *            slots.  Arguments outside these limits are refused.
- * Out of scope: a live (push) form, grammars, n_words_exact, N-best sequences. */
+ * Out of scope: grammars, n_words_exact, N-best sequences.  (The push-by-push session is the next section.) */
 #define SR_CH_TRUNCATED 2u
 /* Stage level, DEVICE buffers: d_mfcc / d_in_frames / frames_stride as for sr_decode_words_dp_dev.  frames_cap is a HOST-side
  * bound on the frames of every row, 0 = max_frames: N is clamped to min(max_frames, frames_cap), and frames_cap fixes the
@@ -1258,6 +1258,93 @@ int sr_decode_onepass_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stri
  * scratch hold, 65 535 at most), out[2] = the block length L = min_tpl_frames / 2 + 1, out[3] = launches per group,
  * 2 * ceil(max_frames / L) + 2. */
 int sr_decode_onepass_geometry(uint32_t tpl_rows, uint32_t K, uint32_t max_frames, uint32_t min_tpl_frames, uint32_t out[4]);
+
+/* ------------------------------------------------------------------ live one-pass connected-word decoding: no word cap, state carried between pushes
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  The live connected-word decoding section holds at most 16 words per recording
+ * and pays max_words levels per push.  A session of this section takes the frames of n_channels channels as they arrive, in
+ * pushes of any size up to chunk_max, keeps per channel ONE A / E history, per (channel, slot) ONE saved column and the
+ * channel's feature row on the device between calls, and after every push says how everything heard so far parses under the
+ * one-pass section's definition: as many words as the frames allow, 2 x n x K x M cells per push of n frames, plus a trace.
+ * No existing call, record or byte changes.
+ * THE RULE: let Y_c be every feature frame pushed to channel c since it was opened or last ended, N = |Y_c|; N is at most
+ * utt_frames, fixed at open in 1..16 383 (the u32 cost bound and the 16-bit start field of a key end there).  Every push
+ * emits one row for every channel with n[c] > 0, by ascending channel: an sr_chain_rec and words_cap x sr_chain_word, compact
+ * and labelled with sr_chain_live_row.  The row is, byte for byte, what the one-pass section defines for Y_c as ONE row of N
+ * frames with the session's words_cap, skip_cost, word_cost and the engine's current word map -- whatever the chunking.
+ * Whenever an engine's max_frames >= N it therefore equals what sr_decode_onepass_dp[_dev] writes for that row, under ties
+ * too: the definition is the same and so is the tie rule.  start and end are 0-based frame indices of the channel's
+ * recording.
+ *   flags    0: the batch call's truncation -- when n_words > words_cap the FIRST words_cap words are written, n_words is the
+ *            true count and status is SR_CH_TRUNCATED.  SR_OP_LIVE_TAIL: the LAST words_cap words of the trace instead, in
+ *            spoken order in entries 0..words_cap-1 (a feed that runs past words_cap words wants the recent ones); the record
+ *            is the same.  Any other flag is refused.
+ *   blocks   why it is exact: the one-pass section's block argument asks of a block only that it is at most L frames long.  A
+ *            push of n[c] frames is cut into ceil(n[c] / L) blocks; the first resumes from the column saved at the first frame
+ *            of the channel's last block, whichever push that was in.  A word that starts inside a block cannot end inside
+ *            it, so A and E over a block follow from E at or before its first frame.  A(p) and E(p) depend on frames < p
+ *            only: the history of a recording is a prefix of that of any longer one, and the trace reads A, E and N.
+ *   state    per channel on the device: A (u64) and E (u32) over utt_frames + 1 positions; one saved exact column per slot,
+ *            K x tpl_rows x 16 bytes; and the channel's WHOLE feature row, utt_frames x 24 bytes, of which a block sweeps the
+ *            at most L - 1 frames before the push again (a ring of L - 1 frames would do; the whole row needs no wrap and
+ *            survives a store whose L differs).  Nothing is read back: the host mirror knows every channel's N and the first
+ *            frame of its last block.
+ *   limits   the one-pass section's; (utt_frames / L) * word_cost <= 2^30 is checked at open against the current store and
+ *            again at every push.
+ * PCM sessions (mid given at open): the channel's samples X_c, R = |X_c|, are framed exactly as the live word spotting section
+ * frames them (a segment with start = 1, end = R and mid[c]); n[c] counts samples, a row is emitted for n[c] > 0 whether or
+ * not a frame was completed, and while there are at most max_frames frames the row equals sr_decode_onepass_batch(X_c, 1, R,
+ * mid[c]).
+ * Refusals, stream ordering and the binding of a channel to its template store are the live connected-word decoding
+ * section's: a call refused for its arguments, its counts or the store is refused before anything is enqueued, writes nothing
+ * and changes no state; a push on another stream than the last push's is ordered behind it by an event; a push to a channel
+ * whose store has been replaced returns SR_ERR_BAD_ARG until that channel is ended, and it ends with the SR_CH_NONE record.
+ * The session uses its engine's scratch buffers: the engine's one-caller-at-a-time rule covers its sessions.
+ * Out of scope: recordings past 16 383 frames (committing and forgetting a prefix), grammars, n_words_exact, N-best
+ * sequences, a "stable prefix" marker. */
+#define SR_OP_LIVE_TAIL 1u
+typedef struct sr_onepass_live sr_onepass_live;
+/* host-only, no device: a store of K slots whose longest template has tpl_rows rows and whose shortest valid one has
+ * min_tpl_frames frames.  out[0] = device state bytes per channel, (utt_frames + 1) * 12 + K * tpl_rows * 16 + utt_frames * 24,
+ * saturating; out[1] = the longest template that fits (sr_spot_geometry's out[2]); out[2] = L = min_tpl_frames / 2 + 1;
+ * out[3] = the kernel launches a feature push of chunk_max frames enqueues at most, 2 * ceil(chunk_max / L) + 1: a sweep and a
+ * close per block, and the trace (no launch initialises anything: see k_onepass_live.hip).  tpl_rows and utt_frames 1..16 383,
+ * K 1..65 536, min_tpl_frames 1..tpl_rows, chunk_max 1..utt_frames. */
+int sr_onepass_live_geometry(uint32_t tpl_rows, uint32_t K, uint32_t min_tpl_frames, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[4]);
+/* mid NULL: a feature session, chunk_max in frames, 1..utt_frames.  mid a HOST array [n_channels]: a PCM session, chunk_max in
+ * samples; SR_ERR_BAD_ARG if a push of chunk_max samples could complete more than min(max_frames, utt_frames) frames.
+ * n_channels 1..65535, words_cap >= 1.  Argument limits and configuration errors exactly as sr_decode_onepass_dp_dev. */
+int sr_onepass_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames, uint32_t words_cap, uint32_t flags,
+                         uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid, sr_onepass_live **out);
+void sr_onepass_live_close(sr_onepass_live *l); /* before sr_destroy of its engine; waits for the session's last push */
+/* One push: sr_decode_live_push_dev's arguments and rules without level costs.  n: HOST array [n_channels] in both forms,
+ * 0 <= n[c] <= chunk_max, 0 leaves the channel untouched; NULL: n_all each.  Channel c's new frames are d_mfcc + c*row_stride;
+ * nothing past n[c] frames of a row is read.  DEVICE form: d_mfcc 8-byte aligned, row_stride a multiple of 4; ONE asynchronous
+ * operation on `stream`, no host synchronisation, no read-back.  d_rec[r] and d_words[r*words_cap + i] are COMPACT over the
+ * emitted rows r; rows at and past *n_rows are not written.  rows[max_rows] and *n_rows are HOST outputs, filled from the
+ * counts alone before the call returns.  Refused (SR_ERR_BAD_ARG): the word-cost bound against the current store, a count
+ * above chunk_max, a channel bound to a replaced store, a push that would take a channel past utt_frames, max_rows below the
+ * number of channels with n[c] > 0, a word map that does not fit, a null required pointer, outputs that overlap. */
+int sr_onepass_live_push_dev(sr_onepass_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                             uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows, uint32_t *n_rows,
+                             void *stream);
+/* the same on HOST buffers (2-byte aligned rows, any row_stride that holds the largest count) */
+int sr_onepass_live_push(sr_onepass_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                         uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows);
+/* PCM sessions: channel c's new samples are d_pcm + c*pcm_stride, n in samples; alignment rules as sr_spot_live_push_pcm_dev
+ * (device form: 16-byte aligned, pcm_stride a multiple of 8).  The spot session's copy kernels and the frame kernel launch of
+ * sr_mfcc_batch_dev turn them into the push's new frames, the decoder runs over those. */
+int sr_onepass_live_push_pcm_dev(sr_onepass_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                                 uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows,
+                                 uint32_t *n_rows, void *stream);
+int sr_onepass_live_push_pcm(sr_onepass_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                             uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows);
+/* The listed channels' recordings end here: HOST outputs rec[n_ch], words[n_ch][words_cap] and rows[n_ch], of which *n_rows
+ * rows are written -- one per DISTINCT listed channel, at its first mention: the parse of everything pushed to it (an empty
+ * channel gives the SR_CH_NONE record).  Waits for the device.  Each listed channel is then as freshly opened, and bound to
+ * the current store.  rows overlapping rec or words is refused like outputs that overlap in a push.  HIP failures as in
+ * sr_decode_live_end. */
+int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
+                        sr_chain_live_row *rows, uint32_t *n_rows);
 
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
@@ -1377,7 +1464,8 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    when that is 0, "spot_chunk_cols") and "chain_rows" as the decoder does
  *   "onepass_block"                  frames per block of the one-pass decoder, clamped to 1..L (a longer block would be wrong;
  *                                    the same bytes come out of every admissible length); read per call and by
- *                                    sr_decode_onepass_geometry
+ *                                    sr_decode_onepass_geometry; the live one-pass session reads it per push, and
+ *                                    sr_onepass_live_geometry reads it likewise
  *   "onepass_rows"                   rows per launch group of the one-pass decoder (default: what 256 MiB of scratch hold);
  *                                    read per call and by sr_decode_onepass_geometry
  *   "live_origin"                    samples (an int64 multiple of the hop) a fresh sr_live channel behaves as having consumed

@@ -167,26 +167,8 @@ __global__ void __launch_bounds__(256) k_onepass_close(const OnePassArgs a, cons
     }
 }
 
-// the first position q in [1, p] from above whose own word closes E there (A(q) reachable and A(q).cost == E(q)), 64 positions
-// per step; returns q and its key, or 0: the rest of the row is filler
-__device__ __forceinline__ uint32_t onepass_word_at(const unsigned long long *A, const uint32_t *E, uint32_t p, uint32_t lane, uint64_t *key)
-{
-    while (p >= 1) {  // (uniform)
-        const bool mine = lane < p;  // position p - lane >= 1
-        const uint64_t ky = mine ? A[p - lane] : kSpotInf;
-        const uint32_t e = mine ? E[p - lane] : kChainNone;
-        const unsigned long long hit = __ballot(mine && ky != kSpotInf && (uint32_t)(ky >> 32) == e);
-        if (hit) {
-            const uint32_t first = (uint32_t)__ffsll((long long)hit) - 1u;
-            *key = spot_shfl(ky, first);
-            return p - first;
-        }
-        p = p > 64u ? p - 64u : 0u;
-    }
-    return 0u;
-}
-
-// one wave per row: the history is walked twice, first for the count, then for the words in spoken order
+// one wave per row: the history is walked twice (onepass_word_at, sr_spot_dev.h), first for the count, then for the words in
+// spoken order
 __global__ void __launch_bounds__(64) k_onepass_trace(const OnePassArgs a)
 {
     const uint32_t row = blockIdx.x, lane = threadIdx.x, P = a.max_frames + 1u, W = a.words_cap;

@@ -1,0 +1,252 @@
+// k_onepass_live.hip -- live one-pass connected-word decoding (include/sr_engine.h, "live one-pass connected-word decoding"):
+// k_onepass.hip's blocks with the boundaries set by the caller's pushes, per channel and of unequal length.  OPT-IN EXTENSION,
+// no reference counterpart.  gfx950 (MI355X, CDNA4) only; wave = 64 lanes; integer VALU + LDS.
+//
+// The batch kernel's argument carries over: a word that starts inside a block of at most L = min_k(M_k / 2 + 1) frames cannot
+// end inside it, so A and E over a block follow from E at or before its first frame -- whatever the lengths of the blocks
+// before it.  A channel keeps A and E over its whole recording, per slot the EXACT column at the first frame c0 of the block
+// swept last, and its feature row.  A push that appends the frames [x0, x0 + n) is, per block b = 0.. of `block` <= L frames,
+// in stream order:
+//   k_onepass_live_words   k_onepass_words with (xs, c0, cN) per channel from the plan table: c0 = x0 + b * block, the sweep
+//                          starts behind the saved column (that of the last push's last block for b = 0).  Columns before x0
+//                          come from the channel's kept feature row, the rest from the push.  A channel with fewer than b + 1
+//                          blocks leaves (wave-uniform);
+//   k_onepass_live_close   k_onepass_close per channel; it also appends the block's frames to the kept feature row, which no
+//                          sweep of this push reads at those columns;
+//   k_onepass_live_trace   k_onepass_trace with N = x0 + n into the compact row the host assigned, the first words_cap words
+//                          or (tail) the last.
+// No init launch: a position of A that no push has reached holds all ones from the open call on, and the end call puts that
+// back (k_onepass_live_wipe); E(0) = 0 never changes.  No workgroup waits on another: the blocks are ordered by the stream
+// alone.  Plain vector stores; the atomic minimum on A is the only atomic, and it does not depend on the order of the waves, so
+// two runs give the same bytes.
+#include "sr_dtw_plan.h"
+#include "sr_spot_dev.h"
+
+namespace sr {
+
+// block b of a channel: frames [c0, cN); false: the channel has no such block (a silent channel has none at all)
+__device__ __forceinline__ bool onepass_live_block(const OnePassLiveArgs &a, const SpotLiveChan &ch, uint32_t b, uint32_t *c0, uint32_t *cN)
+{
+    const uint32_t end = ch.x0 + ch.n;  // <= utt_frames <= 16 383, and b * block < 16 384: no wrap
+    *c0 = ch.x0 + b * a.block;
+    *cN = end - *c0 < a.block ? end : *c0 + a.block;
+    return *c0 < end;
+}
+
+__global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_live_words(const OnePassLiveArgs a, const uint32_t b)
+{
+    extern __shared__ __attribute__((aligned(16))) u32x4 ol_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
+    const uint32_t k = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.y * kSpotWaves + w;
+    uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
+    M = M < a.tpl_len ? M : a.tpl_len;
+    ulonglong2 *s_col = (ulonglong2 *)(ol_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
+    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
+        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
+        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+        ol_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
+        ol_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
+    }
+    __syncthreads();
+    if (c >= a.C || !M) return;  // (an invalid slot ends no word and keeps no column)
+    const SpotLiveChan ch = a.chan[c];
+    uint32_t c0, cN;
+    if (!onepass_live_block(a, ch, b, &c0, &cN)) return;  // (wave-uniform)
+    // the sweep starts behind the saved column: that of this push's last block, or of the last push's (none at frame 0)
+    const uint32_t xs = c0 ? (b ? c0 - a.block : ch.aux) + 1u : 0u;
+
+    ulonglong2 *g_col = a.cols + ((size_t)c * a.K + k) * a.tpl_len;
+    const uint32_t *E = a.E + (size_t)c * a.P;
+    unsigned long long *A = a.A + (size_t)c * a.P;
+    if (xs) {  // resume: the saved column, that of xs - 1 (16-byte loads, coalesced over template rows)
+        for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
+        wave_sync();
+    }
+    const int16_t *kept = a.feat + (size_t)c * (a.P - 1u) * kCoef;  // the columns before the push
+    const int16_t *in = a.mfcc + (uint64_t)c * a.row_stride;         // the columns [x0, x0 + n)
+    for (uint32_t s0 = xs; s0 < cN; s0 += 64) {  // (wave-uniform)
+        const uint32_t col = s0 + lane;
+        const bool live = col < cN;
+        const uint32_t last = (cN - s0 < 64u ? cN - s0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
+        const bool keep = col == c0;                                // the exact column the next block resumes from
+        Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
+        uint32_t charge = kChainNone;  // E(col): what a word that starts in this column builds on; none yet inside the block
+        if (live) {
+            const uint2 *src = (const uint2 *)(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
+            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+            fi.w[6] = (uint32_t)dot_rows(fi, fi);
+            if (col <= c0) charge = E[col];
+        }
+        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
+        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
+        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
+        const uint32_t steps = M + last;
+        for (uint32_t t = 0; t < steps; t++) {
+            const int r = (int)t - (int)lane;
+            // the left lane's results of the previous step are the states of (col - 1, r)
+            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
+            if (lane == 0) {
+                fl_d = fl_m = kSpotInf;
+                if (s0 != 0 && t < M) {  // column s0 - 1: this launch's last sweep, or the saved column (none for column 0)
+                    const ulonglong2 v = s_col[t];
+                    fl_d = v.x;
+                    fl_m = v.y;
+                }
+            }
+            if (live && r >= 0 && r < (int)M) {
+                const Row32 fm = row_from(ol_smem[2 * r], ol_smem[2 * r + 1]);
+                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
+                uint64_t cd = kSpotInf, cn;
+                if (r > 0) {
+                    cd = spot_add(diag, d);
+                    cn = spot_add(spot_min(fl_d, up_d), d);
+                } else {  // row 0: a charged start, of the non-diagonal kind
+                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
+                }
+                up_d = cd;
+                up_m = spot_min(cd, cn);
+                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
+                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
+                if (r == (int)M - 1) end_v = up_m;
+            }
+            diag = fl_m;
+        }
+        wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
+
+        // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1); col + 1 <= cN <= utt_frames
+        if (live && col >= c0 && end_v != kSpotInf) {
+            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
+            atomicMin(&A[col + 1], (unsigned long long)key);
+        }
+    }
+}
+
+// E(p), p in (c0, cN], as k_onepass_close gives it, per channel; before it, the block's frames go to the kept feature row.
+// One workgroup per channel: wave scans plus an LDS carry.
+__global__ void __launch_bounds__(256) k_onepass_live_close(const OnePassLiveArgs a, const uint32_t b)
+{
+    __shared__ uint64_t s_tot[4];
+    const uint32_t c = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const SpotLiveChan ch = a.chan[c];
+    uint32_t c0, cN;
+    if (!onepass_live_block(a, ch, b, &c0, &cN)) return;  // (uniform)
+    {  // 24-byte rows as three 8-byte words each; both sides are 8-byte aligned
+        const uint2 *src = (const uint2 *)(a.mfcc + (uint64_t)c * a.row_stride + (size_t)(c0 - ch.x0) * kCoef);
+        uint2 *dst = (uint2 *)(a.feat + ((size_t)c * (a.P - 1u) + c0) * kCoef);
+        for (uint32_t i = threadIdx.x; i < (cN - c0) * 3u; i += 256) dst[i] = src[i];
+    }
+    const unsigned long long *A = a.A + (size_t)c * a.P;
+    uint32_t *E = a.E + (size_t)c * a.P;
+    if (a.skip_cost == kChainNone) {  // no skipping: the costs themselves (all ones stays SR_DIS_ERR)
+        for (uint32_t p = c0 + 1 + threadIdx.x; p <= cN; p += 256) E[p] = (uint32_t)(A[p] >> 32);
+        return;
+    }
+    const uint64_t skip = a.skip_cost;
+    const uint32_t e_c0 = E[c0];  // (written by the last block's close, in this push or the last; 0 at frame 0)
+    uint64_t carry = e_c0 == kChainNone ? kSpotInf : (uint64_t)e_c0 + (uint64_t)(cN - c0) * skip;
+    for (uint32_t p0 = c0 + 1; p0 <= cN; p0 += 256) {  // (uniform)
+        const uint32_t p = p0 + threadIdx.x;
+        uint64_t v = kSpotInf;
+        if (p <= cN) {
+            const uint64_t key = A[p];
+            if (key != kSpotInf) v = (key >> 32) + (uint64_t)(cN - p) * skip;
+        }
+#pragma unroll
+        for (uint32_t by = 1; by < 64; by <<= 1) {
+            const uint64_t o = spot_shfl_up(v, by);
+            if (lane >= by) v = spot_min(v, o);
+        }
+        if (lane == 63) s_tot[w] = v;
+        __syncthreads();
+        uint64_t m = spot_min(v, carry);
+        for (uint32_t i = 0; i < w; i++) m = spot_min(m, s_tot[i]);
+        if (p <= cN) E[p] = m != kSpotInf ? (uint32_t)(m - (uint64_t)(cN - p) * skip) : kChainNone;
+        for (uint32_t i = 0; i < 4; i++) carry = spot_min(carry, s_tot[i]);
+        __syncthreads();  // s_tot is read before the next round overwrites it
+    }
+}
+
+// one wave per emitting channel: the history of its N = x0 + n frames is walked twice (onepass_word_at, sr_spot_dev.h), first
+// for the count, then for the words in spoken order -- the first words_cap of them, or (tail) the last, where the second walk
+// ends as soon as they are written
+__global__ void __launch_bounds__(64) k_onepass_live_trace(const OnePassLiveArgs a)
+{
+    const uint32_t c = blockIdx.x, lane = threadIdx.x, W = a.words_cap;
+    const SpotLiveChan ch = a.chan[c];
+    if (!ch.first_win) return;
+    const uint32_t N = ch.x0 + ch.n;
+    const unsigned long long *A = a.A + (size_t)c * a.P;
+    const uint32_t *E = a.E + (size_t)c * a.P;
+    sr_chain_rec *rec = a.rec + ch.row_base;
+    sr_chain_word *words = a.words + (size_t)ch.row_base * W;
+    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const uint32_t total = N ? E[N] : kChainNone;
+    if (total == kChainNone) {  // (uniform) an empty channel or no parse
+        for (uint32_t i = lane; i < W; i += 64) words[i] = none;
+        if (lane == 0) *rec = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
+        return;
+    }
+    uint32_t n = 0, in_words = 0;
+    for (uint32_t p = N; p;) {  // (uniform) the count; every start lies below its end position: the walk ends
+        uint64_t key = kSpotInf;
+        const uint32_t q = onepass_word_at(A, E, p, lane, &key);
+        if (!q) break;
+        const uint32_t start = (uint32_t)(key >> 16) & 0xFFFFu;
+        n++;
+        in_words += q - start;  // frames start .. q - 1
+        p = start;
+    }
+    const uint32_t shown = n < W ? n : W, first = a.tail ? n - shown : 0u;  // the words first .. first + shown - 1 are written
+    for (uint32_t i = shown + lane; i < W; i += 64) words[i] = none;
+    uint32_t i = n;
+    for (uint32_t p = N; p && i > first;) {  // (uniform)
+        uint64_t key = kSpotInf;
+        const uint32_t q = onepass_word_at(A, E, p, lane, &key);
+        if (!q) break;
+        const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu, end = q - 1;
+        i--;
+        if (lane == 0 && i - first < shown) {
+            const uint32_t acc = (uint32_t)(key >> 32) - a.word_cost - E[start];
+            words[i - first] =
+                sr_chain_word{a.word_id[a.group_of_slot[slot]], slot, start, end, acc, acc / (end - start + 1 + a.tpl_frames[slot]), E[q], 0u};
+        }
+        p = start;
+    }
+    if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, n > W ? SR_CH_TRUNCATED : SR_CH_OK};
+}
+
+// sr_onepass_live_end, behind the trace: the keys of every listed channel are all ones again over the positions it had reached
+__global__ void __launch_bounds__(256) k_onepass_live_wipe(const OnePassLiveArgs a)
+{
+    const uint32_t c = blockIdx.x;
+    const SpotLiveChan ch = a.chan[c];
+    if (!ch.first_win) return;
+    unsigned long long *A = a.A + (size_t)c * a.P;
+    for (uint32_t p = 1 + threadIdx.x; p <= ch.aux; p += 256) A[p] = kSpotInf;  // aux <= utt_frames = P - 1
+}
+
+void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_t s)
+{
+    if (!a.C || !a.K) return;
+    const size_t lds = spot_lds_bytes(a.tpl_len);
+    const dim3 grid(a.K, (a.C + kSpotWaves - 1) / kSpotWaves);
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        hipLaunchKernelGGL(k_onepass_live_words, grid, dim3(64 * kSpotWaves), lds, s, a, b);
+        hipLaunchKernelGGL(k_onepass_live_close, dim3(a.C), dim3(256), 0, s, a, b);
+    }
+    hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
+}
+void launch_onepass_live_end(const OnePassLiveArgs &a, hipStream_t s)
+{
+    if (!a.C) return;
+    hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_onepass_live_wipe, dim3(a.C), dim3(256), 0, s, a);
+}
+const char *onepass_live_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_onepass_live_words, "k_onepass_live_words"}}, bytes);
+}
+
+}  // namespace sr

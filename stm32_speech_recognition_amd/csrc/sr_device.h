@@ -35,7 +35,7 @@ enum DevHook {
     kHookSpanGroups,      // "span_groups": groups of spans per launch of the span scorer (default 65 535, the grid's limit; read per call)
     kHookClusterPairs,    // "cluster_pairs": (example, model) pairs per launch of the clustering score pass (default 2^20; read per call)
     kHookForcedPruneOff,  // "forced_prune_off": the forced aligner sweeps every end frame of every level (no column bound; read per call)
-    kHookOnePassBlock,    // "onepass_block": frames per block of the one-pass decoder, clamped to 1..L (read per call and by sr_decode_onepass_geometry)
+    kHookOnePassBlock,    // "onepass_block": frames per block of the one-pass decoder, clamped to 1..L (read per call and push, and by the two one-pass geometry calls)
     kHookOnePassRows,     // "onepass_rows": rows per launch group of the one-pass decoder (read per call and by sr_decode_onepass_geometry)
     kHookLiveOrigin,      // "live_origin": samples a fresh sr_live channel behaves as having consumed before (a multiple of hop; read at open / end)
     kHookSpotLiveOrigin,  // "spot_live_origin": frames a fresh sr_spot_live channel stands at (up to 0xFFFF0000; read at open / end)
@@ -315,7 +315,8 @@ struct SpotLiveChan {  // 32 bytes, one per channel and push
     uint32_t kept;       // PCM sessions: samples kept from earlier pushes, new samples, and the samples at the front of
     uint32_t n_samp;     // [kept | chunk] that no later frame needs (new frames * hop)
     uint32_t drop;
-    uint32_t _pad;
+    uint32_t aux;        // one-pass live sessions (OnePassLiveArgs) -- a push: the first frame of the block the channel's saved
+                         // columns are of; the end call: the frames the channel holds.  Every other session: 0
 };
 // the carry: the first minimum so far of the window the channel's last frame lies in, two 16-byte words
 // {key = q << 32 | end (all ones = none; an invalid slot keeps it that way), start | cost << 32}, {window id, 0}
@@ -473,6 +474,44 @@ struct OnePassArgs {
 };
 // init, per block of the host's list (sr_onepass_plan.h) (k_onepass_words, k_onepass_close), k_onepass_trace
 void launch_onepass(const OnePassArgs &a, const OnePassBlock *blocks, uint32_t n_blocks, hipStream_t s);
+
+// live one-pass connected-word decoding (k_onepass_live.hip): k_onepass.hip's blocks with the boundaries set by the caller's
+// pushes.  Per channel the session keeps the history A[C][P] / E[C][P], P = utt_frames + 1, in OnePassArgs' layout, one saved
+// column per slot, cols[C][K][tpl_len] -- the EXACT column at the first frame of the block swept last, chan[c].aux -- and the
+// channel's whole feature row feat[C][utt_frames][12], of which a sweep reads the columns before the push.  A position of A no
+// push has reached holds all ones (set at open, put back by the end call); E(0) = 0.  The per-channel entry is the spot
+// session's: x0, n; row_base = the channel's compact output row; first_win != 0 = the channel emits a row.  A push's frames
+// [x0, x0 + n) are cut into blocks of `block` frames; launch b sweeps block b of every channel that has one.
+struct OnePassLiveArgs {
+    const int16_t *mfcc;        // channel c's new frames at mfcc + c * row_stride, 8-byte aligned rows
+    uint64_t row_stride;        // s16 elements
+    const SpotLiveChan *chan;   // [C]
+    uint32_t C;
+    const int16_t *tpl;         // [K][tpl_stride]
+    const uint32_t *tpl_frames;
+    const uint8_t *tpl_valid;
+    uint32_t K;
+    uint32_t tpl_stride;
+    uint32_t tpl_len;           // the longest template: rows of the LDS image and of a saved column
+    uint32_t P;                 // utt_frames + 1: positions of the history
+    uint32_t block;             // frames per block, 1..max(L, 1)
+    uint32_t words_cap;
+    uint32_t tail;              // SR_OP_LIVE_TAIL: the last words_cap words instead of the first
+    uint32_t skip_cost;         // SR_DIS_ERR: no skipping
+    uint32_t word_cost;
+    ulonglong2 *cols;
+    unsigned long long *A;
+    uint32_t *E;
+    int16_t *feat;
+    const uint32_t *group_of_slot;
+    const uint32_t *word_id;
+    sr_chain_rec *rec;          // [rows], compact over the emitting channels
+    sr_chain_word *words;       // [rows][words_cap]
+};
+void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_t s);  // n_blocks x (words, close), trace
+// sr_onepass_live_end: the trace of the listed channels (n = 0, x0 = the frames to parse), then all ones over their keys again
+// (positions 1..aux: the frames the channel held)
+void launch_onepass_live_end(const OnePassLiveArgs &a, hipStream_t s);
 
 // grammar-constrained decoding (k_gram.hip): k_chain's levels over a word network of n_states states.  c is the decoder's
 // argument block with the scratch in the grammar's layout: c.A[row][level 1..max_words][state][max_frames + 1], c.E[row][level

@@ -169,6 +169,7 @@ const char *span_allow_lds(uint32_t bytes);
 const char *cluster_allow_lds(uint32_t bytes);
 const char *forced_allow_lds(uint32_t bytes);
 const char *onepass_allow_lds(uint32_t bytes);
+const char *onepass_live_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

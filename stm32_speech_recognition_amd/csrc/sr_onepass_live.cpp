@@ -1,0 +1,341 @@
+// Live one-pass connected-word decoding (include/sr_engine.h, "live one-pass connected-word decoding"): feature frames or
+// samples that arrive in pushes; per channel the one-pass decoder's A / E history, one saved column per slot and the feature
+// row kept on the device between calls (k_onepass_live.hip).  OPT-IN EXTENSION, NO REFERENCE COUNTERPART.
+//
+// The host knows every count: each channel's frames so far and the first frame of its last block, hence which channels a push
+// touches, how their new frames are cut into blocks and which compact output row each of them gets (the mirror,
+// sr_onepass_live_plan.h).  Nothing is read back to size or to label an output.  What the two level sessions do alike on the
+// host (sr_decode_live_host.h) serves here too: `m` and `max_words` are the names those rules know the mirror and the word
+// rows of an output row by.
+#include "sr_onepass_live_plan.h"
+#include "sr_decode_live_host.h"
+
+using namespace sr;
+
+struct sr_onepass_live {
+    sr_engine *h = nullptr;
+    OnePassLiveMirror om;
+    DecodeLiveMirror &m = om.d;
+    uint32_t max_words = 0, n_words_exact = 0;  // words_cap; no count is given
+    uint32_t tail = 0, skip_cost = 0, word_cost = 0;
+    std::vector<uint32_t> mid;            // PCM sessions: the channels' mid values
+    // layout of the saved columns: that of the store the session was opened or last reset against
+    uint32_t K = 0, tpl_len = 0;
+    uint64_t layout_serial = 0;
+    DevBuf<ulonglong2> cols;              // [C][K][tpl_len]
+    DevBuf<unsigned long long> A;         // [C][utt_frames + 1]
+    DevBuf<uint32_t> E;                   // [C][utt_frames + 1]
+    DevBuf<int16_t> hist;                 // [C][utt_frames][12]: the channels' feature rows
+    DevBuf<SpotLiveChan> d_chan;
+    // PCM sessions: kept samples, the rows [kept | chunk], their records and the features of one push
+    DevBuf<uint16_t> keep, stage;
+    DevBuf<sr_vad_rec> recs;
+    DevBuf<int16_t> feat;
+    uint32_t keep_stride = 0;
+    uint64_t stage_stride = 0;
+    hipEvent_t ev_last = nullptr;         // end of the last push (sr_onepass_live_end / _close wait for it)
+    hipStream_t last_stream = nullptr;    // ... and the stream it ran on: a push on another stream runs behind it
+    bool pending = false;
+};
+
+namespace {
+
+constexpr uint32_t kOnePassLiveMaxChannels = 65535u;  // a grid dimension
+constexpr uint32_t kOnePassLiveMaxFrames = 16383u;    // the u32 cost bound and the 16-bit start of a key
+
+uint32_t block_hook()
+{
+    const int64_t v = dev_hook(kHookOnePassBlock);  // testing build: short blocks put seams into small test shapes
+    return v > 0 ? (uint32_t)std::min<int64_t>(v, 16383) : 0u;
+}
+
+// the decoder's conditions on the engine, the store, the word map and the costs (the word-cost bound is the plan's)
+int check_store(const sr_onepass_live *l) { return check_chain(l->h, 1, 0, l->skip_cost, l->word_cost); }
+
+// the saved columns laid out for the engine's current store (nothing of value is in them: see sr_onepass_live_end)
+int relayout(sr_onepass_live *l)
+{
+    const sr_engine *h = l->h;
+    const uint32_t tpl_len = h->tpl_rows - 1;
+    if (int rc = l->cols.reserve((size_t)l->m.C * h->K * tpl_len)) return rc;
+    l->K = h->K;
+    l->tpl_len = tpl_len;
+    l->layout_serial = h->store_serial;
+    return SR_OK;
+}
+
+int plan_push(const sr_onepass_live *l, const uint32_t *n, uint32_t n_all, OnePassLivePlan *pl)
+{
+    const sr_engine *h = l->h;
+    std::string why;
+    if (!onepass_live_plan(l->om, h->store_serial, onepass_reach(h->tpl_len_host.data(), h->K), block_hook(), l->word_cost, n, n_all, pl, &why))
+        return fail(SR_ERR_BAD_ARG, why);
+    return SR_OK;
+}
+
+int check_out(const sr_onepass_live *l, uint32_t n_out, uint32_t max_rows, const sr_chain_rec *rec, const sr_chain_word *words,
+              const sr_chain_live_row *rows)
+{
+    if (int rc = check_outputs(l, n_out, max_rows, rec, words, nullptr, rows, false)) return rc;
+    return n_out ? check_store(l) : SR_OK;
+}
+
+OnePassLiveArgs live_args(const sr_onepass_live *l, const int16_t *d_mfcc, uint64_t row_stride, uint32_t block, sr_chain_rec *d_rec,
+                          sr_chain_word *d_words)
+{
+    const sr_engine *h = l->h;
+    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    return OnePassLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->m.C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, l->K, h->tpl_stride, l->tpl_len,
+                           l->m.utt_frames + 1u, block, l->max_words, l->tail, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p, l->hist.p,
+                           t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec, d_words};
+}
+
+// the blocks over the new frames of every channel and the trace of every emitting one, enqueued on s (PCM: samples, but no
+// new frame, is no block: the parse so far again)
+int launch_push(sr_onepass_live *l, const OnePassLivePlan &pl, const int16_t *d_mfcc, uint64_t row_stride, sr_chain_rec *d_rec,
+                sr_chain_word *d_words, hipStream_t s)
+{
+    if (!pl.d.rows) return SR_OK;
+    launch_onepass_live(live_args(l, d_mfcc, row_stride, pl.block, d_rec, d_words), pl.n_blocks, s);
+    HIP_TRY(hipGetLastError());
+    return SR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sr_onepass_live_geometry(uint32_t tpl_rows, uint32_t K, uint32_t min_tpl_frames, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[4])
+{
+    if (!out || !tpl_rows || tpl_rows > 16383 || !K || K > kChainMaxSlots || !min_tpl_frames || min_tpl_frames > tpl_rows || !utt_frames ||
+        utt_frames > kOnePassLiveMaxFrames || !chunk_max || chunk_max > utt_frames)
+        return fail(SR_ERR_BAD_ARG, "null / zero argument, or one outside its range");
+    const LdsBudget mi355x;  // no device: MI355X's figures
+    const uint32_t L = min_tpl_frames / 2u + 1u;
+    out[0] = onepass_live_state_bytes(tpl_rows, K, utt_frames);
+    out[1] = spot_max_tpl(mi355x);
+    out[2] = L;
+    out[3] = onepass_live_launches(chunk_max, onepass_live_block(L, block_hook(), chunk_max));
+    return SR_OK;
+}
+
+int sr_onepass_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames, uint32_t words_cap, uint32_t flags,
+                         uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid, sr_onepass_live **out)
+{
+    if (!h || !out) return fail(SR_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (int rc = check_chain(h, 1, 0, skip_cost, word_cost)) return rc;
+    if (!words_cap) return fail(SR_ERR_BAD_ARG, "words_cap must be at least 1");
+    if (flags & ~SR_OP_LIVE_TAIL) return fail(SR_ERR_BAD_ARG, "unknown flag");
+    if (!n_channels || n_channels > kOnePassLiveMaxChannels || !utt_frames || utt_frames > kOnePassLiveMaxFrames)
+        return fail(SR_ERR_BAD_ARG, "n_channels not in 1..65535 / utt_frames not in 1..16383");
+    if (!onepass_cost_ok(utt_frames, onepass_reach(h->tpl_len_host.data(), h->K), word_cost))
+        return fail(SR_ERR_BAD_ARG, "(utt_frames / L) * word_cost must be at most 2^30, L = the shortest valid template's frames / 2 + 1");
+    if (!chunk_max) return fail(SR_ERR_BAD_ARG, "chunk_max 0");
+    if (mid) {
+        if (((uint64_t)chunk_max + h->hop - 1) / h->hop > std::min(h->cfg.max_frames, utt_frames))
+            return fail(SR_ERR_BAD_ARG, "a push of chunk_max samples could complete more than min(max_frames, utt_frames) frames");
+        for (uint32_t c = 0; c < n_channels; c++)
+            if (mid[c] > 0xFFFFu) return fail(SR_ERR_BAD_ARG, "mid exceeds the u16 sample range");
+        if (int rc = check_batch(h, n_channels)) return rc;
+    } else if (chunk_max > utt_frames) {
+        return fail(SR_ERR_BAD_ARG, "chunk_max not in 1..utt_frames");
+    }
+    ENTER_DEVICE(h);
+    sr_onepass_live *l = new sr_onepass_live();
+    l->h = h;
+    l->om.open(n_channels, h->store_serial);
+    l->m.chunk_max = chunk_max;
+    l->m.utt_frames = utt_frames;
+    l->m.pcm = mid != nullptr;
+    l->m.frame_len = h->frame_len;
+    l->m.hop = h->hop;
+    l->max_words = words_cap;
+    l->tail = flags & SR_OP_LIVE_TAIL;
+    l->skip_cost = skip_cost;
+    l->word_cost = word_cost;
+    const size_t P = (size_t)utt_frames + 1;
+    int rc = relayout(l);
+    if (!rc) rc = l->A.reserve((size_t)n_channels * P);
+    if (!rc) rc = l->E.reserve((size_t)n_channels * P);
+    if (!rc) rc = l->hist.reserve((size_t)n_channels * utt_frames * kCoef);
+    if (!rc) rc = l->d_chan.reserve(n_channels);
+    if (!rc && mid) {
+        l->mid.assign(mid, mid + n_channels);
+        l->keep_stride = live_pcm_keep_stride(h);
+        l->stage_stride = live_pcm_stage_stride(h, chunk_max);
+        rc = l->keep.reserve((size_t)n_channels * l->keep_stride);
+        if (!rc) rc = l->stage.reserve((size_t)n_channels * l->stage_stride);
+        if (!rc) rc = l->recs.reserve(n_channels);
+        if (!rc) rc = l->feat.reserve(h->mfcc_elems(n_channels));
+    }
+    // no word yet anywhere, E(0) = 0: the state of an empty channel, which a push finds without a launch of its own (every other
+    // position of E is written before it is read)
+    if (!rc && (hipMemsetAsync(l->A.p, 0xFF, (size_t)n_channels * P * 8, nullptr) != hipSuccess ||
+                hipMemsetAsync(l->E.p, 0, (size_t)n_channels * P * 4, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
+        rc = fail(SR_ERR_HIP, "clearing the session's history failed");
+    if (!rc && hipEventCreateWithFlags(&l->ev_last, hipEventDisableTiming) != hipSuccess) rc = fail(SR_ERR_HIP, "hipEventCreate failed");
+    if (rc) {
+        (void)hipGetLastError();
+        sr_onepass_live_close(l);
+        return rc;
+    }
+    *out = l;
+    return SR_OK;
+}
+
+void sr_onepass_live_close(sr_onepass_live *l)
+{
+    if (!l) return;
+    DeviceGuard guard;
+    (void)guard.enter(l->h->device);
+    if (l->pending) (void)hipEventSynchronize(l->ev_last);
+    l->cols.release();
+    l->A.release();
+    l->E.release();
+    l->hist.release();
+    l->d_chan.release();
+    l->keep.release();
+    l->stage.release();
+    l->recs.release();
+    l->feat.release();
+    if (l->ev_last) (void)hipEventDestroy(l->ev_last);
+    delete l;
+}
+
+int sr_onepass_live_push_dev(sr_onepass_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                             sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows, uint32_t *n_rows, void *stream)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    OnePassLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_frames_in(l, pl.d, d_mfcc, row_stride, true);
+    if (!rc) rc = check_out(l, pl.d.rows, max_rows, d_rec, d_words, rows);
+    if (rc) return rc;
+    ENTER_DEVICE(l->h);
+    const hipStream_t s = (hipStream_t)stream;
+    if (pl.d.rows) {
+        if ((rc = order_after_last_push(l, s))) return rc;
+        if ((rc = upload_chan(l, pl.d.chan, s))) return rc;
+        if ((rc = launch_push(l, pl, d_mfcc, row_stride, d_rec, d_words, s))) return rc;
+    }
+    onepass_live_advance(l->om, pl, rows, n_rows);
+    return pl.d.rows ? mark_push(l, s) : SR_OK;
+}
+
+int sr_onepass_live_push(sr_onepass_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                         sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    OnePassLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_frames_in(l, pl.d, mfcc, row_stride, false);
+    if (!rc) rc = check_out(l, pl.d.rows, max_rows, rec, words, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_HOST_CALL(h);
+    HostOutputs o;
+    if (pl.d.rows) {
+        const size_t ds = (size_t)pl.d.max_frames * kCoef;  // device rows hold the largest count
+        if ((rc = h->s_mfcc.reserve((size_t)l->m.C * ds))) return rc;
+        if ((rc = o.reserve(pl.d.rows, l->max_words, false))) return rc;
+        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
+            if (pl.d.chan[c].n) COPY_UP(h->s_mfcc.p + c * ds, mfcc + (size_t)c * row_stride, (size_t)pl.d.chan[c].n * kCoef * 2);
+        if ((rc = order_after_last_push(l, nullptr))) return rc;
+        if ((rc = upload_chan(l, pl.d.chan, nullptr))) return rc;
+        if ((rc = launch_push(l, pl, h->s_mfcc.p, ds, o.rec.p, o.words.p, nullptr))) return rc;
+    }
+    onepass_live_advance(l->om, pl, rows, n_rows);
+    if (pl.d.rows && (rc = mark_push(l, nullptr))) return rc;
+    return pl.d.rows ? o.down(pl.d.rows, l->max_words, rec, words, nullptr) : SR_OK;
+}
+
+int sr_onepass_live_push_pcm_dev(sr_onepass_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                                 uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows, uint32_t *n_rows,
+                                 void *stream)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    OnePassLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_pcm_in(l, pl.d, d_pcm, pcm_stride, true);
+    if (!rc) rc = check_out(l, pl.d.rows, max_rows, d_rec, d_words, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_DEVICE(h);
+    const hipStream_t s = (hipStream_t)stream;
+    if (pl.d.rows) {
+        if ((rc = order_after_last_push(l, s))) return rc;
+        if ((rc = upload_chan(l, pl.d.chan, s))) return rc;
+        if ((rc = launch_front_end(l, pl.d, d_pcm, pcm_stride, s))) return rc;
+        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, d_rec, d_words, s))) return rc;
+    }
+    onepass_live_advance(l->om, pl, rows, n_rows);
+    return pl.d.rows ? mark_push(l, s) : SR_OK;
+}
+
+int sr_onepass_live_push_pcm(sr_onepass_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+                             sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    OnePassLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_pcm_in(l, pl.d, pcm, pcm_stride, false);
+    if (!rc) rc = check_out(l, pl.d.rows, max_rows, rec, words, rows);
+    if (rc) return rc;
+    sr_engine *h = l->h;
+    ENTER_HOST_CALL(h);
+    HostOutputs o;
+    if (pl.d.rows) {
+        const uint64_t ds = dev_pitch(pl.d.max_n);
+        if ((rc = h->s_pcm.reserve((size_t)l->m.C * ds))) return rc;
+        if ((rc = o.reserve(pl.d.rows, l->max_words, false))) return rc;
+        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
+            if (pl.d.chan[c].n_samp) COPY_UP(h->s_pcm.p + c * ds, pcm + (size_t)c * pcm_stride, (size_t)pl.d.chan[c].n_samp * 2);
+        if ((rc = order_after_last_push(l, nullptr))) return rc;
+        if ((rc = upload_chan(l, pl.d.chan, nullptr))) return rc;
+        if ((rc = launch_front_end(l, pl.d, h->s_pcm.p, ds, nullptr))) return rc;
+        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, o.rec.p, o.words.p, nullptr))) return rc;
+    }
+    onepass_live_advance(l->om, pl, rows, n_rows);
+    if (pl.d.rows && (rc = mark_push(l, nullptr))) return rc;
+    return pl.d.rows ? o.down(pl.d.rows, l->max_words, rec, words, nullptr) : SR_OK;
+}
+
+int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
+                        sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l || (n_ch && !channels)) return fail(SR_ERR_BAD_ARG, "null argument");
+    sr_engine *h = l->h;
+    std::vector<SpotLiveChan> chan;
+    std::vector<sr_chain_live_row> order;
+    std::string why;
+    if (!onepass_live_end_list(l->om, h->store_serial, channels, n_ch, &chan, &order, &why)) return fail(SR_ERR_BAD_ARG, why);
+    const uint32_t n_out = (uint32_t)order.size();
+    if (int rc = check_out(l, n_out, n_out, rec, words, rows)) return rc;
+    if (int rc = check_end_rows(l, n_out, rec, words, nullptr, rows)) return rc;
+    if (!n_out) {
+        if (n_rows) *n_rows = 0;
+        return SR_OK;
+    }
+    ENTER_HOST_CALL(h);
+    if (l->pending) {
+        HIP_TRY(hipEventSynchronize(l->ev_last));
+        l->pending = false;
+    }
+    HostOutputs o;
+    if (int rc = o.reserve(n_out, l->max_words, false)) return rc;
+    // Every channel that still holds state is bound to a store that is gone, and the trace reads no column: the columns are
+    // laid out again BEFORE anything is written, so that a failed allocation leaves outputs, mirror and layout as they were.
+    if (l->layout_serial != h->store_serial)
+        if (int rc = relayout(l)) return rc;
+    if (int rc = upload_chan(l, chan, nullptr)) return rc;
+    launch_onepass_live_end(live_args(l, nullptr, 0, 1u, o.rec.p, o.words.p), nullptr);
+    HIP_TRY(hipGetLastError());
+    if (int rc = o.down(n_out, l->max_words, rec, words, nullptr)) return rc;
+    onepass_live_reset(l->om, h->store_serial, order);
+    for (uint32_t r = 0; r < n_out; r++) rows[r] = order[r];
+    if (n_rows) *n_rows = n_out;
+    return SR_OK;
+}
+
+}  // extern "C"

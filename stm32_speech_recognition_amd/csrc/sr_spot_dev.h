@@ -88,4 +88,24 @@ __device__ __forceinline__ void chain_trace_row(const unsigned long long *A1, co
     if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, SR_CH_OK};
 }
 
+// The one-pass decoders' step of the trace (k_onepass.hip, k_onepass_live.hip), one wave per row: the first position q in
+// [1, p] from above whose own word closes E there (A(q) reachable and A(q).cost == E(q)), 64 positions per step; returns q and
+// its key, or 0: the rest of the row is filler
+__device__ __forceinline__ uint32_t onepass_word_at(const unsigned long long *A, const uint32_t *E, uint32_t p, uint32_t lane, uint64_t *key)
+{
+    while (p >= 1) {  // (uniform)
+        const bool mine = lane < p;  // position p - lane >= 1
+        const uint64_t ky = mine ? A[p - lane] : kSpotInf;
+        const uint32_t e = mine ? E[p - lane] : kChainNone;
+        const unsigned long long hit = __ballot(mine && ky != kSpotInf && (uint32_t)(ky >> 32) == e);
+        if (hit) {
+            const uint32_t first = (uint32_t)__ffsll((long long)hit) - 1u;
+            *key = spot_shfl(ky, first);
+            return p - first;
+        }
+        p = p > 64u ? p - 64u : 0u;
+    }
+    return 0u;
+}
+
 }  // namespace sr

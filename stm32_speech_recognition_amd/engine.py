@@ -48,6 +48,7 @@ CHAIN_WORD_DTYPE = np.dtype([("word", "<u4"), ("slot", "<u4"), ("start", "<u4"),
                              ("cum", "<u4"), ("reserved", "<u4")])
 CH_OK, CH_NONE = 0, 1
 CH_TRUNCATED = 2  # sr_decode_onepass_*: more words than words_cap, the first words_cap are written
+OP_LIVE_TAIL = 1  # sr_onepass_live_open flag: the last words_cap words instead
 # sr_vad_debug_masks: 16 words per capture, 63 frames (one round of the VAD kernel) per 64-bit word
 VAD_MASK_WORDS, VAD_MASK_FRAMES = 16, 63
 # sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
@@ -866,6 +867,11 @@ class Engine:
         """sr_gram_live_open: a GrammarSession -- decode_live() under a Grammar, which sess.set_grammar() switches between
         recordings.  Close the session before the grammar."""
         return GrammarSession(self, gram, n_channels, chunk_max, utt_frames, max_words, n_words, skip_cost, word_cost, mid)
+
+    def decode_onepass_live(self, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0, mid=None):
+        """sr_onepass_live_open: an OnePassSession -- decode_onepass() push by push, no word cap.  tail: a row holds the LAST
+        words_cap words of the parse (OP_LIVE_TAIL) instead of the first.  mid as for decode_live."""
+        return OnePassSession(self, n_channels, chunk_max, utt_frames, words_cap, tail, skip_cost, word_cost, mid)
 
     # ---- full-DP alignment and word models from many examples -----------------------------------------
     def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
@@ -1975,6 +1981,85 @@ class DecodeSession:
         self.eng._check(self._fn("end")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(lc), _vp(rows), C.byref(n)))
         self._frames[rows[:n.value]["channel"]] = 0
         return dict(rec=rec[:n.value], words=words[:n.value], level_cost=lc[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+
+def onepass_live_geometry(tpl_rows, K, min_tpl_frames, utt_frames, chunk_max, testing=False):
+    """Host-only sr_onepass_live_geometry: dict(state_bytes on the device per channel, max_tpl_rows that fit, block = L, launches
+    a feature push of chunk_max frames enqueues at most).  testing: the testing library, whose "onepass_block" hook caps the
+    blocks."""
+    L = load_library(testing)
+    out = (C.c_uint32 * 4)()
+    rc = L.sr_onepass_live_geometry(C.c_uint32(tpl_rows), C.c_uint32(K), C.c_uint32(min_tpl_frames), C.c_uint32(utt_frames),
+                                    C.c_uint32(chunk_max), out)
+    if rc != 0:
+        raise SrError(f"sr_onepass_live_geometry error {rc}: {L.sr_last_error().decode()}")
+    return dict(state_bytes=out[0], max_tpl_rows=out[1], block=out[2], launches=out[3])
+
+
+class OnePassSession(DecodeSession):
+    """One sr_onepass_live handle (Engine.decode_onepass_live): one-pass connected-word decoding over chunked features or
+    samples, no word cap.  After every push the row of a channel is Engine.decode_onepass on everything pushed to it as one row
+    (include/sr_engine.h, "live one-pass connected-word decoding").  push, push_dev, push_pcm, push_pcm_dev, frames and close
+    are DecodeSession's; the rows carry no level costs: dict(rec, words [n_rows, words_cap], rows, n_rows)."""
+
+    _PREFIX = "sr_onepass_live_"
+
+    def __init__(self, eng, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0, mid=None):
+        self.eng, self.L, self.n_channels, self.chunk_max, self.utt_frames = eng, eng.L, n_channels, chunk_max, utt_frames
+        self.max_words = self.words_cap = words_cap
+        self._fn("close").restype = None
+        self._fn("close").argtypes = [C.c_void_p]
+        md = None if mid is None else np.ascontiguousarray(mid, dtype=np.uint32)
+        assert md is None or md.shape == (n_channels,)
+        self.pcm = md is not None
+        self._frames = np.zeros(n_channels, np.uint32)
+        l = C.c_void_p()
+        eng._check(self._fn("open")(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames), C.c_uint32(words_cap),
+                                    C.c_uint32(OP_LIVE_TAIL if tail else 0), C.c_uint32(Engine._skip(skip_cost)), C.c_uint32(word_cost),
+                                    _vp(md), C.byref(l)))
+        self.l = l
+
+    def _push_host(self, fn, data, stride, width, counts, max_rows):
+        ct, n_all, emit = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = emit
+        rec, words = np.zeros(max_rows, dtype=CHAIN_REC_DTYPE), np.zeros((max_rows, self.words_cap), dtype=CHAIN_WORD_DTYPE)
+        rows, n = np.zeros(max_rows, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(rec), _vp(words),
+                           _vp(rows), C.byref(n)))
+        self._took(rows[:n.value])
+        return dict(rec=rec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+    def _push_dev(self, fn, data, stride, width, counts, max_rows, level_cost, stream):
+        import torch
+        ct, n_all, emit = self._counts(counts, width)
+        if max_rows is None:
+            max_rows = emit
+        W, dev = self.words_cap, data.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        cap = max(max_rows, 1)
+        rec = torch.empty(cap, 4, dtype=torch.int32, device=dev)[:max_rows]
+        words = torch.empty(cap, W, 8, dtype=torch.int32, device=dev)[:max_rows]
+        rows, n = np.zeros(max_rows, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(fn(self.l, _vp(data), C.c_uint64(stride), _vp(ct), C.c_uint32(n_all), C.c_uint32(max_rows), _vp(rec), _vp(words),
+                           _vp(rows), C.byref(n), C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            for t in (data, rec, words):
+                t.record_stream(stream)  # allocated on the current stream, used on `stream`
+        self._took(rows[:n.value])
+        return dict(rec=rec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+    def end(self, channels):
+        """sr_onepass_live_end: the listed channels' recordings end here.  Returns dict(rec, words, rows, n_rows) as push: one
+        row per distinct listed channel, the parse of everything pushed to it; afterwards the channels are as freshly opened."""
+        ch = np.ascontiguousarray(np.atleast_1d(channels), dtype=np.uint32)
+        cap = max(len(ch), 1)
+        rec, words = np.zeros(cap, dtype=CHAIN_REC_DTYPE), np.zeros((cap, self.words_cap), dtype=CHAIN_WORD_DTYPE)
+        rows, n = np.zeros(cap, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(self._fn("end")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(rows), C.byref(n)))
+        self._frames[rows[:n.value]["channel"]] = 0
+        return dict(rec=rec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
 
 
 def grammar_live_geometry(gram, max_words, utt_frames, chunk_max):
