@@ -1346,6 +1346,75 @@ int sr_onepass_live_push_pcm(sr_onepass_live *l, const uint16_t *pcm, uint64_t p
 int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
                         sr_chain_live_row *rows, uint32_t *n_rows);
 
+/* ------------------------------------------------------------------ one-pass grammar decoding: word networks without a word cap
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  Grammar decoding (the grammar-constrained decoding and weighted grammars
+ * sections) is level building: at most 16 words a row, max_words sweeps of every row.  A grammar with a loop -- "a command,
+ * then any number of digits", a bigram model, a phone-number network -- describes sequences whose length the caller does not
+ * know.  This section runs the one-pass recurrence over the states of a grammar: a row holds as many words as its frames
+ * allow, and a call pays 2 x (kept items) x M x N cells whatever that number is.  No existing call, record or byte changes.
+ * Everything not restated here is the one-pass section's: d, the word path, skip_cost, word_cost, the key (cost, start,
+ * slot), sr_chain_rec, sr_chain_word, SR_CH_TRUNCATED.  Grammar notation is the weighted grammar's: states 0..S-1, state 0
+ * the start, the charge list of a pair (t, w), final_cost.  The calls take an sr_grammar as sr_grammar_create[_weighted]
+ * made it.
+ *   E(0, 0)   0; E(0, s) unreachable for s != 0.
+ *   charge    C(x; t, w) = the minimum over the (s, c) of the list of (t, w) with E(x, s) reachable of E(x, s) + c; else
+ *             unreachable.  An unreachable E never has a cost added to it.
+ *   D_k,t     per item (slot k, target t), k a valid slot of a word w with a pair (t, w): the spotter's recurrence with a
+ *             charged start, D(x, 0) = C(x; t, w) + d(x, 0), S = x.
+ *   A(p, t)   p >= 1: the minimum over the items into t of (D_k,t(p-1, M_k-1) + word_cost, S, k), compared as (cost, start,
+ *             slot).
+ *   E(p, t)   min(A(p, t).cost, E(p-1, t) + skip_cost), the second term only when skipping is on.
+ *   result    over the final f with E(N, f) reachable: cost = min E(N, f) + final_cost[f], the end state the smallest such f.
+ *             None, or N = 0: status SR_CH_NONE with the decoder's NONE record.
+ *   trace     p = N, t = the end state; while p > 0: if A(p, t) is unreachable or A(p, t).cost != E(p, t), frame p-1 is
+ *             skipped and p -= 1; else the word is A(p, t): end = p-1, cum = E(p, t), acc = A(p, t).cost - word_cost -
+ *             C(start; t, w(k)), reserved = t; the source state is the smallest s of the list with E(start, s) reachable and
+ *             E(start, s) + c = C(start; t, w(k)); p = start, t = s.
+ *   output    as the one-pass section's, with the grammar state after each word in `reserved`.
+ * Consequences:
+ *   - n_words 0 with SR_CH_OK is possible only when state 0 is final and filler is cheaper than every accepted sequence.
+ *   - The walk always ends in state 0: only E(0, 0) is reachable at position 0.
+ *   - Under the anchor grammar (one final state, one loop per label) record and word rows are sr_decode_onepass_dp's bytes;
+ *     reserved is 0 there, the anchor's only state.
+ *   - Where the minimum over sr_decode_grammar_dp's level costs is unique and has at most 16 words, the word rows equal that
+ *     decoder's at max_words 16.  When state 0 is final and skipping is on that minimum also includes N x skip_cost +
+ *     final_cost[0].  Under ties the two decoders may choose differently.
+ *   blocks    the one-pass section's argument, state by state: a word over M template frames spans at least M / 2 + 1 input
+ *             frames whatever state it leads into, so A(p, t) depends on E(x, s) for x <= p - L only.  The call runs as
+ *             ceil(frames_cap / L) blocks ordered by the stream alone.
+ *   pruning   static, not per level.  An item (slot, target) is kept when its charge list contains a state reachable from
+ *             state 0 in any number of arcs and its target reaches a final state.  The states whose E is kept are every state
+ *             that a kept charge list names and every final state that can be reached -- states without an incoming arc too:
+ *             with skipping on E(p, 0) = p x skip_cost of a sequence grammar's start state is what its first words build on.
+ *             Pruning changes no byte.
+ *   limits    the one-pass section's, with one arc per word and one final cost added: (frames_cap / L) x (word_cost + the
+ *             grammar's largest arc cost) + its largest final cost <= 2^30, refused with SR_ERR_BAD_ARG otherwise; and one
+ *             row's scratch -- S x (max_frames + 1) keys and prefix costs and one saved column per kept item -- within the
+ *             256 MiB of a launch group.
+ * Out of scope: the push-by-push session, n_words_exact, N-best sequences, word alternatives under this decoder
+ * (sr_score_word_spans takes its word rows), grammars of more than 64 states, recordings past 16 383 frames. */
+/* Stage level, DEVICE buffers: sr_decode_onepass_dp_dev's arguments and rules with the grammar in front.  ONE asynchronous
+ * operation on `stream`, no host synchronisation, no read-back; two runs give the same bytes.  Errors, before anything is
+ * launched or written: sr_decode_onepass_dp_dev's, and SR_ERR_BAD_ARG for a null grammar, a grammar of another engine, a
+ * grammar compiled before the last sr_set_templates* or sr_set_word_map, the cost bound above, a row whose scratch exceeds a
+ * launch group (the message names row_bytes). */
+int sr_decode_onepass_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d_mfcc, const uint32_t *d_in_frames,
+                                     uint32_t frames_stride, uint32_t n_rows, uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost,
+                                     uint32_t word_cost, sr_chain_rec *d_rec, sr_chain_word *d_words, void *stream);
+/* the same on HOST buffers (copy in, launch, copy out) */
+int sr_decode_onepass_grammar_dp(sr_engine *h, const sr_grammar *g, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride,
+                                 uint32_t n_rows, uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost,
+                                 sr_chain_rec *rec, sr_chain_word *words);
+/* Whole path on HOST buffers: sr_decode_onepass_batch under the grammar. */
+int sr_decode_onepass_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                                    const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t words_cap, uint32_t skip_cost,
+                                    uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, int16_t *mfcc, uint32_t *frm_num,
+                                    uint32_t *status);
+/* Host-only: what a call with this grammar and frames_cap (0 = max_frames) takes.  out[0] = scratch bytes per row, saturating;
+ * out[1] = rows per launch group (0: one row does not fit, the call is refused); out[2] = the block length L; out[3] =
+ * launches per group, 2 x ceil(frames_cap / L) + 2; out[4] = kept items; out[5] = kept states. */
+int sr_onepass_grammar_plan(const sr_grammar *g, uint32_t frames_cap, uint32_t out[6]);
+
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
  *   delta[t][c] = ((m[t+1][c] - m[t-1][c]) + 2*(m[t+2][c] - m[t-2][c])) / 10,
@@ -1468,7 +1537,10 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    sr_onepass_live_geometry reads it likewise
  *   "onepass_rows"                   rows per launch group of the one-pass decoder (default: what 256 MiB of scratch hold);
  *                                    read per call and by sr_decode_onepass_geometry
- *   "live_origin"                    samples (an int64 multiple of the hop) a fresh sr_live channel behaves as having consumed
+ *   "onepass_gram_prune_off"         one-pass grammar decoding keeps every item and every state (no static pruning; the same
+ *                                    bytes come out); read per call and by sr_onepass_grammar_plan.  The calls also read
+ *                                    "onepass_block" and "onepass_rows" as the one-pass decoder does
+ *   "live_origin"                   samples (an int64 multiple of the hop) a fresh sr_live channel behaves as having consumed
  *                                    before: received = the value, next frame = value / hop, in the device state and the host
  *                                    mirror; nothing in the push path knows of it.  Read where a channel is made fresh
  *                                    (sr_live_open, sr_live_end), which return SR_ERR_BAD_ARG and change nothing when the value

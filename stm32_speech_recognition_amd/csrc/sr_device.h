@@ -37,6 +37,7 @@ enum DevHook {
     kHookForcedPruneOff,  // "forced_prune_off": the forced aligner sweeps every end frame of every level (no column bound; read per call)
     kHookOnePassBlock,    // "onepass_block": frames per block of the one-pass decoder, clamped to 1..L (read per call and push, and by the two one-pass geometry calls)
     kHookOnePassRows,     // "onepass_rows": rows per launch group of the one-pass decoder (read per call and by sr_decode_onepass_geometry)
+    kHookOnePassGramPruneOff,  // "onepass_gram_prune_off": one-pass grammar decoding keeps every item and every state (no static pruning; read per call and by sr_onepass_grammar_plan)
     kHookLiveOrigin,      // "live_origin": samples a fresh sr_live channel behaves as having consumed before (a multiple of hop; read at open / end)
     kHookSpotLiveOrigin,  // "spot_live_origin": frames a fresh sr_spot_live channel stands at (up to 0xFFFF0000; read at open / end)
     kHookCount
@@ -594,6 +595,23 @@ struct GramLiveArgs {
 // w null: the unweighted kernels, otherwise the weighted sweep and trace
 void launch_gram_live(const GramLiveArgs &a, const GramCosts *w, hipStream_t s);        // init, per level with items (words, close), trace
 void launch_gram_live_trace(const GramLiveArgs &a, const GramCosts *w, hipStream_t s);  // the trace alone (no new frame, sr_gram_live_end)
+
+// one-pass grammar decoding (k_onepass_gram.hip): k_onepass.hip's blocks over the states of a grammar.  o is the one-pass
+// decoder's argument block with the scratch in the grammar's layout: o.A[row][state][max_frames + 1], o.E[row][state][max_frames
+// + 1] and o.cols[row][kept item][tpl_len]; o.K is not read.  keep_items / keep_states are the host's static lists, ascending
+// (sr_onepass_gram_plan.h); a null list is the identity: everything is kept.
+struct OnePassGramArgs {
+    OnePassArgs o;
+    uint32_t n_states, n_items;
+    uint32_t n_keep_items, n_keep_states;
+    const unsigned long long *masks;  // [n_sets]: the states of each charge list
+    const GramItem *items;            // [n_items], ascending (slot, target)
+    const uint8_t *final_state;       // [n_states]
+    const uint32_t *keep_items;       // [n_keep_items] indices into items, or null
+    const uint32_t *keep_states;      // [n_keep_states] states, or null
+};
+// init, per block of the host's list (sweep, close), trace; w null: the unweighted kernels, otherwise the weighted sweep and trace
+void launch_onepass_gram(const OnePassGramArgs &a, const GramCosts *w, const OnePassBlock *blocks, uint32_t n_blocks, hipStream_t s);
 
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the

@@ -170,6 +170,7 @@ const char *cluster_allow_lds(uint32_t bytes);
 const char *forced_allow_lds(uint32_t bytes);
 const char *onepass_allow_lds(uint32_t bytes);
 const char *onepass_live_allow_lds(uint32_t bytes);
+const char *onepass_gram_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

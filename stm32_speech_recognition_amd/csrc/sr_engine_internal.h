@@ -329,6 +329,11 @@ struct sr_grammar {
     size_t items_at = 0, lists_at = 0, final_at = 0;  // offsets in u64 units
     bool weighted = false;
     size_t cost_off_at = 0, costs_at = 0, final_cost_at = 0;  // offsets in u64 units (weighted only)
+    // behind all of that, for one-pass grammar decoding (sr_onepass_gram.cpp; sr_onepass_gram_plan.h builds them at create):
+    // kept items u32 [op_n_items] (indices into items) | kept states u32 [op_n_states], both ascending
+    size_t op_items_at = 0, op_states_at = 0;  // offsets in u64 units
+    uint32_t op_n_items = 0, op_n_states = 0;
+    uint32_t max_arc_cost = 0, max_final_cost = 0;  // the largest of each: the decoder's cost bound
     GramCosts costs() const  // the weighted kernels' second argument
     {
         return GramCosts{(const uint32_t *)(blob.p + cost_off_at), (const uint32_t *)(blob.p + costs_at), (const uint32_t *)(blob.p + final_cost_at)};
@@ -338,3 +343,6 @@ struct sr_grammar {
 int check_grammar(const sr_engine *h, const sr_grammar *g);
 // what level l (1-based) of a call with max_words keeps
 GramLevel gram_level_of(const sr_grammar *g, uint32_t l, uint32_t max_words);
+// ---- one-pass grammar decoding (sr_onepass_gram.cpp) --------------------------------------------------------------------------
+// the conditions of sr_decode_onepass_grammar_dp_dev on the engine, the store, the grammar and the parameters (not on the buffers)
+int check_onepass_grammar(const sr_engine *h, const sr_grammar *g, uint32_t frames_cap, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost);

@@ -6,6 +6,7 @@
 // host form is in sr_host.cpp, next to sr_decode_words_batch.
 #include "sr_gram_compile.h"
 #include "sr_host_call.h"
+#include "sr_onepass_gram_plan.h"
 
 using namespace sr;
 
@@ -102,7 +103,18 @@ int sr_grammar_create_weighted(sr_engine *h, uint32_t n_states, const sr_gram_ar
         g->final_cost_at = g->costs_at + (c.costs.size() + 1) / 2;
         end = g->final_cost_at + (S + 1) / 2;
     }
+    // one-pass grammar decoding (sr_onepass_gram.cpp): its static lists, built once, behind everything the level decoders read
+    const OnePassGramKeep keep = onepass_gram_keep(S, arcs, n_arcs, net.finals, c.items.data(), g->n_items, c.masks.data(), true);
+    g->op_n_items = (uint32_t)keep.items.size();
+    g->op_n_states = (uint32_t)keep.states.size();
+    g->op_items_at = end;
+    g->op_states_at = g->op_items_at + (keep.items.size() + 1) / 2;
+    end = g->op_states_at + (keep.states.size() + 1) / 2;
+    for (uint32_t i = 0; i < n_arcs; i++) g->max_arc_cost = std::max(g->max_arc_cost, arc_cost ? arc_cost[i] : 0u);
+    for (uint32_t s = 0; s < S; s++) g->max_final_cost = std::max(g->max_final_cost, net.final_cost[s]);
     std::vector<unsigned long long> blob(end, 0ull);
+    if (!keep.items.empty()) std::memcpy(blob.data() + g->op_items_at, keep.items.data(), keep.items.size() * 4);
+    if (!keep.states.empty()) std::memcpy(blob.data() + g->op_states_at, keep.states.data(), keep.states.size() * 4);
     std::memcpy(blob.data(), c.masks.data(), c.masks.size() * 8);
     if (!c.items.empty()) std::memcpy(blob.data() + g->items_at, c.items.data(), c.items.size() * sizeof(GramItem));
     if (!c.lists.empty()) std::memcpy(blob.data() + g->lists_at, c.lists.data(), c.lists.size() * 4);

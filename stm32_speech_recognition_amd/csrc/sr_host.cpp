@@ -391,6 +391,36 @@ int sr_decode_onepass_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stri
     return SR_OK;
 }
 
+// One-pass grammar decoding, whole path (sr_onepass_gram.cpp has the stage): sr_decode_onepass_batch under a grammar
+int sr_decode_onepass_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
+                                    const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t words_cap, uint32_t skip_cost,
+                                    uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, int16_t *mfcc, uint32_t *frm_num, uint32_t *status)
+{
+    if (!h || !pcm || !start || !end || !mid || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (int rc_chk = check_onepass_grammar(h, g, 0u, words_cap, skip_cost, word_cost)) return rc_chk;
+    if (B == 0) return SR_OK;
+    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
+    ENTER_HOST_CALL(h);
+    std::vector<sr_vad_rec> recs;
+    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
+    if (rc) return rc;
+    const size_t n_mfcc = h->mfcc_elems(B), n_w = (size_t)B * words_cap;
+    TmpDevBuf<sr_chain_rec> d_rec;
+    TmpDevBuf<sr_chain_word> d_words;
+    if ((rc = h->s_vad.reserve(B)) || (rc = h->s_mfcc.reserve(n_mfcc)) || (rc = d_rec.reserve(B)) || (rc = d_words.reserve(n_w))) return rc;
+    uint64_t ds = 0;
+    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
+    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
+    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
+    if ((rc = sr_decode_onepass_grammar_dp_dev(h, g, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, 0u, words_cap,
+                                               skip_cost, word_cost, d_rec.p, d_words.p, nullptr)))
+        return rc;
+    COPY_DOWN(rec, d_rec.p, (size_t)B * sizeof *rec);
+    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
+    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
+    return SR_OK;
+}
+
 // the same under a grammar (sr_gram.cpp has the stage)
 int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len,
                             uint32_t B, const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t max_words,

@@ -857,6 +857,52 @@ class Engine:
                                                    _vp(out["status"])))
         return out
 
+    # ---- one-pass grammar decoding ------------------------------------------------------------------------------
+    def decode_onepass_grammar(self, gram, mfcc, frames, words_cap=64, skip_cost=None, word_cost=0, frames_cap=0):
+        """OPT-IN one-pass grammar decoder (sr_decode_onepass_grammar_dp): decode_onepass() under a Grammar, weighted or not --
+        the cheapest parse among the word sequences the grammar accepts, without a word cap.  Arguments and returns as
+        decode_onepass(); the word rows' `reserved` holds the grammar state after each word."""
+        mfcc = np.ascontiguousarray(mfcc, dtype=np.int16)
+        assert mfcc.shape[1:] == (self.max_frames, self.n_coef)
+        frames = np.ascontiguousarray(frames, dtype=np.uint32)
+        n = mfcc.shape[0]
+        assert len(frames) == n
+        rec, words = np.zeros(n, dtype=CHAIN_REC_DTYPE), np.zeros((n, max(words_cap, 1)), dtype=CHAIN_WORD_DTYPE)
+        self._check(self.L.sr_decode_onepass_grammar_dp(self.h, gram.g, _vp(mfcc), _vp(frames), C.c_uint32(1), C.c_uint32(n),
+                                                        C.c_uint32(frames_cap), C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)),
+                                                        C.c_uint32(word_cost), _vp(rec), _vp(words)))
+        return rec, words
+
+    def decode_onepass_grammar_dev(self, gram, mfcc, frames, rec, words, words_cap=64, skip_cost=None, word_cost=0, frames_cap=0,
+                                   frames_stride=1, stream=None):
+        """decode_onepass_dev() under a Grammar (sr_decode_onepass_grammar_dp_dev): the same tensors, asynchronous on `stream`."""
+        import torch
+        assert mfcc.is_cuda and mfcc.is_contiguous() and rec.is_contiguous() and words.is_contiguous()
+        n = mfcc.shape[0]
+        assert rec.numel() == n * 4 and words.numel() == n * words_cap * 8
+        if stream is None:
+            stream = torch.cuda.current_stream(mfcc.device).cuda_stream
+        self._check(self.L.sr_decode_onepass_grammar_dp_dev(self.h, gram.g, _vp(mfcc), _vp(frames), C.c_uint32(frames_stride), C.c_uint32(n),
+                                                            C.c_uint32(frames_cap), C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)),
+                                                            C.c_uint32(word_cost), _vp(rec), _vp(words), C.c_void_p(stream)))
+        return rec, words
+
+    def decode_onepass_grammar_pcm(self, gram, pcm, start, end, mid, words_cap=64, skip_cost=None, word_cost=0):
+        """decode_onepass_pcm() under a Grammar (sr_decode_onepass_grammar_batch): the same dict."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint16)
+        B, S = pcm.shape
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        mid = np.ascontiguousarray(mid, dtype=np.uint32)
+        out = dict(rec=np.zeros(B, dtype=CHAIN_REC_DTYPE), words=np.zeros((B, max(words_cap, 1)), dtype=CHAIN_WORD_DTYPE),
+                   mfcc=np.zeros((B, self.max_frames, self.n_coef), dtype=np.int16), frm_num=np.zeros(B, dtype=np.uint32),
+                   status=np.zeros(B, dtype=np.uint32))
+        self._check(self.L.sr_decode_onepass_grammar_batch(self.h, gram.g, _vp(pcm), C.c_uint64(S), C.c_uint32(S), C.c_uint32(B), _vp(start),
+                                                           _vp(end), _vp(mid), C.c_uint32(words_cap), C.c_uint32(self._skip(skip_cost)),
+                                                           C.c_uint32(word_cost), _vp(out["rec"]), _vp(out["words"]), _vp(out["mfcc"]),
+                                                           _vp(out["frm_num"]), _vp(out["status"])))
+        return out
+
     def decode_live(self, n_channels, chunk_max, utt_frames, max_words=8, n_words=0, skip_cost=None, word_cost=0, mid=None):
         """sr_decode_live_open: a DecodeSession of n_channels channels of at most utt_frames frames each.  mid None: a feature
         session (chunk_max in frames); mid uint32 [n_channels]: a PCM session (chunk_max in samples)."""
@@ -1764,6 +1810,27 @@ def grammar_word_pairs(labels, allowed_pairs, first=None, last=None):
     arcs = [(0, st[w], w) for w in labels if first is None or w in first]
     arcs += [(st[a], st[b], int(b)) for a, b in dict.fromkeys((int(a), int(b)) for a, b in allowed_pairs)]
     return 1 + len(labels), arcs, [0] + [int(last is None or w in last) for w in labels]
+
+
+def grammar_repeat(positions, loop_labels, min_repeat=1):
+    """A sequence followed by a loop -- "one command, then any number of digits": word i of a parse is one of the labels
+    positions[i], then at least min_repeat words of loop_labels follow, as many as were said.  The parse may end after the
+    min_repeat-th looped word and after every one behind it (min_repeat 0: right after the sequence too).  A loop has no
+    length: decode it with Engine.decode_onepass_grammar.  Returns (n_states, arcs, final)."""
+    n, loop = len(positions), list(dict.fromkeys(int(w) for w in loop_labels))
+    arcs = [(i, i + 1, int(w)) for i, ws in enumerate(positions) for w in dict.fromkeys(ws)]
+    arcs += [(n + j, n + j + 1, w) for j in range(min_repeat) for w in loop]
+    last = n + min_repeat
+    arcs += [(last, last, w) for w in loop]
+    return last + 1, arcs, [int(s == last) for s in range(last + 1)]
+
+
+def onepass_grammar_plan(gram, frames_cap=0):
+    """sr_onepass_grammar_plan (host only) for a Grammar: dict(row_bytes, rows, block, launches, kept_items, kept_states); rows 0 =
+    one row exceeds a launch group's scratch and a call is refused."""
+    out = (C.c_uint32 * 6)()
+    gram.eng._check(gram.L.sr_onepass_grammar_plan(gram.g, C.c_uint32(frames_cap), out))
+    return dict(row_bytes=out[0], rows=out[1], block=out[2], launches=out[3], kept_items=out[4], kept_states=out[5])
 
 
 def grammar_bigram(labels, cost, first_cost=None, last_cost=None):
