@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "sr_device.h"
+#include "sr_live_plan.h"
 
 namespace sr {
 
@@ -27,10 +27,7 @@ struct DecodeLiveMirror {
     }
 };
 
-struct DecodeLivePlan {
-    std::vector<SpotLiveChan> chan;                              // ChainLiveArgs::chan, sr_device.h
-    uint32_t rows = 0, max_n = 0, max_frames = 0, max_row = 0;   // emitted rows; the largest count, frame count and [kept | chunk] row
-};
+using DecodeLivePlan = LivePlan;  // chan = ChainLiveArgs::chan; rows = the channels that emit one
 
 // What a push with these counts does, from the counts alone.  Refusals, channel by channel in ascending order and per
 // channel in this order: a count above chunk_max; a channel bound to a replaced store; a channel taken past utt_frames.
@@ -51,15 +48,7 @@ inline bool decode_live_plan(const DecodeLiveMirror &m, uint64_t store_serial, c
             *why = "the template store changed: end channel " + std::to_string(c) + " before pushing to it";
             return false;
         }
-        uint32_t nf = cnt;
-        if (m.pcm) {  // frame j exists once 1 + j * hop + frame_len samples have arrived; the row starts at frame x0's predecessor
-            const uint64_t total = (uint64_t)m.kept[c] + cnt;
-            nf = total >= 1 + (uint64_t)m.frame_len ? (uint32_t)((total - 1 - m.frame_len) / m.hop + 1) : 0;
-            ch.kept = m.kept[c];
-            ch.n_samp = cnt;
-            ch.drop = nf * m.hop;
-            if (cnt) pl->max_row = std::max(pl->max_row, (uint32_t)total);
-        }
+        const uint32_t nf = m.pcm ? live_pcm_frames(m.kept[c], cnt, m.frame_len, m.hop, &ch, &pl->max_row) : cnt;
         if ((uint64_t)m.frames[c] + nf > m.utt_frames) {
             *why = "channel " + std::to_string(c) + " would pass utt_frames: end it first";
             return false;

@@ -1,4 +1,4 @@
-// The front end of the PCM sessions (sr_spot_live.cpp, sr_decode_live.cpp): a channel keeps the samples from its next frame's
+// The front end of the PCM sessions (every live session through LiveCore, sr_live_host.h): a channel keeps the samples from its next frame's
 // pre-emphasis predecessor on; a push stages [kept | chunk] rows (k_spot_live_stage), runs the frame kernel over them as
 // sr_mfcc_batch_dev launches it, and puts back what the next push's first frame needs (k_spot_live_keep).  HOST ONLY.
 #pragma once
@@ -6,7 +6,7 @@
 
 namespace sr {
 
-// the layout the stage and keep kernels share: one definition for both sessions
+// the layout the stage and keep kernels share: one definition for every session
 static inline uint32_t live_pcm_keep_stride(const sr_engine *h) { return (h->frame_len + 7u) & ~7u; }  // a channel keeps at most frame_len samples
 static inline uint64_t live_pcm_stage_stride(const sr_engine *h, uint32_t chunk_max)  // [kept | chunk] and a frame of slack
 {

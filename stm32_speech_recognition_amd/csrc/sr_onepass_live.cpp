@@ -4,21 +4,17 @@
 //
 // The host knows every count: each channel's frames so far and the first frame of its last block, hence which channels a push
 // touches, how their new frames are cut into blocks and which compact output row each of them gets (the mirror,
-// sr_onepass_live_plan.h).  Nothing is read back to size or to label an output.  What the two level sessions do alike on the
-// host (sr_decode_live_host.h) serves here too: `m` and `max_words` are the names those rules know the mirror and the word
-// rows of an output row by.
+// sr_onepass_live_plan.h).  Nothing is read back to size or to label an output.  The session core, the checks, the push
+// sequence and the sequence of an end call are every live session's (sr_live_host.h).
 #include "sr_onepass_live_plan.h"
-#include "sr_decode_live_host.h"
+#include "sr_live_host.h"
 
 using namespace sr;
 
-struct sr_onepass_live {
-    sr_engine *h = nullptr;
+struct sr_onepass_live : LiveCore {
     OnePassLiveMirror om;
-    DecodeLiveMirror &m = om.d;
-    uint32_t max_words = 0, n_words_exact = 0;  // words_cap; no count is given
+    uint32_t words_cap = 0;               // the word rows of an output row; no count is given
     uint32_t tail = 0, skip_cost = 0, word_cost = 0;
-    std::vector<uint32_t> mid;            // PCM sessions: the channels' mid values
     // layout of the saved columns: that of the store the session was opened or last reset against
     uint32_t K = 0, tpl_len = 0;
     uint64_t layout_serial = 0;
@@ -26,22 +22,9 @@ struct sr_onepass_live {
     DevBuf<unsigned long long> A;         // [C][utt_frames + 1]
     DevBuf<uint32_t> E;                   // [C][utt_frames + 1]
     DevBuf<int16_t> hist;                 // [C][utt_frames][12]: the channels' feature rows
-    DevBuf<SpotLiveChan> d_chan;
-    // PCM sessions: kept samples, the rows [kept | chunk], their records and the features of one push
-    DevBuf<uint16_t> keep, stage;
-    DevBuf<sr_vad_rec> recs;
-    DevBuf<int16_t> feat;
-    uint32_t keep_stride = 0;
-    uint64_t stage_stride = 0;
-    hipEvent_t ev_last = nullptr;         // end of the last push (sr_onepass_live_end / _close wait for it)
-    hipStream_t last_stream = nullptr;    // ... and the stream it ran on: a push on another stream runs behind it
-    bool pending = false;
 };
 
 namespace {
-
-constexpr uint32_t kOnePassLiveMaxChannels = 65535u;  // a grid dimension
-constexpr uint32_t kOnePassLiveMaxFrames = 16383u;    // the u32 cost bound and the 16-bit start of a key
 
 uint32_t block_hook()
 {
@@ -57,7 +40,7 @@ int relayout(sr_onepass_live *l)
 {
     const sr_engine *h = l->h;
     const uint32_t tpl_len = h->tpl_rows - 1;
-    if (int rc = l->cols.reserve((size_t)l->m.C * h->K * tpl_len)) return rc;
+    if (int rc = l->cols.reserve((size_t)l->C * h->K * tpl_len)) return rc;
     l->K = h->K;
     l->tpl_len = tpl_len;
     l->layout_serial = h->store_serial;
@@ -73,10 +56,11 @@ int plan_push(const sr_onepass_live *l, const uint32_t *n, uint32_t n_all, OnePa
     return SR_OK;
 }
 
+// (the store is checked behind the buffers here)
 int check_out(const sr_onepass_live *l, uint32_t n_out, uint32_t max_rows, const sr_chain_rec *rec, const sr_chain_word *words,
               const sr_chain_live_row *rows)
 {
-    if (int rc = check_outputs(l, n_out, max_rows, rec, words, nullptr, rows, false)) return rc;
+    if (int rc = check_outputs(l->words_cap, n_out, max_rows, rec, words, nullptr, rows, [] { return SR_OK; })) return rc;
     return n_out ? check_store(l) : SR_OK;
 }
 
@@ -85,8 +69,8 @@ OnePassLiveArgs live_args(const sr_onepass_live *l, const int16_t *d_mfcc, uint6
 {
     const sr_engine *h = l->h;
     const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
-    return OnePassLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->m.C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, l->K, h->tpl_stride, l->tpl_len,
-                           l->m.utt_frames + 1u, block, l->max_words, l->tail, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p, l->hist.p,
+    return OnePassLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, l->K, h->tpl_stride, l->tpl_len,
+                           l->om.d.utt_frames + 1u, block, l->words_cap, l->tail, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p, l->hist.p,
                            t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec, d_words};
 }
 
@@ -95,10 +79,27 @@ OnePassLiveArgs live_args(const sr_onepass_live *l, const int16_t *d_mfcc, uint6
 int launch_push(sr_onepass_live *l, const OnePassLivePlan &pl, const int16_t *d_mfcc, uint64_t row_stride, sr_chain_rec *d_rec,
                 sr_chain_word *d_words, hipStream_t s)
 {
-    if (!pl.d.rows) return SR_OK;
     launch_onepass_live(live_args(l, d_mfcc, row_stride, pl.block, d_rec, d_words), pl.n_blocks, s);
     HIP_TRY(hipGetLastError());
     return SR_OK;
+}
+
+// the four push forms: a push enqueues work when a channel emits a row
+int push(sr_onepass_live *l, const LiveIn &in, bool device, void *stream, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
+         sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    OnePassLivePlan pl;
+    int rc = plan_push(l, n, n_all, &pl);
+    if (!rc) rc = check_live_in(l->om.d.pcm, in, pl.d.max_n, device);
+    if (!rc) rc = check_out(l, pl.d.rows, max_rows, rec, words, rows);
+    if (rc) return rc;
+    return live_push_chain(
+        *l, pl.d, in, device, stream, l->words_cap, rec, words, nullptr,
+        [&](const int16_t *f, uint64_t rs, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *, hipStream_t s) {
+            return launch_push(l, pl, f, rs, d_rec, d_words, s);
+        },
+        [&] { onepass_live_advance(l->om, pl, rows, n_rows); });
 }
 
 }  // namespace
@@ -108,7 +109,7 @@ extern "C" {
 int sr_onepass_live_geometry(uint32_t tpl_rows, uint32_t K, uint32_t min_tpl_frames, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[4])
 {
     if (!out || !tpl_rows || tpl_rows > 16383 || !K || K > kChainMaxSlots || !min_tpl_frames || min_tpl_frames > tpl_rows || !utt_frames ||
-        utt_frames > kOnePassLiveMaxFrames || !chunk_max || chunk_max > utt_frames)
+        utt_frames > kLiveMaxFrames || !chunk_max || chunk_max > utt_frames)
         return fail(SR_ERR_BAD_ARG, "null / zero argument, or one outside its range");
     const LdsBudget mi355x;  // no device: MI355X's figures
     const uint32_t L = min_tpl_frames / 2u + 1u;
@@ -127,54 +128,34 @@ int sr_onepass_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, 
     if (int rc = check_chain(h, 1, 0, skip_cost, word_cost)) return rc;
     if (!words_cap) return fail(SR_ERR_BAD_ARG, "words_cap must be at least 1");
     if (flags & ~SR_OP_LIVE_TAIL) return fail(SR_ERR_BAD_ARG, "unknown flag");
-    if (!n_channels || n_channels > kOnePassLiveMaxChannels || !utt_frames || utt_frames > kOnePassLiveMaxFrames)
+    if (!n_channels || n_channels > kLiveMaxChannels || !utt_frames || utt_frames > kLiveMaxFrames)
         return fail(SR_ERR_BAD_ARG, "n_channels not in 1..65535 / utt_frames not in 1..16383");
     if (!onepass_cost_ok(utt_frames, onepass_reach(h->tpl_len_host.data(), h->K), word_cost))
         return fail(SR_ERR_BAD_ARG, "(utt_frames / L) * word_cost must be at most 2^30, L = the shortest valid template's frames / 2 + 1");
-    if (!chunk_max) return fail(SR_ERR_BAD_ARG, "chunk_max 0");
-    if (mid) {
-        if (((uint64_t)chunk_max + h->hop - 1) / h->hop > std::min(h->cfg.max_frames, utt_frames))
-            return fail(SR_ERR_BAD_ARG, "a push of chunk_max samples could complete more than min(max_frames, utt_frames) frames");
-        for (uint32_t c = 0; c < n_channels; c++)
-            if (mid[c] > 0xFFFFu) return fail(SR_ERR_BAD_ARG, "mid exceeds the u16 sample range");
-        if (int rc = check_batch(h, n_channels)) return rc;
-    } else if (chunk_max > utt_frames) {
-        return fail(SR_ERR_BAD_ARG, "chunk_max not in 1..utt_frames");
-    }
+    if (int rc = LiveCore::check_open(h, n_channels, chunk_max, mid ? std::min(h->cfg.max_frames, utt_frames) : utt_frames, mid)) return rc;
     ENTER_DEVICE(h);
     sr_onepass_live *l = new sr_onepass_live();
-    l->h = h;
     l->om.open(n_channels, h->store_serial);
-    l->m.chunk_max = chunk_max;
-    l->m.utt_frames = utt_frames;
-    l->m.pcm = mid != nullptr;
-    l->m.frame_len = h->frame_len;
-    l->m.hop = h->hop;
-    l->max_words = words_cap;
+    l->om.d.chunk_max = chunk_max;
+    l->om.d.utt_frames = utt_frames;
+    l->om.d.pcm = mid != nullptr;
+    l->om.d.frame_len = h->frame_len;
+    l->om.d.hop = h->hop;
+    l->words_cap = words_cap;
     l->tail = flags & SR_OP_LIVE_TAIL;
     l->skip_cost = skip_cost;
     l->word_cost = word_cost;
     const size_t P = (size_t)utt_frames + 1;
-    int rc = relayout(l);
+    int rc = l->open_common(h, n_channels, chunk_max, mid);
+    if (!rc) rc = relayout(l);
     if (!rc) rc = l->A.reserve((size_t)n_channels * P);
     if (!rc) rc = l->E.reserve((size_t)n_channels * P);
     if (!rc) rc = l->hist.reserve((size_t)n_channels * utt_frames * kCoef);
-    if (!rc) rc = l->d_chan.reserve(n_channels);
-    if (!rc && mid) {
-        l->mid.assign(mid, mid + n_channels);
-        l->keep_stride = live_pcm_keep_stride(h);
-        l->stage_stride = live_pcm_stage_stride(h, chunk_max);
-        rc = l->keep.reserve((size_t)n_channels * l->keep_stride);
-        if (!rc) rc = l->stage.reserve((size_t)n_channels * l->stage_stride);
-        if (!rc) rc = l->recs.reserve(n_channels);
-        if (!rc) rc = l->feat.reserve(h->mfcc_elems(n_channels));
-    }
     // no word yet anywhere, E(0) = 0: the state of an empty channel, which a push finds without a launch of its own (every other
     // position of E is written before it is read)
     if (!rc && (hipMemsetAsync(l->A.p, 0xFF, (size_t)n_channels * P * 8, nullptr) != hipSuccess ||
                 hipMemsetAsync(l->E.p, 0, (size_t)n_channels * P * 4, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
         rc = fail(SR_ERR_HIP, "clearing the session's history failed");
-    if (!rc && hipEventCreateWithFlags(&l->ev_last, hipEventDisableTiming) != hipSuccess) rc = fail(SR_ERR_HIP, "hipEventCreate failed");
     if (rc) {
         (void)hipGetLastError();
         sr_onepass_live_close(l);
@@ -189,116 +170,37 @@ void sr_onepass_live_close(sr_onepass_live *l)
     if (!l) return;
     DeviceGuard guard;
     (void)guard.enter(l->h->device);
-    if (l->pending) (void)hipEventSynchronize(l->ev_last);
+    l->release();
     l->cols.release();
     l->A.release();
     l->E.release();
     l->hist.release();
-    l->d_chan.release();
-    l->keep.release();
-    l->stage.release();
-    l->recs.release();
-    l->feat.release();
-    if (l->ev_last) (void)hipEventDestroy(l->ev_last);
     delete l;
 }
 
 int sr_onepass_live_push_dev(sr_onepass_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
                              sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows, uint32_t *n_rows, void *stream)
 {
-    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
-    OnePassLivePlan pl;
-    int rc = plan_push(l, n, n_all, &pl);
-    if (!rc) rc = check_frames_in(l, pl.d, d_mfcc, row_stride, true);
-    if (!rc) rc = check_out(l, pl.d.rows, max_rows, d_rec, d_words, rows);
-    if (rc) return rc;
-    ENTER_DEVICE(l->h);
-    const hipStream_t s = (hipStream_t)stream;
-    if (pl.d.rows) {
-        if ((rc = order_after_last_push(l, s))) return rc;
-        if ((rc = upload_chan(l, pl.d.chan, s))) return rc;
-        if ((rc = launch_push(l, pl, d_mfcc, row_stride, d_rec, d_words, s))) return rc;
-    }
-    onepass_live_advance(l->om, pl, rows, n_rows);
-    return pl.d.rows ? mark_push(l, s) : SR_OK;
+    return push(l, LiveIn{d_mfcc, row_stride, false}, true, stream, n, n_all, max_rows, d_rec, d_words, rows, n_rows);
 }
 
 int sr_onepass_live_push(sr_onepass_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
                          sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows)
 {
-    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
-    OnePassLivePlan pl;
-    int rc = plan_push(l, n, n_all, &pl);
-    if (!rc) rc = check_frames_in(l, pl.d, mfcc, row_stride, false);
-    if (!rc) rc = check_out(l, pl.d.rows, max_rows, rec, words, rows);
-    if (rc) return rc;
-    sr_engine *h = l->h;
-    ENTER_HOST_CALL(h);
-    HostOutputs o;
-    if (pl.d.rows) {
-        const size_t ds = (size_t)pl.d.max_frames * kCoef;  // device rows hold the largest count
-        if ((rc = h->s_mfcc.reserve((size_t)l->m.C * ds))) return rc;
-        if ((rc = o.reserve(pl.d.rows, l->max_words, false))) return rc;
-        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
-            if (pl.d.chan[c].n) COPY_UP(h->s_mfcc.p + c * ds, mfcc + (size_t)c * row_stride, (size_t)pl.d.chan[c].n * kCoef * 2);
-        if ((rc = order_after_last_push(l, nullptr))) return rc;
-        if ((rc = upload_chan(l, pl.d.chan, nullptr))) return rc;
-        if ((rc = launch_push(l, pl, h->s_mfcc.p, ds, o.rec.p, o.words.p, nullptr))) return rc;
-    }
-    onepass_live_advance(l->om, pl, rows, n_rows);
-    if (pl.d.rows && (rc = mark_push(l, nullptr))) return rc;
-    return pl.d.rows ? o.down(pl.d.rows, l->max_words, rec, words, nullptr) : SR_OK;
+    return push(l, LiveIn{mfcc, row_stride, false}, false, nullptr, n, n_all, max_rows, rec, words, rows, n_rows);
 }
 
 int sr_onepass_live_push_pcm_dev(sr_onepass_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
                                  uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows, uint32_t *n_rows,
                                  void *stream)
 {
-    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
-    OnePassLivePlan pl;
-    int rc = plan_push(l, n, n_all, &pl);
-    if (!rc) rc = check_pcm_in(l, pl.d, d_pcm, pcm_stride, true);
-    if (!rc) rc = check_out(l, pl.d.rows, max_rows, d_rec, d_words, rows);
-    if (rc) return rc;
-    sr_engine *h = l->h;
-    ENTER_DEVICE(h);
-    const hipStream_t s = (hipStream_t)stream;
-    if (pl.d.rows) {
-        if ((rc = order_after_last_push(l, s))) return rc;
-        if ((rc = upload_chan(l, pl.d.chan, s))) return rc;
-        if ((rc = launch_front_end(l, pl.d, d_pcm, pcm_stride, s))) return rc;
-        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, d_rec, d_words, s))) return rc;
-    }
-    onepass_live_advance(l->om, pl, rows, n_rows);
-    return pl.d.rows ? mark_push(l, s) : SR_OK;
+    return push(l, LiveIn{d_pcm, pcm_stride, true}, true, stream, n, n_all, max_rows, d_rec, d_words, rows, n_rows);
 }
 
 int sr_onepass_live_push_pcm(sr_onepass_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all, uint32_t max_rows,
                              sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows)
 {
-    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
-    OnePassLivePlan pl;
-    int rc = plan_push(l, n, n_all, &pl);
-    if (!rc) rc = check_pcm_in(l, pl.d, pcm, pcm_stride, false);
-    if (!rc) rc = check_out(l, pl.d.rows, max_rows, rec, words, rows);
-    if (rc) return rc;
-    sr_engine *h = l->h;
-    ENTER_HOST_CALL(h);
-    HostOutputs o;
-    if (pl.d.rows) {
-        const uint64_t ds = dev_pitch(pl.d.max_n);
-        if ((rc = h->s_pcm.reserve((size_t)l->m.C * ds))) return rc;
-        if ((rc = o.reserve(pl.d.rows, l->max_words, false))) return rc;
-        for (uint32_t c = 0; c < l->m.C; c++)  // count by count: nothing past n[c] of a caller's row is read
-            if (pl.d.chan[c].n_samp) COPY_UP(h->s_pcm.p + c * ds, pcm + (size_t)c * pcm_stride, (size_t)pl.d.chan[c].n_samp * 2);
-        if ((rc = order_after_last_push(l, nullptr))) return rc;
-        if ((rc = upload_chan(l, pl.d.chan, nullptr))) return rc;
-        if ((rc = launch_front_end(l, pl.d, h->s_pcm.p, ds, nullptr))) return rc;
-        if ((rc = launch_push(l, pl, l->feat.p, (uint64_t)h->cfg.max_frames * kCoef, o.rec.p, o.words.p, nullptr))) return rc;
-    }
-    onepass_live_advance(l->om, pl, rows, n_rows);
-    if (pl.d.rows && (rc = mark_push(l, nullptr))) return rc;
-    return pl.d.rows ? o.down(pl.d.rows, l->max_words, rec, words, nullptr) : SR_OK;
+    return push(l, LiveIn{pcm, pcm_stride, true}, false, nullptr, n, n_all, max_rows, rec, words, rows, n_rows);
 }
 
 int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
@@ -312,30 +214,14 @@ int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n
     if (!onepass_live_end_list(l->om, h->store_serial, channels, n_ch, &chan, &order, &why)) return fail(SR_ERR_BAD_ARG, why);
     const uint32_t n_out = (uint32_t)order.size();
     if (int rc = check_out(l, n_out, n_out, rec, words, rows)) return rc;
-    if (int rc = check_end_rows(l, n_out, rec, words, nullptr, rows)) return rc;
-    if (!n_out) {
-        if (n_rows) *n_rows = 0;
-        return SR_OK;
-    }
-    ENTER_HOST_CALL(h);
-    if (l->pending) {
-        HIP_TRY(hipEventSynchronize(l->ev_last));
-        l->pending = false;
-    }
-    HostOutputs o;
-    if (int rc = o.reserve(n_out, l->max_words, false)) return rc;
+    if (int rc = check_end_rows(l->words_cap, n_out, rec, words, nullptr, rows)) return rc;
     // Every channel that still holds state is bound to a store that is gone, and the trace reads no column: the columns are
     // laid out again BEFORE anything is written, so that a failed allocation leaves outputs, mirror and layout as they were.
-    if (l->layout_serial != h->store_serial)
-        if (int rc = relayout(l)) return rc;
-    if (int rc = upload_chan(l, chan, nullptr)) return rc;
-    launch_onepass_live_end(live_args(l, nullptr, 0, 1u, o.rec.p, o.words.p), nullptr);
-    HIP_TRY(hipGetLastError());
-    if (int rc = o.down(n_out, l->max_words, rec, words, nullptr)) return rc;
-    onepass_live_reset(l->om, h->store_serial, order);
-    for (uint32_t r = 0; r < n_out; r++) rows[r] = order[r];
-    if (n_rows) *n_rows = n_out;
-    return SR_OK;
+    return live_end(
+        *l, chan, order, l->words_cap, rec, words, nullptr, rows, n_rows,
+        [&] { return l->layout_serial != h->store_serial ? relayout(l) : SR_OK; },
+        [&](sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) { launch_onepass_live_end(live_args(l, nullptr, 0, 1u, d_rec, d_words), nullptr); },
+        [&] { onepass_live_reset(l->om, h->store_serial, order); });
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@ import ctypes as C
 import functools
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -22,6 +23,7 @@ from stm32_speech_recognition_amd.engine import DIS_ERR, NBEST_DTYPE, Engine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "sr_engine.h")
+CSRC = os.path.join(ROOT, "stm32_speech_recognition_amd", "csrc")
 FUNCS = ("sr_spot_live_geometry", "sr_spot_live_open", "sr_spot_live_rows", "sr_spot_live_windows", "sr_spot_live_push_dev", "sr_spot_live_push",
          "sr_spot_live_push_pcm_dev", "sr_spot_live_push_pcm", "sr_spot_live_end")
 BAD_ARG = 3
@@ -159,6 +161,19 @@ def test_geometry_and_row_counts_follow_their_definitions():
     L.sr_spot_live_rows.restype = U32
     assert L.sr_spot_live_rows(None, None, U32(5)) == 0
     assert live.pcm_frames(160, 160, 80) == 0 and live.pcm_frames(161, 160, 80) == 1 and live.pcm_frames(241, 160, 80) == 2
+
+
+def test_host_mirror_runs_clean_under_the_sanitizers(tmp_path):
+    """windows and row bases of a push, PCM framing and its agreement with the decoders' plan, refusal order, the flush list of
+    csrc/sr_spot_live_plan.h against values worked out by hand: a stand-alone program on the CPU under AddressSanitizer and
+    UndefinedBehaviorSanitizer"""
+    exe = str(tmp_path / "plan_check")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "--cuda-host-only", "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-Xarch_host", "-fno-sanitize-recover=undefined", "-I" + CSRC, os.path.join(ROOT, "tests", "spot_live_plan", "plan_check.cpp"),
+                           "-o", exe])
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "plan_check ok" in run.stdout, (run.stdout, run.stderr)
 
 
 # ---- GPU: fixtures -------------------------------------------------------------------------------------------------------------
