@@ -191,11 +191,14 @@ __global__ void __launch_bounds__(64 * ext::kWaves, mfcc_ext_waves_per_simd<Args
             qa[t] = q2.x;  // x[i-2] | x[i-1] << 16
             qb[t] = q2.y;  // x[i]   | x[i+1] << 16
         }
-        // A segment that starts at sample 1 (only sr_mfcc_batch / sr_recognize_segments callers can produce one: VAD
-        // segments start on frame boundaries) puts the first pair of frame 0 at byte offset -2: out of range for the
-        // resource, so the load (at least its first dword: x[i-2] AND x[i-1]) came back as 0 -- but x[i-1] = sample 0 is
-        // the pre-emphasis predecessor of the segment's first sample (MFCC.C:119).  Wave-uniform and rare: that lane
-        // fetches its first pair again with plain loads (x[i-2] does not exist and is never used).
+        // A segment that starts at sample 1 (VAD segments start on frame boundaries and never do; a caller's own segment
+        // may: sr_mfcc_batch, sr_recognize_segments and the *_batch PCM forms of the spotter and the decoders -- and EVERY
+        // push of a PCM session does, csrc/sr_live_pcm.h stages its rows with seg[0] = 1, so there this branch is the only
+        // path and every pair of every frame is fetched in the 2-byte-aligned form above) puts the first pair of frame 0
+        // at byte offset -2: out of range for the resource, so the load (at least its first dword: x[i-2] AND x[i-1])
+        // came back as 0 -- but x[i-1] = sample 0 is the pre-emphasis predecessor of the segment's first sample
+        // (MFCC.C:119).  Wave-uniform: that lane fetches its first pair again with plain loads (x[i-2] does not exist and
+        // is never used).  tests/test_pcm_front_ends.py runs it under every PCM entry point.
         if (it.s0 < 2) {
             if (off < 0) {
                 qa[0] = (uint32_t)it.row[0] << 16;
