@@ -1552,9 +1552,25 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    PCM sessions alike.  Puts columns up to the frame cap within a test's reach
  *   "multi_allow_dup"                sr_multi_create accepts one device several times; honoured only when SR_RCCL_LIBRARY
  *                                    names the collective library explicitly (1-GPU tests over the in-process RCCL double)
+ *   "lds_poison_launches"            while non-zero, the LDS of every CU is overwritten (k_lds_poison, as sr_lds_poison does) on
+ *                                    the launch's own stream in front of EVERY kernel launch of the library, between the
+ *                                    launches of one call too.  Bits 0..31 are the seed, bits 32..33 the pattern: 0 = HIGH,
+ *                                    sr_lds_poison's (seed ^ i * 2654435761) | 0x80000000 for word i, which loses every minimum
+ *                                    it enters; 1 = LOW, (seed ^ i * 2654435761) & 7, a small, valid-looking cost or index that
+ *                                    wins every minimum.  Other patterns and negative values return SR_ERR_BAD_ARG.  Setting
+ *                                    it (to any value) empties what sr_lds_launch_points reports.  It multiplies the launches
+ *                                    of a call: keep it 0 around timings, sr_get_stage_launches and sr_get_stage_ms
  * Unknown names return SR_ERR_BAD_ARG. */
 int sr_dev_hook(const char *name, int64_t value);
 int sr_testing_build(void);
+/* Testing build only (the product library returns SR_ERR_BAD_ARG from both).
+ * sr_lds_launch_points: *count = poison launches issued in front of kernel launches since "lds_poison_launches" was last set;
+ * names (optional, names_cap bytes) = the distinct kernel names they stood in front of, comma-separated, in order of first use.
+ * sr_lds_probe: one workgroup per CU copies the first `words` (1..4096) words of its LDS -- which it does not write -- to
+ * d_out[workgroup * words + i] (device memory, CUs * words words), asynchronous on `stream`.  Each workgroup takes a CU's whole
+ * LDS, so word i is the CU's word i.  The launch goes through a launch point like every other. */
+int sr_lds_launch_points(uint64_t *count, char *names, uint32_t names_cap);
+int sr_lds_probe(sr_engine *h, uint32_t words, uint32_t *d_out, void *stream);
 
 /* diagnostics, host-only (touches no device): the launch geometry the staged DTW kernel would use for a store of n_templates
  * and a frame cap of max_frames: out[0] = utterances per workgroup (0 = generic kernel), out[1] = templates per workgroup (the

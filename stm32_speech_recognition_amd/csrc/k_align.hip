@@ -227,17 +227,20 @@ __global__ void __launch_bounds__(256) k_align_finalise(const AlignFinalArgs a)
 void launch_align(const AlignArgs &a, size_t lds_bytes, hipStream_t s)
 {
     if (!a.n_pairs) return;
+    SR_LAUNCH_POINT(s, "k_dp_align");
     hipLaunchKernelGGL(k_dp_align, dim3(a.n_pairs), dim3(64), lds_bytes, s, a);
 }
 void launch_align_accum(const AlignAccumArgs &a, hipStream_t s)
 {
     if (!a.n_pairs) return;
+    SR_LAUNCH_POINT(s, "k_align_accum");
     hipLaunchKernelGGL(k_align_accum, dim3(a.n_pairs), dim3(64), 0, s, a);
 }
 void launch_align_finalise(const AlignFinalArgs &a, hipStream_t s)
 {
     const uint64_t n = (uint64_t)a.M * a.cen_rows, blocks = (n + 255) / 256;
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_align_finalise");
     hipLaunchKernelGGL(k_align_finalise, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, s, a);
 }
 const char *align_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_dp_align, "k_dp_align"}}, bytes); }

@@ -176,17 +176,26 @@ void launch_chain(const ChainArgs &a, hipStream_t s)
 {
     if (!a.n_rows || !a.K) return;
     const size_t lds = spot_lds_bytes(a.tpl_len);
+    SR_LAUNCH_POINT(s, "k_chain_init");
     hipLaunchKernelGGL(k_chain_init, dim3(a.n_rows), dim3(256), 0, s, a);
     const dim3 grid(a.K, a.n_rows, (a.n_chunks + kSpotWaves - 1) / kSpotWaves);
     for (uint32_t l = 1; l <= a.max_words; l++) {
+        SR_LAUNCH_POINT(s, "k_chain_words");
         hipLaunchKernelGGL(k_chain_words, grid, dim3(64 * kSpotWaves), lds, s, a, l);
+        SR_LAUNCH_POINT(s, "k_chain_close");
         hipLaunchKernelGGL(k_chain_close, dim3(a.n_rows), dim3(256), 0, s, a, l);
     }
+    SR_LAUNCH_POINT(s, "k_chain_trace");
     hipLaunchKernelGGL(k_chain_trace, dim3(a.n_rows), dim3(64), 0, s, a);
 }
-void launch_chain_init(const ChainArgs &a, hipStream_t s) { hipLaunchKernelGGL(k_chain_init, dim3(a.n_rows), dim3(256), 0, s, a); }
+void launch_chain_init(const ChainArgs &a, hipStream_t s)
+{
+    SR_LAUNCH_POINT(s, "k_chain_init");
+    hipLaunchKernelGGL(k_chain_init, dim3(a.n_rows), dim3(256), 0, s, a);
+}
 void launch_chain_close(const ChainArgs &a, uint32_t level, hipStream_t s)
 {
+    SR_LAUNCH_POINT(s, "k_chain_close");
     hipLaunchKernelGGL(k_chain_close, dim3(a.n_rows), dim3(256), 0, s, a, level);
 }
 const char *chain_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_chain_words, "k_chain_words"}}, bytes); }

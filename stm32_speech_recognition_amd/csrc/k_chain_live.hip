@@ -189,17 +189,22 @@ void launch_chain_live(const ChainLiveArgs &a, hipStream_t s)
 {
     if (!a.C || !a.K) return;
     const size_t lds = spot_lds_bytes(a.tpl_len);
+    SR_LAUNCH_POINT(s, "k_chain_live_init");
     hipLaunchKernelGGL(k_chain_live_init, dim3(a.C), dim3(256), 0, s, a);
     const dim3 grid(a.K, (a.C + kSpotWaves - 1) / kSpotWaves);
     for (uint32_t l = 1; l <= a.max_words; l++) {
+        SR_LAUNCH_POINT(s, "k_chain_live_words");
         hipLaunchKernelGGL(k_chain_live_words, grid, dim3(64 * kSpotWaves), lds, s, a, l);
+        SR_LAUNCH_POINT(s, "k_chain_live_close");
         hipLaunchKernelGGL(k_chain_live_close, dim3(a.C), dim3(256), 0, s, a, l);
     }
+    SR_LAUNCH_POINT(s, "k_chain_live_trace");
     hipLaunchKernelGGL(k_chain_live_trace, dim3(a.C), dim3(64), 0, s, a);
 }
 void launch_chain_live_trace(const ChainLiveArgs &a, hipStream_t s)
 {
     if (!a.C) return;
+    SR_LAUNCH_POINT(s, "k_chain_live_trace");
     hipLaunchKernelGGL(k_chain_live_trace, dim3(a.C), dim3(64), 0, s, a);
 }
 const char *chain_live_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_chain_live_words, "k_chain_live_words"}}, bytes); }

@@ -156,15 +156,18 @@ __global__ void __launch_bounds__(256) k_cluster_tally(const sr_train_stat *stat
 void launch_cluster_score(const ClusterScoreArgs &a, size_t lds_bytes, hipStream_t s)
 {
     if (!a.n_wg) return;
+    SR_LAUNCH_POINT(s, "k_cluster_score");
     hipLaunchKernelGGL(k_cluster_score, dim3(a.n_wg), dim3(64 * kClusterWaves), lds_bytes, s, a);
 }
 void launch_cluster_assign(const ClusterAssignArgs &a, hipStream_t s)
 {
     if (!a.E) return;
+    SR_LAUNCH_POINT(s, "k_cluster_assign");
     hipLaunchKernelGGL(k_cluster_assign, dim3((a.E + 255) / 256), dim3(256), 0, s, a);
 }
 void launch_cluster_tally(const sr_train_stat *stats, uint32_t M, sr_cluster_iter *iter, hipStream_t s)
 {
+    SR_LAUNCH_POINT(s, "k_cluster_tally");
     hipLaunchKernelGGL(k_cluster_tally, dim3((M + 255) / 256), dim3(256), 0, s, stats, M, iter);
 }
 const char *cluster_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_cluster_score, "k_cluster_score"}}, bytes); }

@@ -123,6 +123,7 @@ __global__ void __launch_bounds__(64) k_get_mdl(const GetMdlArgs a)
 void launch_get_mdl(const GetMdlArgs &a, hipStream_t s)
 {
     if (!a.P) return;
+    SR_LAUNCH_POINT(s, "k_get_mdl");
     hipLaunchKernelGGL(k_get_mdl, dim3((a.P + 63) / 64), dim3(64), 0, s, a);
 }
 
@@ -839,11 +840,18 @@ void launch_dtw(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
         const uint32_t U = p.lds_u, Kc = p.lds_kc;
         DtwLdsArgs la{a, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, U, a.tie_delta, p.lds_tie_g, Kc};
         const dim3 grid((a.B + U - 1) / U, (a.K + Kc - 1) / Kc), block((uint32_t)(((uint64_t)U * Kc + 63) / 64 * 64));
-        if (a.n_coef > (uint32_t)kCoef) hipLaunchKernelGGL(k_dtw_lds<Dtw16>, grid, block, p.lds_bytes, s, la);
-        else hipLaunchKernelGGL(k_dtw_lds<Dtw12>, grid, block, p.lds_bytes, s, la);
+        if (a.n_coef > (uint32_t)kCoef) {
+            SR_LAUNCH_POINT(s, "k_dtw_lds");
+            hipLaunchKernelGGL(k_dtw_lds<Dtw16>, grid, block, p.lds_bytes, s, la);
+        } else {
+            SR_LAUNCH_POINT(s, "k_dtw_lds");
+            hipLaunchKernelGGL(k_dtw_lds<Dtw12>, grid, block, p.lds_bytes, s, la);
+        }
     } else if (a.n_coef != (uint32_t)kCoef) {  // stores that cannot be staged, other feature widths
+        SR_LAUNCH_POINT(s, "k_dtw_gen");
         hipLaunchKernelGGL(k_dtw_gen, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, s, a);
     } else {  // very long sequences / very many templates: generic global-memory walk
+        SR_LAUNCH_POINT(s, "k_dtw");
         hipLaunchKernelGGL(k_dtw, dim3((uint32_t)((n + 127) / 128)), dim3(128), 0, s, a);
     }
 }
@@ -893,6 +901,7 @@ __global__ void __launch_bounds__(256) k_argmin(const DtwArgs a)
 void launch_argmin(const DtwArgs &a, hipStream_t s)
 {
     if (!a.B) return;
+    SR_LAUNCH_POINT(s, "k_argmin");
     hipLaunchKernelGGL(k_argmin, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
 }
 

@@ -427,8 +427,13 @@ void launch_dtw_cells(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
     const size_t lds = p.cells_bytes;
     for (uint32_t b0 = 0; b0 < a.B; b0 += 65535) {  // utterances are the grid's second dimension
         const uint32_t nb = a.B - b0 < 65535 ? a.B - b0 : 65535;
-        if (a.n_coef <= (uint32_t)kCoef) hipLaunchKernelGGL(k_dtw_cells<6>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
-        else hipLaunchKernelGGL(k_dtw_cells<8>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
+        if (a.n_coef <= (uint32_t)kCoef) {
+            SR_LAUNCH_POINT(s, "k_dtw_cells");
+            hipLaunchKernelGGL(k_dtw_cells<6>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
+        } else {
+            SR_LAUNCH_POINT(s, "k_dtw_cells");
+            hipLaunchKernelGGL(k_dtw_cells<8>, dim3(a.K, nb), dim3(cells::kThreads), lds, s, a, b0);
+        }
     }
 }
 const char *dtw_cells_allow_lds(uint32_t bytes)

@@ -507,10 +507,19 @@ void launch_dtw_dp(const DtwArgs &a, uint32_t lanes, const LdsBudget &budget, hi
         sa.scores = a.scores + (size_t)b0 * a.K;
         const dim3 grid(a.K, (sa.B + per_wg - 1) / per_wg), block(64 * W);
         DpBandArgs ba{sa, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, rp};
-        if (G == 1) hipLaunchKernelGGL(k_dtw_dp_wave64, grid, block, lds, s, sa);
-        else if (G == 4) hipLaunchKernelGGL((k_dtw_dp_band<4, 4>), grid, block, lds, s, ba);
-        else if (G == 8) hipLaunchKernelGGL((k_dtw_dp_band<8, 4>), grid, block, lds, s, ba);
-        else hipLaunchKernelGGL((k_dtw_dp_band<16, 4>), grid, block, lds, s, ba);
+        if (G == 1) {
+            SR_LAUNCH_POINT(s, "k_dtw_dp_wave64");
+            hipLaunchKernelGGL(k_dtw_dp_wave64, grid, block, lds, s, sa);
+        } else if (G == 4) {
+            SR_LAUNCH_POINT(s, "k_dtw_dp_band");
+            hipLaunchKernelGGL((k_dtw_dp_band<4, 4>), grid, block, lds, s, ba);
+        } else if (G == 8) {
+            SR_LAUNCH_POINT(s, "k_dtw_dp_band");
+            hipLaunchKernelGGL((k_dtw_dp_band<8, 4>), grid, block, lds, s, ba);
+        } else {
+            SR_LAUNCH_POINT(s, "k_dtw_dp_band");
+            hipLaunchKernelGGL((k_dtw_dp_band<16, 4>), grid, block, lds, s, ba);
+        }
     }
 }
 
@@ -527,15 +536,23 @@ void launch_dtw_dp_sparse(const DtwArgs &a, const uint8_t *marks, uint32_t mark_
     const dim3 block(64 * W);
     if (G == 1) {  // (the flags of the mark check live in the boundary columns: the dense kernel's LDS)
         const dim3 grid(a.K, (a.B + kDpSparseRowsWave - 1) / kDpSparseRowsWave);
+        SR_LAUNCH_POINT(s, "k_dtw_dp_wave64_sparse");
         hipLaunchKernelGGL(k_dtw_dp_wave64_sparse, grid, block, (size_t)a.tpl_rows * 32 + (size_t)4 * a.tpl_rows * 4, s, a, sp);
         return;
     }
     const size_t lds = dp_band_lds(a.tpl_rows, G, W, &rp) + kDpSparseLds;
     const dim3 grid(a.K, (a.B + kDpSparseRowsBand - 1) / kDpSparseRowsBand);
     const DpBandArgs ba{a, (const u32x4 *)a.tplR, a.tpl_frames_s, a.tpl_orig, rp};
-    if (G == 4) hipLaunchKernelGGL((k_dtw_dp_band_sparse<4, 4>), grid, block, lds, s, ba, sp);
-    else if (G == 8) hipLaunchKernelGGL((k_dtw_dp_band_sparse<8, 4>), grid, block, lds, s, ba, sp);
-    else hipLaunchKernelGGL((k_dtw_dp_band_sparse<16, 4>), grid, block, lds, s, ba, sp);
+    if (G == 4) {
+        SR_LAUNCH_POINT(s, "k_dtw_dp_band_sparse");
+        hipLaunchKernelGGL((k_dtw_dp_band_sparse<4, 4>), grid, block, lds, s, ba, sp);
+    } else if (G == 8) {
+        SR_LAUNCH_POINT(s, "k_dtw_dp_band_sparse");
+        hipLaunchKernelGGL((k_dtw_dp_band_sparse<8, 4>), grid, block, lds, s, ba, sp);
+    } else {
+        SR_LAUNCH_POINT(s, "k_dtw_dp_band_sparse");
+        hipLaunchKernelGGL((k_dtw_dp_band_sparse<16, 4>), grid, block, lds, s, ba, sp);
+    }
 }
 const char *dtw_dp_allow_lds(uint32_t bytes)
 {

@@ -267,11 +267,21 @@ void launch_dtw_quad(const DtwArgs &a, const DtwPlan &p, hipStream_t s)
         const dim3 grid(gx, (nb + pu - 1) / pu);
         const dim3 blk(quad::kThreads);
         if (a.n_coef <= (uint32_t)kCoef) {
-            if (p.quad_neg2) hipLaunchKernelGGL((k_dtw_quad<6, true>), grid, blk, lds, s, a, pu, pk, b0);
-            else hipLaunchKernelGGL((k_dtw_quad<6, false>), grid, blk, lds, s, a, pu, pk, b0);
+            if (p.quad_neg2) {
+                SR_LAUNCH_POINT(s, "k_dtw_quad");
+                hipLaunchKernelGGL((k_dtw_quad<6, true>), grid, blk, lds, s, a, pu, pk, b0);
+            } else {
+                SR_LAUNCH_POINT(s, "k_dtw_quad");
+                hipLaunchKernelGGL((k_dtw_quad<6, false>), grid, blk, lds, s, a, pu, pk, b0);
+            }
         } else {
-            if (p.quad_neg2) hipLaunchKernelGGL((k_dtw_quad<8, true>), grid, blk, lds, s, a, pu, pk, b0);
-            else hipLaunchKernelGGL((k_dtw_quad<8, false>), grid, blk, lds, s, a, pu, pk, b0);
+            if (p.quad_neg2) {
+                SR_LAUNCH_POINT(s, "k_dtw_quad");
+                hipLaunchKernelGGL((k_dtw_quad<8, true>), grid, blk, lds, s, a, pu, pk, b0);
+            } else {
+                SR_LAUNCH_POINT(s, "k_dtw_quad");
+                hipLaunchKernelGGL((k_dtw_quad<8, false>), grid, blk, lds, s, a, pu, pk, b0);
+            }
         }
     }
 }

@@ -21,6 +21,7 @@ __global__ void __launch_bounds__(64) k_fft_q15(const uint32_t *in, uint32_t *ou
 void launch_fft_q15(const uint32_t *in, uint32_t *out, uint32_t n, const DevTables &t, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_fft_q15");
     hipLaunchKernelGGL(k_fft_q15, dim3(n < 4096 ? n : 4096), dim3(64), 0, s, in, out, n, t);
 }
 
@@ -50,6 +51,7 @@ void launch_fft_mag(const int16_t *frames, uint32_t len, uint32_t *mag, uint32_t
                     hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_fft_mag");
     hipLaunchKernelGGL(k_fft_mag, dim3(n < 4096 ? n : 4096), dim3(64), 0, s, frames, len, mag, raw_hi, n, t);
 }
 

@@ -208,16 +208,22 @@ void launch_forced(const ForcedArgs &a, const uint32_t *item0, uint32_t levels, 
     launch_chain_init(a.c, s);
     for (uint32_t l = 1; l <= levels; l++) {
         const uint32_t n_items = item0[l] - item0[l - 1];
-        if (n_items)  // (a level without items stays unreachable: the close below says so in E_l)
+        if (n_items) {  // (a level without items stays unreachable: the close below says so in E_l)
+            SR_LAUNCH_POINT(s, "k_forced_words");
             hipLaunchKernelGGL(k_forced_words, dim3(n_items, (a.c.n_chunks + kSpotWaves - 1) / kSpotWaves), dim3(64 * kSpotWaves), lds, s, a, l,
                                item0[l - 1]);
+        }
         launch_chain_close(a.c, l, s);
     }
+    SR_LAUNCH_POINT(s, "k_forced_trace");
     hipLaunchKernelGGL(k_forced_trace, dim3(a.c.n_rows), dim3(64), 0, s, a);
 }
 void launch_gather_spans(const GatherArgs &a, hipStream_t s)
 {
-    if (a.n_ex) hipLaunchKernelGGL(k_gather_spans, dim3(a.n_ex), dim3(256), 0, s, a);
+    if (a.n_ex) {
+        SR_LAUNCH_POINT(s, "k_gather_spans");
+        hipLaunchKernelGGL(k_gather_spans, dim3(a.n_ex), dim3(256), 0, s, a);
+    }
 }
 const char *forced_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_forced_words, "k_forced_words"}}, bytes); }
 

@@ -415,19 +415,32 @@ void launch_gram(const GramArgs &a, const GramCosts *w, hipStream_t s)
     const size_t lds = spot_lds_bytes(a.c.tpl_len);
     const uint32_t P = a.c.max_frames + 1u;
     const size_t n_e = (size_t)(a.c.max_words + 1u) * a.n_states * P;
+    SR_LAUNCH_POINT(s, "k_gram_init");
     hipLaunchKernelGGL(k_gram_init, dim3(a.c.n_rows, (uint32_t)std::min<size_t>((n_e + 4095u) / 4096u, 64u)), dim3(256), 0, s, a);
     for (uint32_t l = 1; l <= a.c.max_words; l++) {
         const GramLevel &lv = a.lv[l - 1];
         if (!lv.n_items) continue;  // nothing can end here: the level stays unreachable
         const dim3 charge_grid((P + 255u) / 256u, lv.n_sets, a.c.n_rows);
-        if (w) hipLaunchKernelGGL(k_gram_charge_w, charge_grid, dim3(256), 0, s, a, *w, l);
-        else hipLaunchKernelGGL(k_gram_charge, charge_grid, dim3(256), 0, s, a, l);
+        if (w) {
+            SR_LAUNCH_POINT(s, "k_gram_charge_w");
+            hipLaunchKernelGGL(k_gram_charge_w, charge_grid, dim3(256), 0, s, a, *w, l);
+        } else {
+            SR_LAUNCH_POINT(s, "k_gram_charge");
+            hipLaunchKernelGGL(k_gram_charge, charge_grid, dim3(256), 0, s, a, l);
+        }
+        SR_LAUNCH_POINT(s, "k_gram_words");
         hipLaunchKernelGGL(k_gram_words, dim3(lv.n_items, a.c.n_rows, (a.c.n_chunks + kSpotWaves - 1) / kSpotWaves), dim3(64 * kSpotWaves), lds, s,
                            a, l);
+        SR_LAUNCH_POINT(s, "k_gram_close");
         hipLaunchKernelGGL(k_gram_close, dim3(a.c.n_rows, lv.n_states), dim3(256), 0, s, a, l);
     }
-    if (w) hipLaunchKernelGGL(k_gram_trace_w, dim3(a.c.n_rows), dim3(64), 0, s, a, *w);
-    else hipLaunchKernelGGL(k_gram_trace, dim3(a.c.n_rows), dim3(64), 0, s, a);
+    if (w) {
+        SR_LAUNCH_POINT(s, "k_gram_trace_w");
+        hipLaunchKernelGGL(k_gram_trace_w, dim3(a.c.n_rows), dim3(64), 0, s, a, *w);
+    } else {
+        SR_LAUNCH_POINT(s, "k_gram_trace");
+        hipLaunchKernelGGL(k_gram_trace, dim3(a.c.n_rows), dim3(64), 0, s, a);
+    }
 }
 const char *gram_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_gram_words, "k_gram_words"}}, bytes); }
 

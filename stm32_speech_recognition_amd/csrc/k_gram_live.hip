@@ -494,13 +494,20 @@ void launch_gram_live(const GramLiveArgs &a, const GramCosts *w, hipStream_t s)
 {
     if (!a.c.C) return;
     const size_t lds = spot_lds_bytes(a.c.tpl_len);
+    SR_LAUNCH_POINT(s, "k_gram_live_init");
     hipLaunchKernelGGL(k_gram_live_init, dim3(a.c.C, a.c.max_words + 1u), dim3(256), 0, s, a);
     const uint32_t groups = (a.c.C + kSpotWaves - 1) / kSpotWaves;
     for (uint32_t l = 1; l <= a.c.max_words; l++) {
         const GramLevel &lv = a.lv[l - 1];
         if (!lv.n_items) continue;  // nothing can end here: the level stays unreachable
-        if (w) hipLaunchKernelGGL(k_gram_live_words_w, dim3(lv.n_items, groups), dim3(64 * kSpotWaves), lds, s, a, *w, l);
-        else hipLaunchKernelGGL(k_gram_live_words, dim3(lv.n_items, groups), dim3(64 * kSpotWaves), lds, s, a, l);
+        if (w) {
+            SR_LAUNCH_POINT(s, "k_gram_live_words_w");
+            hipLaunchKernelGGL(k_gram_live_words_w, dim3(lv.n_items, groups), dim3(64 * kSpotWaves), lds, s, a, *w, l);
+        } else {
+            SR_LAUNCH_POINT(s, "k_gram_live_words");
+            hipLaunchKernelGGL(k_gram_live_words, dim3(lv.n_items, groups), dim3(64 * kSpotWaves), lds, s, a, l);
+        }
+        SR_LAUNCH_POINT(s, "k_gram_live_close");
         hipLaunchKernelGGL(k_gram_live_close, dim3(a.c.C, lv.n_states), dim3(256), 0, s, a, l);
     }
     launch_gram_live_trace(a, w, s);
@@ -508,8 +515,13 @@ void launch_gram_live(const GramLiveArgs &a, const GramCosts *w, hipStream_t s)
 void launch_gram_live_trace(const GramLiveArgs &a, const GramCosts *w, hipStream_t s)
 {
     if (!a.c.C) return;
-    if (w) hipLaunchKernelGGL(k_gram_live_trace_w, dim3(a.c.C), dim3(64), 0, s, a, *w);
-    else hipLaunchKernelGGL(k_gram_live_trace, dim3(a.c.C), dim3(64), 0, s, a);
+    if (w) {
+        SR_LAUNCH_POINT(s, "k_gram_live_trace_w");
+        hipLaunchKernelGGL(k_gram_live_trace_w, dim3(a.c.C), dim3(64), 0, s, a, *w);
+    } else {
+        SR_LAUNCH_POINT(s, "k_gram_live_trace");
+        hipLaunchKernelGGL(k_gram_live_trace, dim3(a.c.C), dim3(64), 0, s, a);
+    }
 }
 const char *gram_live_allow_lds(uint32_t bytes)
 {

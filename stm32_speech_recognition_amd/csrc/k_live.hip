@@ -228,6 +228,7 @@ __global__ void __launch_bounds__(256) k_live_records(const LiveRecArgs a)
 void launch_live_append(const LiveArgs &a, hipStream_t s)
 {
     if (!a.C) return;
+    SR_LAUNCH_POINT(s, "k_live_append");
     hipLaunchKernelGGL(k_live_append, dim3(a.C), dim3(kLiveAppendThreads), 0, s, a);
 }
 
@@ -235,8 +236,13 @@ template <int FL>
 static void launch_scan_fl(const LiveArgs &a, bool sad, hipStream_t s)
 {
     const dim3 grid((a.C + kLiveWaves - 1) / kLiveWaves), block(64 * kLiveWaves);
-    if (sad) hipLaunchKernelGGL((k_live_scan<FL, FL / 2, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_live_scan<FL, FL / 2, false>), grid, block, 0, s, a);
+    if (sad) {
+        SR_LAUNCH_POINT(s, "k_live_scan");
+        hipLaunchKernelGGL((k_live_scan<FL, FL / 2, true>), grid, block, 0, s, a);
+    } else {
+        SR_LAUNCH_POINT(s, "k_live_scan");
+        hipLaunchKernelGGL((k_live_scan<FL, FL / 2, false>), grid, block, 0, s, a);
+    }
 }
 
 void launch_live_scan(const LiveArgs &a, bool sad, hipStream_t s)
@@ -251,12 +257,14 @@ void launch_live_scan(const LiveArgs &a, bool sad, hipStream_t s)
     case 512: launch_scan_fl<512>(a, sad, s); break;
     default: return;  // sr_create accepts only the framings of vad_framing_supported
     }
+    SR_LAUNCH_POINT(s, "k_live_compact");
     hipLaunchKernelGGL(k_live_compact, dim3(1), dim3(kLiveCompactThreads), 0, s, a);
 }
 
 void launch_live_records(const LiveRecArgs &a, uint32_t n, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_live_records");
     hipLaunchKernelGGL(k_live_records, dim3(n), dim3(256), 0, s, a);
 }
 

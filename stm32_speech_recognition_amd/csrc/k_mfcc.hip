@@ -743,15 +743,18 @@ void launch_mfcc(const MfccArgs &a, const MfccMagTab &tab, hipStream_t s)
     }
     if (a.small_tiles == 2) {  // a.tiles counts tiles of mfcc_frames_per_tile_small(frame_len, 1) frames
         const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWaveSmall) * sizeof(uint32_t);
+        SR_LAUNCH_POINT(s, "k_mfcc");
         hipLaunchKernelGGL(k_mfcc<kFramesPerWaveSmall>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
         return;
     }
     if (a.small_tiles == 1) {  // ... of mfcc_frames_per_tile_small(frame_len, 0) frames
         const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWaveMid) * sizeof(uint32_t);
+        SR_LAUNCH_POINT(s, "k_mfcc");
         hipLaunchKernelGGL(k_mfcc<kFramesPerWaveMid>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
         return;
     }
     const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFramesPerWave) * sizeof(uint32_t);
+    SR_LAUNCH_POINT(s, "k_mfcc");
     hipLaunchKernelGGL(k_mfcc<kFramesPerWave>, dim3(grid), dim3(64 * kMfccWaves), lds, s, mfcc_tab_args(a, tab));
 }
 
@@ -759,6 +762,7 @@ template <int kFPW, int kKind>
 static void launch_mfcc_feat_kind(const MfccArgs &a, const MfccMagTab &tab, uint32_t *feat, uint32_t grid, hipStream_t s)
 {
     const size_t lds = (size_t)kMfccWaves * mfcc_wave_lds_words(kFPW) * sizeof(uint32_t);
+    SR_LAUNCH_POINT(s, "k_mfcc");
     hipLaunchKernelGGL((k_mfcc<kFPW, MfccTabArgs<MfccFeatArgs<kKind>>>), dim3(grid), dim3(64 * kMfccWaves), lds, s,
                        mfcc_tab_args(mfcc_feat_args<kKind>(a, feat), tab));
 }

@@ -453,12 +453,14 @@ int mfcc_ext_occupancy(int *per_cu)
 void launch_mfcc_ext(const MfccArgs &a, uint32_t grid, hipStream_t s)
 {
     const size_t lds = (size_t)ext::kWaves * ext::kWaveWords * sizeof(uint32_t);
+    SR_LAUNCH_POINT(s, "k_mfcc_ext");
     hipLaunchKernelGGL(k_mfcc_ext<MfccArgs>, dim3(grid), dim3(64 * ext::kWaves), lds, s, a);
 }
 template <int kKind>
 static void launch_mfcc_ext_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
 {
     const size_t lds = (size_t)ext::kWaves * ext::kWaveWords * sizeof(uint32_t);
+    SR_LAUNCH_POINT(s, "k_mfcc_ext");
     hipLaunchKernelGGL(k_mfcc_ext<MfccFeatArgs<kKind>>, dim3(grid), dim3(64 * ext::kWaves), lds, s, mfcc_feat_args<kKind>(a, feat));
 }
 void launch_mfcc_ext_features(const MfccArgs &a, int kind, uint32_t *feat, uint32_t grid, hipStream_t s)

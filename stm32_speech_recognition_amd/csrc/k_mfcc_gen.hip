@@ -195,11 +195,13 @@ void launch_mfcc_gen(const MfccArgs &a, hipStream_t s)
     if (!n) return;
     const uint64_t wgs = (n + kGenWaves - 1) / kGenWaves;
     const uint32_t grid = (uint32_t)(wgs < 8192 ? wgs : 8192);
+    SR_LAUNCH_POINT(s, "k_mfcc_gen");
     hipLaunchKernelGGL(k_mfcc_gen<MfccArgs>, dim3(grid), dim3(64 * kGenWaves), (size_t)kGenWaves * kGenWaveWords * sizeof(uint32_t), s, a);
 }
 template <int kKind>
 static void launch_mfcc_gen_feat_kind(const MfccArgs &a, uint32_t *feat, uint32_t grid, hipStream_t s)
 {
+    SR_LAUNCH_POINT(s, "k_mfcc_gen");
     hipLaunchKernelGGL(k_mfcc_gen<MfccFeatArgs<kKind>>, dim3(grid), dim3(64 * kGenWaves), (size_t)kGenWaves * kGenWaveWords * sizeof(uint32_t),
                        s, mfcc_feat_args<kKind>(a, feat));
 }

@@ -2,6 +2,13 @@
 // gfx950 (MI355X, CDNA4) only; wave = 64 lanes; no MFMA (the path has no dense contraction), integer VALU + LDS.
 // Every kernel reproduces the reference's integer arithmetic bit for bit; cited lines are relative to the reference tree.
 #include "sr_dtw_dev.h"
+#ifdef SR_TESTING
+#include <algorithm>
+#include <cstdio>
+#include <mutex>
+#include <string>
+#include <vector>
+#endif
 
 namespace sr {
 
@@ -35,6 +42,7 @@ void launch_delta_mfcc(const int16_t *mfcc, const sr_vad_rec *vad, const uint32_
 {
     const uint64_t n = (uint64_t)B * max_frames * n_coef;
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_delta_mfcc");
     hipLaunchKernelGGL(k_delta_mfcc, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, mfcc, vad, frames, B, max_frames, n_coef, delta);
 }
 
@@ -62,6 +70,7 @@ void launch_unpack12(const void *packed, uint64_t row_bytes, uint16_t *out, uint
     const uint32_t groups = (buf_len + 7) / 8;
     const uint64_t n = (uint64_t)B * groups;
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_unpack12");
     hipLaunchKernelGGL(k_unpack12, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const uint32_t *)packed, row_bytes / 4, out,
                        out_stride, groups, B);
 }
@@ -90,6 +99,7 @@ __global__ void k_math_diag(const uint32_t *in, uint32_t *out, uint32_t n, const
 void launch_math_diag(const uint32_t *in, uint32_t *out, uint32_t n, const DevTables &t, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_math_diag");
     hipLaunchKernelGGL(k_math_diag, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, t.log_thr);
 }
 
@@ -134,11 +144,13 @@ __global__ void __launch_bounds__(256) k_mag_fast_sweep(uint32_t n_max, unsigned
 }
 void launch_mag_fast_sweep(uint32_t n_max, unsigned long long *bad, uint32_t *first_bad, hipStream_t s)
 {
+    SR_LAUNCH_POINT(s, "k_mag_fast_sweep");
     hipLaunchKernelGGL(k_mag_fast_sweep, dim3(1024), dim3(256), 0, s, n_max, bad, first_bad);
 }
 void launch_mel_term_sweep(uint32_t tri_lo, uint32_t n_tri, uint32_t e_max, unsigned long long *bad, hipStream_t s)
 {
     if (!n_tri) return;
+    SR_LAUNCH_POINT(s, "k_mel_term_sweep");
     hipLaunchKernelGGL(k_mel_term_sweep, dim3(256, n_tri), dim3(256), 0, s, tri_lo, e_max, bad);
 }
 
@@ -155,6 +167,7 @@ __global__ void k_get_dis(const int16_t *pa, const int16_t *pb, uint32_t *out, u
 void launch_get_dis(const int16_t *pa, const int16_t *pb, uint32_t *out, uint32_t n, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_get_dis");
     hipLaunchKernelGGL(k_get_dis, dim3((n + 63) / 64), dim3(64), 0, s, pa, pb, out, n);
 }
 
@@ -167,6 +180,7 @@ __global__ void k_dtw_limit(const uint16_t *xy, uint8_t *out, uint32_t n, int X1
 void launch_dtw_limit(const uint16_t *xy, uint8_t *out, uint32_t n, int X1, int X2, int in_n, int mdl_n, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_dtw_limit");
     hipLaunchKernelGGL(k_dtw_limit, dim3((n + 63) / 64), dim3(64), 0, s, xy, out, n, X1, X2, in_n, mdl_n);
 }
 
@@ -202,5 +216,91 @@ int launch_lds_poison(uint32_t seed, hipStream_t s)
     hipLaunchKernelGGL(k_lds_poison, dim3((uint32_t)(4 * n_cu)), dim3(256), (size_t)max_lds, s, seed, (uint32_t)max_lds / 4u, 40000u);
     return max_lds;
 }
+
+#ifdef SR_TESTING
+// ------------------------------------------------------------------------------------------------
+// launch points (sr_device.h; the testing build only).  k_lds_poison_low is k_lds_poison with the LOW pattern: words 0..7,
+// which read as a u32 cost, an s16 pair, an index or either half of a u64 key are small and valid-looking.  k_lds_probe
+// copies the first `words` words of its LDS out WITHOUT writing them first: what the CU's previous tenant left.  It takes the
+// whole LDS of a CU as k_lds_poison does, so its allocation starts at the CU's first byte whichever CU it lands on.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_lds_poison_low(uint32_t seed, uint32_t words, uint32_t spin)
+{
+    extern __shared__ uint32_t poison[];
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) poison[i] = (seed ^ (i * 2654435761u)) & 7u;
+    __syncthreads();
+    uint32_t acc = 0;
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) acc += poison[i];  // keeps the stores alive
+    const uint64_t t0 = __builtin_readcyclecounter();
+    while (__builtin_readcyclecounter() - t0 < spin) {}
+    if (acc == 0x12345678u && seed == 0xFFFFFFFFu) poison[0] = acc;
+}
+__global__ void __launch_bounds__(256) k_lds_probe(uint32_t words, uint32_t *out)
+{
+    extern __shared__ uint32_t probe[];
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) out[(size_t)blockIdx.x * words + i] = probe[i];
+}
+
+static std::mutex g_lp_mutex;
+static uint64_t g_lp_count;
+static std::vector<std::string> g_lp_names;
+
+// all of a CU's LDS for one workgroup of kernel `fn`, as launch_lds_poison arranges it; 0 on failure
+static int whole_cu_lds(const void *fn, int *n_cu)
+{
+    int dev = 0, max_lds = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || *n_cu <= 0) return 0;
+    if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || max_lds <= 0) return 0;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess) {
+        (void)hipGetLastError();
+        max_lds = 64 * 1024;
+    }
+    return max_lds;
+}
+
+void launch_point(hipStream_t s, const char *kernel)
+{
+    const uint64_t v = (uint64_t)dev_hook(kHookLdsPoisonLaunches);
+    if (!v) return;
+    const uint32_t seed = (uint32_t)v, pattern = (uint32_t)(v >> 32) & 3u;
+    if (pattern == kPoisonLow) {
+        int n_cu = 0;
+        const int max_lds = whole_cu_lds((const void *)k_lds_poison_low, &n_cu);
+        if (!max_lds) return;
+        hipLaunchKernelGGL(k_lds_poison_low, dim3((uint32_t)(4 * n_cu)), dim3(256), (size_t)max_lds, s, seed, (uint32_t)max_lds / 4u, 40000u);
+    } else if (launch_lds_poison(seed, s) < 0) {
+        return;
+    }
+    std::lock_guard<std::mutex> lock(g_lp_mutex);
+    g_lp_count++;
+    if (std::find(g_lp_names.begin(), g_lp_names.end(), kernel) == g_lp_names.end()) g_lp_names.emplace_back(kernel);
+}
+void launch_points_reset()
+{
+    std::lock_guard<std::mutex> lock(g_lp_mutex);
+    g_lp_count = 0;
+    g_lp_names.clear();
+}
+uint64_t launch_points_seen(char *names, size_t names_cap)
+{
+    std::lock_guard<std::mutex> lock(g_lp_mutex);
+    if (names && names_cap) {
+        std::string all;
+        for (const std::string &n : g_lp_names) all += (all.empty() ? "" : ",") + n;
+        std::snprintf(names, names_cap, "%s", all.c_str());
+    }
+    return g_lp_count;
+}
+int launch_lds_probe(uint32_t words, uint32_t *d_out, hipStream_t s)
+{
+    int n_cu = 0;
+    const int max_lds = whole_cu_lds((const void *)k_lds_probe, &n_cu);
+    if (!max_lds || (size_t)words * 4 > (size_t)max_lds) return -1;
+    SR_LAUNCH_POINT(s, "k_lds_probe");
+    hipLaunchKernelGGL(k_lds_probe, dim3((uint32_t)n_cu), dim3(256), (size_t)max_lds, s, words, d_out);
+    return n_cu;
+}
+#endif
 
 }  // namespace sr

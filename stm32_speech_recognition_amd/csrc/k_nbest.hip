@@ -132,8 +132,13 @@ void launch_nbest(const NbestArgs &a, hipStream_t s)
 {
     if (!a.n_rows) return;
     const dim3 grid((a.n_rows + 3) / 4), block(256);
-    if (a.n_words <= (uint32_t)(SR_NBEST_REG_LIMIT)) hipLaunchKernelGGL(k_nbest<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(k_nbest<false>, grid, block, 0, s, a);
+    if (a.n_words <= (uint32_t)(SR_NBEST_REG_LIMIT)) {
+        SR_LAUNCH_POINT(s, "k_nbest");
+        hipLaunchKernelGGL(k_nbest<true>, grid, block, 0, s, a);
+    } else {
+        SR_LAUNCH_POINT(s, "k_nbest");
+        hipLaunchKernelGGL(k_nbest<false>, grid, block, 0, s, a);
+    }
 }
 
 }  // namespace sr

@@ -214,13 +214,17 @@ void launch_onepass(const OnePassArgs &a, const OnePassBlock *blocks, uint32_t n
 {
     if (!a.n_rows || !a.K) return;
     const size_t lds = spot_lds_bytes(a.tpl_len);
+    SR_LAUNCH_POINT(s, "k_onepass_init");
     hipLaunchKernelGGL(k_onepass_init, dim3(a.n_rows), dim3(256), 0, s, a);
     const dim3 grid(a.K, (a.n_rows + kSpotWaves - 1) / kSpotWaves);
     for (uint32_t b = 0; b < n_blocks; b++) {
         const OnePassBlock &o = blocks[b];
+        SR_LAUNCH_POINT(s, "k_onepass_words");
         hipLaunchKernelGGL(k_onepass_words, grid, dim3(64 * kSpotWaves), lds, s, a, b ? o.c0_prev + 1u : 0u, o.c0, o.cN);
+        SR_LAUNCH_POINT(s, "k_onepass_close");
         hipLaunchKernelGGL(k_onepass_close, dim3(a.n_rows), dim3(256), 0, s, a, o.c0, o.cN);
     }
+    SR_LAUNCH_POINT(s, "k_onepass_trace");
     hipLaunchKernelGGL(k_onepass_trace, dim3(a.n_rows), dim3(64), 0, s, a);
 }
 const char *onepass_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_onepass_words, "k_onepass_words"}}, bytes); }

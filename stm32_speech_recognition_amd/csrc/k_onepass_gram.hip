@@ -405,19 +405,35 @@ void launch_onepass_gram(const OnePassGramArgs &a, const GramCosts *w, const One
 {
     if (!a.o.n_rows) return;
     const size_t lds = spot_lds_bytes(a.o.tpl_len);
-    if (a.n_keep_states) hipLaunchKernelGGL(k_onepass_gram_init, dim3(a.o.n_rows, a.n_keep_states), dim3(256), 0, s, a);
+    if (a.n_keep_states) {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_init");
+        hipLaunchKernelGGL(k_onepass_gram_init, dim3(a.o.n_rows, a.n_keep_states), dim3(256), 0, s, a);
+    }
     const dim3 grid(a.n_keep_items, (a.o.n_rows + kSpotWaves - 1) / kSpotWaves);
     for (uint32_t b = 0; b < n_blocks; b++) {
         const OnePassBlock &o = blocks[b];
         const uint32_t xs = b ? o.c0_prev + 1u : 0u;
         if (a.n_keep_items) {
-            if (w) hipLaunchKernelGGL(k_onepass_gram_words_w, grid, dim3(64 * kSpotWaves), lds, s, a, *w, xs, o.c0, o.cN);
-            else hipLaunchKernelGGL(k_onepass_gram_words, grid, dim3(64 * kSpotWaves), lds, s, a, xs, o.c0, o.cN);
+            if (w) {
+                SR_LAUNCH_POINT(s, "k_onepass_gram_words_w");
+                hipLaunchKernelGGL(k_onepass_gram_words_w, grid, dim3(64 * kSpotWaves), lds, s, a, *w, xs, o.c0, o.cN);
+            } else {
+                SR_LAUNCH_POINT(s, "k_onepass_gram_words");
+                hipLaunchKernelGGL(k_onepass_gram_words, grid, dim3(64 * kSpotWaves), lds, s, a, xs, o.c0, o.cN);
+            }
         }
-        if (a.n_keep_states) hipLaunchKernelGGL(k_onepass_gram_close, dim3(a.o.n_rows, a.n_keep_states), dim3(256), 0, s, a, o.c0, o.cN);
+        if (a.n_keep_states) {
+            SR_LAUNCH_POINT(s, "k_onepass_gram_close");
+            hipLaunchKernelGGL(k_onepass_gram_close, dim3(a.o.n_rows, a.n_keep_states), dim3(256), 0, s, a, o.c0, o.cN);
+        }
     }
-    if (w) hipLaunchKernelGGL(k_onepass_gram_trace_w, dim3(a.o.n_rows), dim3(64), 0, s, a, *w);
-    else hipLaunchKernelGGL(k_onepass_gram_trace, dim3(a.o.n_rows), dim3(64), 0, s, a);
+    if (w) {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_trace_w");
+        hipLaunchKernelGGL(k_onepass_gram_trace_w, dim3(a.o.n_rows), dim3(64), 0, s, a, *w);
+    } else {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_trace");
+        hipLaunchKernelGGL(k_onepass_gram_trace, dim3(a.o.n_rows), dim3(64), 0, s, a);
+    }
 }
 const char *onepass_gram_allow_lds(uint32_t bytes)
 {

@@ -233,15 +233,20 @@ void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_
     const size_t lds = spot_lds_bytes(a.tpl_len);
     const dim3 grid(a.K, (a.C + kSpotWaves - 1) / kSpotWaves);
     for (uint32_t b = 0; b < n_blocks; b++) {
+        SR_LAUNCH_POINT(s, "k_onepass_live_words");
         hipLaunchKernelGGL(k_onepass_live_words, grid, dim3(64 * kSpotWaves), lds, s, a, b);
+        SR_LAUNCH_POINT(s, "k_onepass_live_close");
         hipLaunchKernelGGL(k_onepass_live_close, dim3(a.C), dim3(256), 0, s, a, b);
     }
+    SR_LAUNCH_POINT(s, "k_onepass_live_trace");
     hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
 }
 void launch_onepass_live_end(const OnePassLiveArgs &a, hipStream_t s)
 {
     if (!a.C) return;
+    SR_LAUNCH_POINT(s, "k_onepass_live_trace");
     hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
+    SR_LAUNCH_POINT(s, "k_onepass_live_wipe");
     hipLaunchKernelGGL(k_onepass_live_wipe, dim3(a.C), dim3(256), 0, s, a);
 }
 const char *onepass_live_allow_lds(uint32_t bytes)

@@ -26,6 +26,7 @@ void launch_rescore_mark(const RescoreMarkArgs &a, hipStream_t s)
 {
     const uint64_t n = (uint64_t)a.n_rows * a.n_best;
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_rescore_mark");
     hipLaunchKernelGGL(k_rescore_mark, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, a);
 }
 

@@ -123,6 +123,7 @@ void launch_span(const SpanArgs &a, hipStream_t s)
         sa.in_frames = a.in_frames + (size_t)r0 * a.frames_stride;
         sa.words = a.words + s0;
         sa.scores = a.scores + (size_t)s0 * a.K;
+        SR_LAUNCH_POINT(s, "k_span_words");
         hipLaunchKernelGGL(k_span_words, dim3(a.K, (sa.n_spans + kSpotWaves - 1) / kSpotWaves), dim3(64 * kSpotWaves), lds, s, sa);
     }
 }

@@ -194,10 +194,12 @@ void launch_spot(const SpotArgs &a, hipStream_t s)
         sa.scores = a.scores ? a.scores + (size_t)r0 * a.n_win * a.K : nullptr;
         sa.part = a.part ? a.part + (size_t)r0 * a.n_chunks * a.K : nullptr;
         const dim3 grid(a.K, sa.n_rows, (a.n_chunks + kSpotWaves - 1) / kSpotWaves);
+        SR_LAUNCH_POINT(s, "k_spot");
         hipLaunchKernelGGL(k_spot, grid, dim3(64 * kSpotWaves), lds, s, sa);
     }
     if (a.split) {
         const uint64_t n = (uint64_t)a.n_rows * a.n_win * a.K, blocks = (n + 255) / 256;
+        SR_LAUNCH_POINT(s, "k_spot_finish");
         hipLaunchKernelGGL(k_spot_finish, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, s, a);
     }
 }

@@ -205,6 +205,7 @@ void launch_spot_live(const SpotLiveArgs &a, hipStream_t s)
 {
     if (!a.C || !a.K) return;
     const dim3 grid(a.K, (a.C + kSpotWaves - 1) / kSpotWaves);
+    SR_LAUNCH_POINT(s, "k_spot_live");
     hipLaunchKernelGGL(k_spot_live, grid, dim3(64 * kSpotWaves), spot_lds_bytes(a.tpl_len), s, a);
 }
 void launch_spot_live_flush(const SpotLiveFlush *list, uint32_t n_list, uint8_t *state, uint64_t chan_stride, uint32_t K, uint32_t tpl_len,
@@ -212,6 +213,7 @@ void launch_spot_live_flush(const SpotLiveFlush *list, uint32_t n_list, uint8_t 
 {
     if (!n_list || !K) return;
     const uint64_t blocks = ((uint64_t)n_list * K + 255) / 256;
+    SR_LAUNCH_POINT(s, "k_spot_live_flush");
     hipLaunchKernelGGL(k_spot_live_flush, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, s, list, n_list, state, chan_stride, K,
                        tpl_len, hits);
 }
@@ -219,11 +221,13 @@ void launch_spot_live_stage(const SpotLivePcmArgs &a, hipStream_t s)
 {
     if (!a.C || !a.max_row) return;
     const uint32_t bx = (a.max_row + 255) / 256;
+    SR_LAUNCH_POINT(s, "k_spot_live_stage");
     hipLaunchKernelGGL(k_spot_live_stage, dim3(bx < 64u ? bx : 64u, a.C), dim3(256), 0, s, a);
 }
 void launch_spot_live_keep(const SpotLivePcmArgs &a, hipStream_t s)
 {
     if (!a.C || !a.max_row) return;
+    SR_LAUNCH_POINT(s, "k_spot_live_keep");
     hipLaunchKernelGGL(k_spot_live_keep, dim3(a.C), dim3(256), 0, s, a);
 }
 const char *spot_live_allow_lds(uint32_t bytes) { return allow_dynamic_lds({{(const void *)k_spot_live, "k_spot_live"}}, bytes); }

@@ -44,6 +44,7 @@ void launch_select_segment(const sr_vad_rec *in, sr_vad_rec *out, uint32_t B, ui
                            uint32_t frame_len, uint32_t hop, hipStream_t s)
 {
     if (!B) return;
+    SR_LAUNCH_POINT(s, "k_select_segment");
     hipLaunchKernelGGL(k_select_segment, dim3((B + 255) / 256), dim3(256), 0, s, in, out, B, seg_idx, max_frames,
                        frame_len, hop);
 }
@@ -64,11 +65,21 @@ void launch_vad(const VadArgs &a, hipStream_t s)
         return;
     }
     if (a.frame_len == 320) {
-        if (own_thresholds) hipLaunchKernelGGL((k_vad<320, 160, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_vad<320, 160, false>), grid, block, 0, s, a);
+        if (own_thresholds) {
+            SR_LAUNCH_POINT(s, "k_vad");
+            hipLaunchKernelGGL((k_vad<320, 160, true>), grid, block, 0, s, a);
+        } else {
+            SR_LAUNCH_POINT(s, "k_vad");
+            hipLaunchKernelGGL((k_vad<320, 160, false>), grid, block, 0, s, a);
+        }
     } else {
-        if (own_thresholds) hipLaunchKernelGGL((k_vad<160, 80, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_vad<160, 80, false>), grid, block, 0, s, a);
+        if (own_thresholds) {
+            SR_LAUNCH_POINT(s, "k_vad");
+            hipLaunchKernelGGL((k_vad<160, 80, true>), grid, block, 0, s, a);
+        } else {
+            SR_LAUNCH_POINT(s, "k_vad");
+            hipLaunchKernelGGL((k_vad<160, 80, false>), grid, block, 0, s, a);
+        }
     }
 }
 

@@ -15,8 +15,13 @@ template <int FL>
 static void launch_one(const VadArgs &a, hipStream_t s)
 {
     const dim3 grid((a.B + kVadWaves - 1) / kVadWaves), block(64 * kVadWaves);
-    if (a.atap_in == nullptr) hipLaunchKernelGGL((k_vad<FL, FL / 2, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_vad<FL, FL / 2, false>), grid, block, 0, s, a);
+    if (a.atap_in == nullptr) {
+        SR_LAUNCH_POINT(s, "k_vad");
+        hipLaunchKernelGGL((k_vad<FL, FL / 2, true>), grid, block, 0, s, a);
+    } else {
+        SR_LAUNCH_POINT(s, "k_vad");
+        hipLaunchKernelGGL((k_vad<FL, FL / 2, false>), grid, block, 0, s, a);
+    }
 }
 
 void launch_vad_other(const VadArgs &a, hipStream_t s)

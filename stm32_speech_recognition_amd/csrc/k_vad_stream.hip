@@ -264,8 +264,13 @@ template <int FL>
 static void launch_tiles_fl(const VadStreamArgs &a, bool sad, hipStream_t s)
 {
     const dim3 grid((uint32_t)((uint64_t)a.B * a.nt)), block(64);
-    if (sad) hipLaunchKernelGGL((k_stream_tiles<FL, FL / 2, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_stream_tiles<FL, FL / 2, false>), grid, block, 0, s, a);
+    if (sad) {
+        SR_LAUNCH_POINT(s, "k_stream_tiles");
+        hipLaunchKernelGGL((k_stream_tiles<FL, FL / 2, true>), grid, block, 0, s, a);
+    } else {
+        SR_LAUNCH_POINT(s, "k_stream_tiles");
+        hipLaunchKernelGGL((k_stream_tiles<FL, FL / 2, false>), grid, block, 0, s, a);
+    }
 }
 
 void launch_vad_stream(const VadStreamArgs &a, bool sad, hipStream_t s)
@@ -280,14 +285,17 @@ void launch_vad_stream(const VadStreamArgs &a, bool sad, hipStream_t s)
     case 512: launch_tiles_fl<512>(a, sad, s); break;
     default: return;  // sr_create accepts only the framings of vad_framing_supported
     }
+    SR_LAUNCH_POINT(s, "k_stream_scan");
     hipLaunchKernelGGL(k_stream_scan, dim3(1), dim3(kScanThreads), 0, s, a);
     const uint64_t slots = (uint64_t)a.B * a.nt;
+    SR_LAUNCH_POINT(s, "k_stream_emit");
     hipLaunchKernelGGL(k_stream_emit, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, a);
 }
 
 void launch_stream_records(const StreamRecArgs &a, uint32_t n, hipStream_t s)
 {
     if (!n) return;
+    SR_LAUNCH_POINT(s, "k_stream_records");
     hipLaunchKernelGGL(k_stream_records, dim3(n), dim3(256), 0, s, a);
 }
 

@@ -258,8 +258,13 @@ template <int FL>
 static void launch_wide(const VadArgs &a, hipStream_t s)
 {
     const dim3 grid(a.B), block(64 * wide::kWaves);
-    if (a.atap_in == nullptr) hipLaunchKernelGGL((k_vad_wide<FL, FL / 2, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_vad_wide<FL, FL / 2, false>), grid, block, 0, s, a);
+    if (a.atap_in == nullptr) {
+        SR_LAUNCH_POINT(s, "k_vad_wide");
+        hipLaunchKernelGGL((k_vad_wide<FL, FL / 2, true>), grid, block, 0, s, a);
+    } else {
+        SR_LAUNCH_POINT(s, "k_vad_wide");
+        hipLaunchKernelGGL((k_vad_wide<FL, FL / 2, false>), grid, block, 0, s, a);
+    }
 }
 
 // every framing vad_framing_supported accepts

@@ -40,12 +40,31 @@ enum DevHook {
     kHookOnePassGramPruneOff,  // "onepass_gram_prune_off": one-pass grammar decoding keeps every item and every state (no static pruning; read per call and by sr_onepass_grammar_plan)
     kHookLiveOrigin,      // "live_origin": samples a fresh sr_live channel behaves as having consumed before (a multiple of hop; read at open / end)
     kHookSpotLiveOrigin,  // "spot_live_origin": frames a fresh sr_spot_live channel stands at (up to 0xFFFF0000; read at open / end)
+    kHookLdsPoisonLaunches,  // "lds_poison_launches": k_lds_poison in front of every kernel launch (SR_LAUNCH_POINT): bits 0..31 seed, 32..33 pattern
     kHookCount
 };
 #ifdef SR_TESTING
 int64_t dev_hook(DevHook h);
 #else
 constexpr int64_t dev_hook(DevHook) { return 0; }
+#endif
+
+// Launch points: SR_LAUNCH_POINT(stream, "k_name") stands immediately in front of EVERY kernel launch of the library
+// (tests/test_stale_state.py scans the sources for one that has none).  The product library compiles it to nothing.  In the
+// -DSR_TESTING build it calls launch_point (k_misc.hip): while the hook "lds_poison_launches" is non-zero, the LDS of every CU is
+// overwritten on that stream before the kernel runs -- between the launches of ONE call too, where no caller can reach -- and
+// the kernel's name is recorded.  Patterns (bits 32..33 of the hook): kPoisonHigh is sr_lds_poison's, every word >= 2^31 (loses
+// every minimum: "unreachable"); kPoisonLow is (seed ^ i * 2654435761) & 7, a small, valid-looking cost, index or s16 pair that
+// WINS every minimum it enters.
+constexpr uint32_t kPoisonHigh = 0, kPoisonLow = 1;
+#ifdef SR_TESTING
+void launch_point(hipStream_t s, const char *kernel);
+void launch_points_reset();                                   // counter and names back to nothing (sr_dev_hook, when the hook is set)
+uint64_t launch_points_seen(char *names, size_t names_cap);   // poison launches since then; the distinct names, comma-separated
+int launch_lds_probe(uint32_t words, uint32_t *d_out, hipStream_t s);  // returns the workgroups launched (one per CU), < 0 on failure
+#define SR_LAUNCH_POINT(stream, name) ::sr::launch_point((stream), (name))
+#else
+#define SR_LAUNCH_POINT(stream, name) ((void)0)
 #endif
 
 // device-resident constant tables (see sr_tables.h)

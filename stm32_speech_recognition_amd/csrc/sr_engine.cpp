@@ -24,7 +24,7 @@ static const char *const kHookNames[kHookCount] = {"dtw_u", "dtw_tie_g", "dtw_kc
                                                    "mag_cheap_off", "mag_table_off", "stream_tile_frames", "spot_chunk_cols",
                                                    "align_pairs", "align_marks_global", "chain_chunk_cols", "chain_rows", "span_groups",
                                                    "cluster_pairs", "forced_prune_off", "onepass_block", "onepass_rows", "onepass_gram_prune_off", "live_origin",
-                                                   "spot_live_origin"};
+                                                   "spot_live_origin", "lds_poison_launches"};
 #endif
 }  // namespace sr
 
@@ -138,6 +138,10 @@ int sr_dev_hook(const char *name, int64_t value)
 #ifdef SR_TESTING
     for (int i = 0; i < kHookCount; i++)
         if (std::strcmp(name, kHookNames[i]) == 0) {
+            if (i == kHookLdsPoisonLaunches) {  // seed | pattern << 32; setting it starts the count and the names anew
+                if (value < 0 || (uint64_t)value >> 32 > kPoisonLow) return fail(SR_ERR_BAD_ARG, "lds_poison_launches: bits 0..31 seed, bits 32..33 pattern 0 (high) or 1 (low)");
+                launch_points_reset();
+            }
             g_hooks[i].store(value, std::memory_order_relaxed);
             return SR_OK;
         }

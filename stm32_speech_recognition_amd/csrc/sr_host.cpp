@@ -676,6 +676,36 @@ int sr_lds_poison(sr_engine *h, uint32_t seed, void *stream, uint32_t *bytes_per
     return SR_OK;
 }
 
+// testing build only (launch points, sr_device.h): the poison launches issued through launch points since the hook
+// "lds_poison_launches" was last set, and the distinct kernel names they stood in front of, comma-separated
+int sr_lds_launch_points(uint64_t *count, char *names, uint32_t names_cap)
+{
+#ifdef SR_TESTING
+    if (!count) return fail(SR_ERR_BAD_ARG, "null argument");
+    *count = launch_points_seen(names, names_cap);
+    return SR_OK;
+#else
+    (void)count, (void)names, (void)names_cap;
+    return fail(SR_ERR_BAD_ARG, "sr_lds_launch_points: launch points are not compiled into the product library");
+#endif
+}
+
+// testing build only: what the first `words` words of every CU's LDS hold (k_lds_probe, launched through a launch point)
+int sr_lds_probe(sr_engine *h, uint32_t words, uint32_t *d_out, void *stream)
+{
+#ifdef SR_TESTING
+    if (!h || !d_out || !words || words > 4096u) return fail(SR_ERR_BAD_ARG, "sr_lds_probe: null argument, or words outside 1..4096");
+    ENTER_DEVICE(h);
+    const int n = launch_lds_probe(words, d_out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    if (n < 0) return fail(SR_ERR_HIP, "sr_lds_probe: device attribute query failed");
+    return SR_OK;
+#else
+    (void)h, (void)words, (void)d_out, (void)stream;
+    return fail(SR_ERR_BAD_ARG, "sr_lds_probe: launch points are not compiled into the product library");
+#endif
+}
+
 // diagnostics: k_mfcc's fused filterbank term against the reference's expression, see k_mel_term_sweep
 int sr_mel_term_sweep(sr_engine *h, uint32_t tri_lo, uint32_t tri_hi, uint32_t e_max, uint64_t *mismatches)
 {

@@ -39,7 +39,8 @@ def test_library_exports_every_declared_symbol():
 
 
 HOOKS = ("dtw_u", "dtw_tie_g", "dtw_kc", "mfcc_grid", "perturb_log_thr", "log_thr_from_host", "multi_allow_dup", "dtw_debug",
-         "cells_literal", "mag_cheap_off")
+         "cells_literal", "mag_cheap_off", "lds_poison_launches")
+TESTING_ONLY = ("sr_lds_launch_points", "sr_lds_probe")  # exported by both libraries, refused by the product library
 
 
 def test_product_library_has_no_development_hooks():
@@ -52,10 +53,13 @@ def test_product_library_has_no_development_hooks():
         assert L.sr_dev_hook(name.encode(), C.c_int64(1)) == 3, name          # SR_ERR_BAD_ARG
         assert b"not compiled into the product library" in L.sr_last_error()
     blob = open(engine.LIB_PATH, "rb").read()
-    for name in ("cells_literal", "multi_allow_dup", "perturb_log_thr", "log_thr_from_host"):
+    for name in ("cells_literal", "multi_allow_dup", "perturb_log_thr", "log_thr_from_host", "lds_poison_launches"):
         assert name.encode() + b"\0" not in blob, name                         # not even the name table
     T = engine.load_library(testing=True)
     assert T.sr_testing_build() == 1
+    for fn in TESTING_ONLY:
+        assert fn in declared_functions() and hasattr(L, fn) and hasattr(T, fn), fn
+    assert L.sr_lds_launch_points(None, None, C.c_uint32(0)) == 3 and L.sr_lds_probe(None, C.c_uint32(1), None, None) == 3
     missing = [n for n in declared_functions() if not hasattr(T, n)]
     assert not missing, missing
     for name in HOOKS:
