@@ -43,6 +43,17 @@ static_assert(SR_MAG_TAB_BINS == 0 || SR_MAG_TAB_BINS == 4 || SR_MAG_TAB_BINS ==
 #endif
 static_assert(SR_MFCC_PIPE_VMCNT == 0 || (SR_MFCC_PIPE_VMCNT == 3 && SR_MFCC_PIPE_PEEL), "younger loads counted by the wait");
 constexpr bool mfcc_pipelined(int fpw) { return SR_MFCC_PIPE && mfcc_tab_bins(fpw) == 8; }
+// switches of round 11, which cut the cycles a frame keeps the CU's LDS pipe busy (RESULTS.md, round 11):
+// SR_MFCC_TM_REGS 1 = the batch form keeps the QUIET tier's sixteen filterbank multipliers in VGPRs, not in s_tm;
+// SR_MFCC_PREFIX_TID: below.  Kept together: alone they are worth +0.7 % and -0.5 % of the step, the two -2.0 %.
+#ifndef SR_MFCC_TM_REGS
+#define SR_MFCC_TM_REGS 1
+#endif
+#ifdef SR_INJECT_LDS_RACE  // (the injected race is the late fill of s_tm: that build keeps the multipliers there)
+#undef SR_MFCC_TM_REGS
+#define SR_MFCC_TM_REGS 0
+#endif
+constexpr bool mfcc_tm_regs(int fpw) { return SR_MFCC_TM_REGS && mfcc_pipelined(fpw); }
 // per-wave LDS: exchange/scratch words + windowed frame + filterbank outputs of the wave's frames
 // rows of the filterbank outputs and of the DCT tables are kMelPad = 25 words apart: in the DCT the lanes of a wave read
 // 6 different frames x 12 different coefficients rows at the same column, and a stride of 24 folds those onto 4 banks
@@ -54,6 +65,48 @@ constexpr int kMelPad = kMel + 1;
 // chunk 1 makes the magnitude stage's 4-byte stores -- 32 consecutive bins per service group = 4 lanes' slots x both chunks --
 // hit 32 different banks as well.
 __device__ __forceinline__ constexpr int mel_chunk_word(int j) { return 256 * ((j >> 2) & 1) + 4 * ((j >> 3) ^ (4 * ((j >> 2) & 1))) + (j & 3); }
+// SR_MFCC_PREFIX_TID 1 (round 11): the sixteen in-lane prefixes of a lane leave as sixteen lane-contiguous 4-byte stores
+// (ds_write_addtid_b32, 2 cycles of the CU's store path each) instead of four ds_write_b128 (13 each): prefix P[j] of bin
+// j = 8 l + k sits at word 64 k + l of its poly-line's half.  The look-up's addresses are lane constants in any order; in
+// this one its 24 lanes meet on a bank two at a time at most (three in the chunked order).  The energies keep their order.
+#ifndef SR_MFCC_PREFIX_TID
+#define SR_MFCC_PREFIX_TID 1
+#endif
+__device__ __forceinline__ constexpr int mel_prefix_word(int j)
+{
+#if SR_MFCC_PREFIX_TID
+    return 64 * (j & 7) + (j >> 3);
+#elif SR_MEL_CHUNKED
+    return mel_chunk_word(j);
+#else
+    return j;
+#endif
+}
+// The stores: lane l writes pe[k] to word 64 k + l and po[k] to word kBins + 64 k + l of the area at LDS byte address `base`
+// (wave-uniform).  ds_write_addtid_b32's address is M0 + offset + 4 * lane: no address VGPR goes to the LDS.  M0 is set in
+// the same statement (one wait state before an add-TID instruction reads it) and named as clobbered.  The compiler treats M0
+// as reserved and says so about the clobber; it has no use of M0 of its own in this kernel -- no LDS bounds on gfx9+, no
+// movrel, no message, no LDS-DMA: `m0` occurs in the kernel's assembly in this statement only.  Look again after adding any
+// of those.  The wave's LDS operations complete in issue order, so a wait the compiler counts for its own reads, which does
+// not know of these stores, can only come out stricter.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void mel_prefix_store(uint32_t base, const uint32_t (&pe)[8], const uint32_t (&po)[8])
+{
+    static_assert(kBins == 512, "the offsets below are written out for two halves of 512 words");
+    asm volatile("s_mov_b32 m0, %16\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %0\n\tds_write_addtid_b32 %1 offset:256\n\tds_write_addtid_b32 %2 offset:512\n\t"
+                 "ds_write_addtid_b32 %3 offset:768\n\tds_write_addtid_b32 %4 offset:1024\n\tds_write_addtid_b32 %5 offset:1280\n\t"
+                 "ds_write_addtid_b32 %6 offset:1536\n\tds_write_addtid_b32 %7 offset:1792\n\t"
+                 "ds_write_addtid_b32 %8 offset:2048\n\tds_write_addtid_b32 %9 offset:2304\n\tds_write_addtid_b32 %10 offset:2560\n\t"
+                 "ds_write_addtid_b32 %11 offset:2816\n\tds_write_addtid_b32 %12 offset:3072\n\tds_write_addtid_b32 %13 offset:3328\n\t"
+                 "ds_write_addtid_b32 %14 offset:3584\n\tds_write_addtid_b32 %15 offset:3840"
+                 :
+                 : "v"(pe[0]), "v"(pe[1]), "v"(pe[2]), "v"(pe[3]), "v"(pe[4]), "v"(pe[5]), "v"(pe[6]), "v"(pe[7]), "v"(po[0]),
+                   "v"(po[1]), "v"(po[2]), "v"(po[3]), "v"(po[4]), "v"(po[5]), "v"(po[6]), "v"(po[7]), "s"(base)
+                 : "m0", "memory");
+}
+#pragma clang diagnostic pop
 constexpr int mfcc_wave_lds_words(int fpw) { return kXchgWords + fpw * kMelPad + 64; }
 
 // the kernel's argument block: the block every frame kernel takes (MfccArgs, or MfccFeatArgs<kind>) + the magnitude table
@@ -85,6 +138,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     constexpr int kWaveLdsWords = mfcc_wave_lds_words(kFPW);
     constexpr int kTabBins = mfcc_tab_bins(kFPW);
     constexpr bool kPipe = mfcc_pipelined(kFPW);
+    constexpr bool kTmRegs = mfcc_tm_regs(kFPW);
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ uint32_t s_dctM[kCoef * kMelPad];
     __shared__ int s_dctS[kCoef * kMelPad];  // 32-bit: read with the wide LDS loads, no byte extraction
@@ -96,6 +150,9 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     uint32_t *buf = smem + w * kWaveLdsWords;
     uint32_t *xw = buf;  // windowed frame, one word per sample: consumed by the pass-1 gather before the exchange overwrites it
     uint32_t *powb = buf + kXchgWords, *moff = powb + kFPW * kMelPad;
+    // LDS byte address of buf, wave-uniform: the base of the prefix stores
+    const uint32_t buf_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)buf;
+    (void)buf_lds;
 
     // DCT term (MFCC.C:179): (s32)pow * dct / 100, truncated toward zero, with 0 <= pow <= 2218 (= (u32)(ln(2^32)*100))
     // and |dct| <= 128.  floor(pow*|c|/100) == (pow * M_c) >> 18 with M_c = ceil(|c| * 2^18 / 100) for every such pair
@@ -125,8 +182,18 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     // (-DSR_INJECT_LDS_RACE=1 / =2, fault injection for the suite's race-class tests -- profiles/experiments/ab_build.sh race2 . -DSR_INJECT_LDS_RACE=2:
     // the fill is moved BEHIND the barrier, which is the defect round 5's soak found; level 2 also delays the late writer, which
     // opens the window on every workgroup instead of once in thousands of calls; what the tests make of both: RESULTS.md, round 6)
+    // (round 11: the batch form has the registers for them again since round 9 took it from 128 to 112 -- kTmRegs; four
+    // ds_read_b128 per frame and this table leave its LDS budget.  The forms for underfilled launches keep the table.)
+    u32x4 tm_r[4];
+    if constexpr (kTmRegs) {
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            tm_r[c] = *(const u32x4 *)(a.t.tri_even_m + 8 * lane + 4 * c);
+            tm_r[c + 2] = *(const u32x4 *)(a.t.tri_odd_m + 8 * lane + 4 * c);
+        }
+    }
 #ifndef SR_INJECT_LDS_RACE
-    if (w == 2 % kMfccWaves) {
+    if (!kTmRegs && w == 2 % kMfccWaves) {
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             s_tm[64 * c + lane] = *(const u32x4 *)(a.t.tri_even_m + 8 * lane + 4 * c);
@@ -151,8 +218,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 #pragma unroll
     for (int k = 0; k < 3; k++) hamm_m[k] = (lane + 64 * k < kFrameLen) ? hamm_fused_multiplier(a.t.hamm[lane + 64 * k]) : 0;
     // filter h < 24 owned by lane h: bins [lo, hi) of poly-line (h & 1)  (MFCC.C:136-162)
-    // prefix P[j] of bin j = 8 l + k sits at word 256 (k >> 2) + 4 l + (k & 3) of its poly-line's half (chunked order, see the
-    // magnitude stage), the lane offsets X[l] behind them: the addresses of P[hi - 1] / P[lo - 1] are lane constants
+    // prefix P[j] of bin j sits at word mel_prefix_word(j) of its poly-line's half, the lane offsets X[l] behind them: the
+    // addresses of P[hi - 1] / P[lo - 1] are lane constants
     int f_lo = 0, p_hi = 0, p_lo = 0, x_hi = 0, x_lo = 0;
     if (lane < kMel) {
         const int h = lane;
@@ -161,13 +228,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
         const int ih = f_hi - 1, il = f_lo ? f_lo - 1 : 0, half = (h & 1) ? kBins : 0;
         // X holds INCLUSIVE lane sums: the bins below lane l's first bin sum to X[l - 1]; every edge looked up lies in lane >= 1
         // (tri_cen[0] - 1 = 10), clamped so that an unused entry stays inside the array
-#if SR_MEL_CHUNKED
-        p_hi = half + mel_chunk_word(ih), x_hi = (ih >> 3) > 0 ? (ih >> 3) - 1 : 0;
-        p_lo = half + mel_chunk_word(il), x_lo = (il >> 3) > 0 ? (il >> 3) - 1 : 0;
-#else
-        p_hi = half + ih, x_hi = (ih >> 3) > 0 ? (ih >> 3) - 1 : 0;
-        p_lo = half + il, x_lo = (il >> 3) > 0 ? (il >> 3) - 1 : 0;
-#endif
+        p_hi = half + mel_prefix_word(ih), x_hi = (ih >> 3) > 0 ? (ih >> 3) - 1 : 0;
+        p_lo = half + mel_prefix_word(il), x_lo = (il >> 3) > 0 ? (il >> 3) - 1 : 0;
     }
     // The magnitude table as a structured buffer of exactly its size (stride 2, num_records in elements): the gathers index
     // it with n itself (idxen) -- no address arithmetic on the VALU -- and an n past the end could only load 0, never fault
@@ -226,6 +288,18 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 if (i < kFrameLen) s_pp[k] = *(const u32_align2 *)(x + i - 1);
             }
         }
+        // the in-lane prefixes of the lane's eight bins, both poly-lines (mel_prefix_word; every lane has read its energies: the
+        // wave's LDS operations complete in order)
+        auto store_prefixes = [&](const uint32_t (&pe)[8], const uint32_t (&po)[8]) {
+#if SR_MFCC_PREFIX_TID
+            mel_prefix_store(buf_lds, pe, po);
+#else
+            *(uint4 *)(buf + c0) = make_uint4(pe[0], pe[1], pe[2], pe[3]);
+            *(uint4 *)(buf + c1) = make_uint4(pe[4], pe[5], pe[6], pe[7]);
+            *(uint4 *)(buf + kBins + c0) = make_uint4(po[0], po[1], po[2], po[3]);
+            *(uint4 *)(buf + kBins + c1) = make_uint4(po[4], po[5], po[6], po[7]);
+#endif
+        };
         if constexpr (!kPipe)  // the forms without the table (and the feature variants of those): one frame at a time
         for (uint32_t fi = 0; fi < nf; fi++) {
             // ---- pre-emphasis + Hamming (MFCC.C:115-124); x[-1] is the sample before the frame
@@ -407,14 +481,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 xe = wave_scan_incl(se);  // sum over the bins of the lanes up to and including this one: a filter lane reads the
                 xo = wave_scan_incl(so);  // entry of the lane BELOW its bin's (never lane 0: the first filter edge is bin 10)
             }
-            // (no ordering point is needed here: a lane overwrites only the eight energies it has read itself, every other
-            // store below goes to words nobody reads before the next wave_sync)
+            // (no ordering point is needed here: every lane's energy reads above were issued before the stores below, the wave's LDS
+            // operations complete in order, and nobody reads the stored words before the next wave_sync)
             // in-lane prefixes and the per-lane offsets are stored separately: the 24 filter lanes add them on lookup
             // (2 adds) instead of every lane adding its offset to 16 prefixes
-            *(uint4 *)(buf + c0) = make_uint4(pe[0], pe[1], pe[2], pe[3]);
-            *(uint4 *)(buf + c1) = make_uint4(pe[4], pe[5], pe[6], pe[7]);
-            *(uint4 *)(buf + kBins + c0) = make_uint4(po[0], po[1], po[2], po[3]);
-            *(uint4 *)(buf + kBins + c1) = make_uint4(po[4], po[5], po[6], po[7]);
+            store_prefixes(pe, po);
             buf[2 * kBins + lane] = xe;
             moff[lane] = xo;
             wave_sync();
@@ -544,7 +615,9 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                     const uint32_t e[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
-                        const u32x4 me = s_tm[64 * c + lane], mo = s_tm[64 * (c + 2) + lane];
+                        u32x4 me, mo;
+                        if constexpr (kTmRegs) me = tm_r[c], mo = tm_r[c + 2];
+                        else me = s_tm[64 * c + lane], mo = s_tm[64 * (c + 2) + lane];
 #pragma unroll
                         for (int k = 0; k < 4; k++) {
                             se += mel_term_fused(e[4 * c + k], me[k]);  // (the table's squares are E << 4 already)
@@ -577,10 +650,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                     }
                 }
                 const uint32_t xe = wave_scan_incl(se), xo = wave_scan_incl(so);
-                *(uint4 *)(buf + c0) = make_uint4(pe[0], pe[1], pe[2], pe[3]);
-                *(uint4 *)(buf + c1) = make_uint4(pe[4], pe[5], pe[6], pe[7]);
-                *(uint4 *)(buf + kBins + c0) = make_uint4(po[0], po[1], po[2], po[3]);
-                *(uint4 *)(buf + kBins + c1) = make_uint4(po[4], po[5], po[6], po[7]);
+                store_prefixes(pe, po);
                 buf[2 * kBins + lane] = xe;
                 moff[lane] = xo;
                 wave_sync();
