@@ -1391,8 +1391,9 @@ int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n
  *             grammar's largest arc cost) + its largest final cost <= 2^30, refused with SR_ERR_BAD_ARG otherwise; and one
  *             row's scratch -- S x (max_frames + 1) keys and prefix costs and one saved column per kept item -- within the
  *             256 MiB of a launch group.
- * Out of scope: the push-by-push session, n_words_exact, N-best sequences, word alternatives under this decoder
- * (sr_score_word_spans takes its word rows), grammars of more than 64 states, recordings past 16 383 frames. */
+ * Out of scope: n_words_exact, N-best sequences, word alternatives under this decoder (sr_score_word_spans takes its word
+ * rows), grammars of more than 64 states, recordings past 16 383 frames.  (The push-by-push session is the section "live
+ * one-pass grammar decoding" below.) */
 /* Stage level, DEVICE buffers: sr_decode_onepass_dp_dev's arguments and rules with the grammar in front.  ONE asynchronous
  * operation on `stream`, no host synchronisation, no read-back; two runs give the same bytes.  Errors, before anything is
  * launched or written: sr_decode_onepass_dp_dev's, and SR_ERR_BAD_ARG for a null grammar, a grammar of another engine, a
@@ -1414,6 +1415,83 @@ int sr_decode_onepass_grammar_batch(sr_engine *h, const sr_grammar *g, const uin
  * out[1] = rows per launch group (0: one row does not fit, the call is refused); out[2] = the block length L; out[3] =
  * launches per group, 2 x ceil(frames_cap / L) + 2; out[4] = kept items; out[5] = kept states. */
 int sr_onepass_grammar_plan(const sr_grammar *g, uint32_t frames_cap, uint32_t out[6]);
+
+/* ------------------------------------------------------------------ live one-pass grammar decoding: state carried between pushes
+ * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  A grammar is for feeds -- a dialogue's command and its argument arrive as audio,
+ * not as a finished row -- and the looping grammars are the ones the live grammar-constrained decoding section serves worst: 16
+ * words at most, max_words sweeps per push.  A session of this section takes the frames of n_channels channels as they arrive,
+ * in pushes of any size up to chunk_max, keeps the one-pass grammar decoder's state on the device between calls, and after
+ * every push says how everything heard so far parses under the one-pass grammar decoding section's definition, at
+ * 2 x n x (kept items) x M cells per push of n frames, plus a trace.  No existing call, record or byte changes.
+ * THE RULE: let Y_c be every feature frame pushed to channel c since it was opened or last ended, N = |Y_c| <= utt_frames,
+ * utt_frames fixed at open in 1..16 383.  Every push emits one compact row for every channel with n[c] > 0, by ascending
+ * channel: an sr_chain_rec and words_cap x sr_chain_word (no level costs), labelled by an sr_chain_live_row that the host fills
+ * before the call returns.  The row is, byte for byte and whatever the chunking, what the one-pass grammar decoding section
+ * defines for Y_c as ONE row of N frames under the session's grammar, skip_cost and word_cost; `reserved` holds the state
+ * after each word.  Ties are that decoder's -- so they are not sr_gram_live's.  Whenever an engine's max_frames >= N the row
+ * therefore equals sr_decode_onepass_grammar_dp[_dev]'s.  A weighted grammar is taken as it is.  Under the anchor grammar the
+ * bytes are sr_onepass_live_push_dev's.
+ *   flags    SR_OP_LIVE_TAIL: the LAST words_cap words of the trace instead of the first, as in the live one-pass section; the
+ *            record is the same.  Any other flag is refused.
+ *   exact    why: A(p, t) and E(p, t) depend on frames below p only, so the history of a recording is a prefix of that of any
+ *            longer one; a word that starts inside a block of at most L frames cannot end inside it, whatever state it leads
+ *            into, so a push's frames may be cut into blocks at the push boundaries, each resumed from the column saved at
+ *            the first frame of the channel's last block; and the trace reads A, E and N only.
+ *   state    per channel on the device: A[S][utt_frames + 1] (u64 keys) and E[S][utt_frames + 1] (u32), dense by state index;
+ *            one saved exact column per kept item, tpl_len x 16 bytes; the channel's whole feature row, utt_frames x 24 bytes.
+ *            The kept items and states are the static pruning the grammar carries (the one-pass grammar decoding section).  A
+ *            position of A that no push has reached holds all ones, E(0, 0) = 0 and E(0, s) is unreachable for s != 0: open,
+ *            sr_onepass_gram_live_set_grammar and the end call establish and restore that and may synchronise; a push runs
+ *            without an init launch and never synchronises.  A grammar that keeps no state parses nothing: its pushes launch
+ *            the trace alone, and the feature row is neither written nor read.
+ *   limits   (utt_frames / L) x (word_cost + the grammar's largest arc cost) + its largest final cost <= 2^30, checked at open
+ *            and at sr_onepass_gram_live_set_grammar.  A stale grammar refuses pushes, so the store cannot change under a live
+ *            bound.
+ * The session's grammar, its switching and a grammar gone stale follow the live grammar-constrained decoding section: a grammar
+ * compiled before the last sr_set_templates* or sr_set_word_map refuses every push until the channels are ended (each listed
+ * recording is then DROPPED: the SR_CH_NONE record, frames = 0 -- whatever the engine's current store and word map are) and a
+ * fresh grammar is set.  Teardown order: the session before its grammar, the grammar before the engine.
+ * PCM sessions (mid given at open) share the spot session's front end exactly as the live one-pass section's do: a row is
+ * emitted for n[c] > 0 whether or not a frame was completed; samples without a new frame give the parse so far again (that
+ * push launches the trace only); while the recording has at most max_frames frames the row equals
+ * sr_decode_onepass_grammar_batch(X_c, 1, R, mid[c]).
+ * Refusals come in the order stale grammar, counts, inputs, outputs, device; a refused call writes nothing and changes no
+ * state.  Stream ordering is the live connected-word decoding section's.
+ * Out of scope: a grammar per channel; a history compacted to the kept states; a row for the best non-final state while an
+ * utterance is incomplete; n_words_exact; N-best sequences; recordings past 16 383 frames; a "stable prefix" marker. */
+typedef struct sr_onepass_gram_live sr_onepass_gram_live;
+/* host-only, no device.  out[0] = device state bytes per channel, S x (utt_frames + 1) x 12 + kept items x tpl_len x 16 +
+ * utt_frames x 24, saturating; out[1] = the longest template that fits (sr_spot_geometry's out[2]); out[2] = L; out[3] = the
+ * kernel launches a feature push of chunk_max frames enqueues, per_block x ceil(chunk_max / L) + 1 with per_block = (kept items ?
+ * 1 : 0) + (kept states ? 1 : 0); out[4] = kept items; out[5] = kept states.  utt_frames 1..16 383, chunk_max 1..utt_frames. */
+int sr_onepass_gram_live_geometry(const sr_grammar *g, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[6]);
+/* sr_onepass_live_open's arguments and rules with the grammar in front; SR_ERR_BAD_ARG also for a null grammar, a grammar of
+ * another engine, a stale grammar and the cost bound above. */
+int sr_onepass_gram_live_open(sr_engine *h, const sr_grammar *g, uint32_t n_channels, uint32_t chunk_max, uint32_t utt_frames,
+                              uint32_t words_cap, uint32_t flags, uint32_t skip_cost, uint32_t word_cost, const uint32_t *mid,
+                              sr_onepass_gram_live **out);
+void sr_onepass_gram_live_close(sr_onepass_gram_live *l); /* before sr_grammar_destroy of its grammar; waits for the last push */
+/* sr_gram_live_set_grammar's rules: g a fresh grammar of the session's engine, accepted only while every channel is empty
+ * (SR_ERR_BAD_ARG otherwise, nothing changes).  The state is laid out for g -- what has to grow is allocated aside and swapped in
+ * after the last allocation, so a failed allocation leaves the session as it was -- and the invariants above are put in place
+ * under the new layout.  Waits for the device. */
+int sr_onepass_gram_live_set_grammar(sr_onepass_gram_live *l, const sr_grammar *g);
+/* The four push forms: sr_onepass_live_push[_pcm][_dev]'s arguments and rules. */
+int sr_onepass_gram_live_push_dev(sr_onepass_gram_live *l, const int16_t *d_mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                                  uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words, sr_chain_live_row *rows,
+                                  uint32_t *n_rows, void *stream);
+int sr_onepass_gram_live_push(sr_onepass_gram_live *l, const int16_t *mfcc, uint64_t row_stride, const uint32_t *n, uint32_t n_all,
+                              uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows, uint32_t *n_rows);
+int sr_onepass_gram_live_push_pcm_dev(sr_onepass_gram_live *l, const uint16_t *d_pcm, uint64_t pcm_stride, const uint32_t *n,
+                                      uint32_t n_all, uint32_t max_rows, sr_chain_rec *d_rec, sr_chain_word *d_words,
+                                      sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_onepass_gram_live_push_pcm(sr_onepass_gram_live *l, const uint16_t *pcm, uint64_t pcm_stride, const uint32_t *n, uint32_t n_all,
+                                  uint32_t max_rows, sr_chain_rec *rec, sr_chain_word *words, sr_chain_live_row *rows,
+                                  uint32_t *n_rows);
+/* sr_onepass_live_end's arguments and rules.  With a stale grammar the listed recordings are dropped (above); the channels
+ * are then empty, and their keys are wiped all the same. */
+int sr_onepass_gram_live_end(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
+                             sr_chain_live_row *rows, uint32_t *n_rows);
 
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,
@@ -1539,7 +1617,10 @@ int sr_get_stage_launches(sr_engine *h, uint32_t *launches_per_call);
  *                                    read per call and by sr_decode_onepass_geometry
  *   "onepass_gram_prune_off"         one-pass grammar decoding keeps every item and every state (no static pruning; the same
  *                                    bytes come out); read per call and by sr_onepass_grammar_plan.  The calls also read
- *                                    "onepass_block" and "onepass_rows" as the one-pass decoder does
+ *                                    "onepass_block" and "onepass_rows" as the one-pass decoder does.  The live one-pass
+ *                                    grammar session reads it when a grammar is adopted (open, set_grammar: it fixes the
+ *                                    column layout until the next adoption), sr_onepass_gram_live_geometry when called;
+ *                                    the session reads "onepass_block" per push
  *   "live_origin"                   samples (an int64 multiple of the hop) a fresh sr_live channel behaves as having consumed
  *                                    before: received = the value, next frame = value / hop, in the device state and the host
  *                                    mirror; nothing in the push path knows of it.  Read where a channel is made fresh

@@ -1,0 +1,485 @@
+// k_onepass_gram_live.hip -- live one-pass grammar decoding (include/sr_engine.h, "live one-pass grammar decoding"):
+// k_onepass_gram.hip's blocks with the boundaries set by the caller's pushes, per channel and of unequal length, as
+// k_onepass_live.hip sets them for the decoder without a grammar.  OPT-IN EXTENSION, no reference counterpart.  gfx950 (MI355X,
+// CDNA4) only; wave = 64 lanes; integer VALU + LDS.
+//
+// The block argument holds state by state (sr_onepass_gram_plan.h) and whatever the lengths of the blocks before (k_onepass_live
+// .hip): a word that starts inside a block of at most L frames cannot end inside it whatever state it leads into, so A(., t) and
+// E(., t) over a block follow from E(., s) at or before its first frame.  A channel keeps A and E of every state over its whole
+// recording, dense by state index, per kept item the EXACT column at the first frame c0 of the block swept last, and its feature
+// row.  A push that appends the frames [x0, x0 + n) is, per block b = 0.. of `block` <= L frames, in stream order:
+//   k_onepass_gram_live_words   k_onepass_gram_words with (xs, c0, cN) per channel from the plan table: c0 = x0 + b * block, the
+//                               sweep starts behind the saved column (that of the last push's last block for b = 0).  Columns
+//                               before x0 come from the channel's kept feature row, the rest from the push.  A channel with
+//                               fewer than b + 1 blocks leaves (wave-uniform);
+//   k_onepass_gram_live_close   k_onepass_gram_close per (channel, kept state); the workgroups of the FIRST kept state also append
+//                               the block's frames to the kept feature row, which no sweep of this push reads at those columns;
+//   k_onepass_gram_live_trace   opg_trace_row's walk with N = x0 + n into the compact row the host assigned, the first words_cap
+//                               words or (tail) the last.
+// A WEIGHTED grammar takes k_onepass_gram_live_words_w and k_onepass_gram_live_trace_w; a grammar without a nonzero cost launches
+// the unweighted kernels only.  No init launch: a position of A that no push has reached holds all ones, E(0, 0) = 0 and E(0, s)
+// is unreachable for s != 0 from the open call (or the adoption of a grammar) on, and the end call puts that back
+// (k_onepass_gram_live_wipe).  Where no state is kept no item is kept either (a kept item's charge list is kept): nothing sweeps,
+// nothing closes, nothing parses, and the feature row is neither written nor read.  No workgroup waits on another: the blocks are
+// ordered by the stream alone.  Plain vector stores; the atomic minimum on A is the only atomic, and it does not depend on the
+// order of the waves, so two runs give the same bytes.  The sweep, the close and the walk are restated here and not shared:
+// k_onepass_gram.hip, k_onepass_live.hip and k_gram_live.hip stay byte for byte what they were measured as.
+#include "sr_dtw_plan.h"
+#include "sr_spot_dev.h"
+
+namespace sr {
+
+// block b of a channel: frames [c0, cN); false: the channel has no such block (a silent channel has none at all)
+__device__ __forceinline__ bool opgl_block(const OnePassGramLiveArgs &a, const SpotLiveChan &ch, uint32_t b, uint32_t *c0, uint32_t *cN)
+{
+    const uint32_t end = ch.x0 + ch.n;  // <= utt_frames <= 16 383, and b * block < 16 384: no wrap
+    *c0 = ch.x0 + b * a.o.block;
+    *cN = end - *c0 < a.o.block ? end : *c0 + a.o.block;
+    return *c0 < end;
+}
+__device__ __forceinline__ unsigned long long *opgl_A(const OnePassGramLiveArgs &a, uint32_t c, uint32_t state)
+{
+    return a.o.A + ((size_t)c * a.n_states + state) * a.o.P;
+}
+__device__ __forceinline__ uint32_t *opgl_E(const OnePassGramLiveArgs &a, uint32_t c, uint32_t state)
+{
+    return a.o.E + ((size_t)c * a.n_states + state) * a.o.P;
+}
+__device__ __forceinline__ uint32_t opgl_state(const OnePassGramLiveArgs &a, uint32_t i) { return a.keep_states ? a.keep_states[i] : i; }
+
+// block b of every (kept item, channel)
+__global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(const OnePassGramLiveArgs a, const uint32_t b)
+{
+    extern __shared__ __attribute__((aligned(16))) u32x4 ogl_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
+    const GramItem it = a.items[a.keep_items ? a.keep_items[blockIdx.x] : blockIdx.x];
+    const uint32_t k = it.slot, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.y * kSpotWaves + w;
+    uint32_t M = a.o.tpl_valid[k] ? a.o.tpl_frames[k] : 0u;
+    M = M < a.o.tpl_len ? M : a.o.tpl_len;
+    ulonglong2 *s_col = (ulonglong2 *)(ogl_smem + (size_t)a.o.tpl_len * 2) + (size_t)w * a.o.tpl_len;  // (Dd, min(Dd, Dn)) per row
+    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
+        const uint2 *src = (const uint2 *)(a.o.tpl + (size_t)k * a.o.tpl_stride + (size_t)r * kCoef);
+        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+        ogl_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
+        ogl_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
+    }
+    __syncthreads();
+    if (c >= a.o.C || !M) return;  // (a grammar keeps items of valid slots only)
+    const SpotLiveChan ch = a.o.chan[c];
+    uint32_t c0, cN;
+    if (!opgl_block(a, ch, b, &c0, &cN)) return;  // (wave-uniform)
+    // the sweep starts behind the saved column: that of this push's last block, or of the last push's (none at frame 0)
+    const uint32_t xs = c0 ? (b ? c0 - a.o.block : ch.aux) + 1u : 0u;
+    const uint32_t P = a.o.P;
+
+    ulonglong2 *g_col = a.o.cols + ((size_t)c * a.n_keep_items + blockIdx.x) * a.o.tpl_len;
+    const uint32_t *E = opgl_E(a, c, 0);  // state s at E + s * P
+    const unsigned long long mask = a.masks[it.set];
+    unsigned long long *A = opgl_A(a, c, it.target);
+    if (xs) {  // resume: the saved column, that of xs - 1 (16-byte loads, coalesced over template rows)
+        for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
+        wave_sync();
+    }
+    const int16_t *kept = a.o.feat + (size_t)c * (P - 1u) * kCoef;  // the columns before the push
+    const int16_t *in = a.o.mfcc + (uint64_t)c * a.o.row_stride;     // the columns [x0, x0 + n)
+    for (uint32_t s0 = xs; s0 < cN; s0 += 64) {  // (wave-uniform)
+        const uint32_t col = s0 + lane;
+        const bool live = col < cN;
+        const uint32_t last = (cN - s0 < 64u ? cN - s0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
+        const bool keep = col == c0;                                // the exact column the next block resumes from
+        Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
+        if (live) {
+            const uint2 *src = (const uint2 *)(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
+            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+            fi.w[6] = (uint32_t)dot_rows(fi, fi);
+        }
+        // C(col): what a word that starts in this column builds on, the cheapest state of the charge list; final for col <= c0,
+        // none yet inside the block
+        uint32_t charge = kChainNone;
+        const bool charged = live && col <= c0;  // (col <= c0 < utt_frames: inside the state's row)
+        for (unsigned long long m = mask; m; m &= m - 1) {  // (wave-uniform)
+            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+            const uint32_t e = charged ? E[(size_t)s * P + col] : kChainNone;
+            charge = e < charge ? e : charge;
+        }
+        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
+        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
+        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
+        const uint32_t steps = M + last;
+        for (uint32_t t = 0; t < steps; t++) {
+            const int r = (int)t - (int)lane;
+            // the left lane's results of the previous step are the states of (col - 1, r)
+            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
+            if (lane == 0) {
+                fl_d = fl_m = kSpotInf;
+                if (s0 != 0 && t < M) {  // column s0 - 1: this launch's last sweep, or the saved column (none for column 0)
+                    const ulonglong2 v = s_col[t];
+                    fl_d = v.x;
+                    fl_m = v.y;
+                }
+            }
+            if (live && r >= 0 && r < (int)M) {
+                const Row32 fm = row_from(ogl_smem[2 * r], ogl_smem[2 * r + 1]);
+                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
+                uint64_t cd = kSpotInf, cn;
+                if (r > 0) {
+                    cd = spot_add(diag, d);
+                    cn = spot_add(spot_min(fl_d, up_d), d);
+                } else {  // row 0: a charged start, of the non-diagonal kind
+                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
+                }
+                up_d = cd;
+                up_m = spot_min(cd, cn);
+                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
+                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
+                if (r == (int)M - 1) end_v = up_m;
+            }
+            diag = fl_m;
+        }
+        wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
+
+        // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1, target); col + 1 <= cN <= utt_frames
+        if (live && col >= c0 && end_v != kSpotInf) {
+            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.o.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
+            atomicMin(&A[col + 1], (unsigned long long)key);
+        }
+    }
+}
+
+// k_onepass_gram_live_words under costs (include/sr_engine.h, "weighted grammars"): the same resumed sweep, the charge of a
+// column taken over the item's charge list with the arc costs added.  Restated: k_onepass_gram_live_words stays what it is.
+__global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words_w(const OnePassGramLiveArgs a, const GramCosts wt, const uint32_t b)
+{
+    extern __shared__ __attribute__((aligned(16))) u32x4 oglw_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
+    const GramItem it = a.items[a.keep_items ? a.keep_items[blockIdx.x] : blockIdx.x];
+    const uint32_t k = it.slot, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.y * kSpotWaves + w;
+    uint32_t M = a.o.tpl_valid[k] ? a.o.tpl_frames[k] : 0u;
+    M = M < a.o.tpl_len ? M : a.o.tpl_len;
+    ulonglong2 *s_col = (ulonglong2 *)(oglw_smem + (size_t)a.o.tpl_len * 2) + (size_t)w * a.o.tpl_len;  // (Dd, min(Dd, Dn)) per row
+    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
+        const uint2 *src = (const uint2 *)(a.o.tpl + (size_t)k * a.o.tpl_stride + (size_t)r * kCoef);
+        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+        oglw_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
+        oglw_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
+    }
+    __syncthreads();
+    if (c >= a.o.C || !M) return;  // (a grammar keeps items of valid slots only)
+    const SpotLiveChan ch = a.o.chan[c];
+    uint32_t c0, cN;
+    if (!opgl_block(a, ch, b, &c0, &cN)) return;  // (wave-uniform)
+    // the sweep starts behind the saved column: that of this push's last block, or of the last push's (none at frame 0)
+    const uint32_t xs = c0 ? (b ? c0 - a.o.block : ch.aux) + 1u : 0u;
+    const uint32_t P = a.o.P;
+
+    ulonglong2 *g_col = a.o.cols + ((size_t)c * a.n_keep_items + blockIdx.x) * a.o.tpl_len;
+    const uint32_t *E = opgl_E(a, c, 0);  // state s at E + s * P
+    const unsigned long long mask = a.masks[it.set];
+    const uint32_t *cost = wt.cost + wt.cost_off[it.set];  // by ascending state, as the mask is walked
+    unsigned long long *A = opgl_A(a, c, it.target);
+    if (xs) {  // resume: the saved column, that of xs - 1 (16-byte loads, coalesced over template rows)
+        for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
+        wave_sync();
+    }
+    const int16_t *kept = a.o.feat + (size_t)c * (P - 1u) * kCoef;  // the columns before the push
+    const int16_t *in = a.o.mfcc + (uint64_t)c * a.o.row_stride;     // the columns [x0, x0 + n)
+    for (uint32_t s0 = xs; s0 < cN; s0 += 64) {  // (wave-uniform)
+        const uint32_t col = s0 + lane;
+        const bool live = col < cN;
+        const uint32_t last = (cN - s0 < 64u ? cN - s0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
+        const bool keep = col == c0;                                // the exact column the next block resumes from
+        Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
+        if (live) {
+            const uint2 *src = (const uint2 *)(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
+            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
+            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
+            fi.w[6] = (uint32_t)dot_rows(fi, fi);
+        }
+        // C(col): the cheapest E + arc cost of the charge list; an unreachable E takes no cost (all ones + c would wrap to
+        // c - 1 and win); final for col <= c0, none yet inside the block
+        uint32_t charge = kChainNone;
+        const bool charged = live && col <= c0;  // (col <= c0 < utt_frames: inside the state's row)
+        uint32_t j = 0;
+        for (unsigned long long m = mask; m; m &= m - 1, j++) {  // (wave-uniform)
+            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+            const uint32_t e = charged ? E[(size_t)s * P + col] : kChainNone, v = e + cost[j];
+            charge = (e != kChainNone && v < charge) ? v : charge;
+        }
+        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
+        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
+        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
+        const uint32_t steps = M + last;
+        for (uint32_t t = 0; t < steps; t++) {
+            const int r = (int)t - (int)lane;
+            // the left lane's results of the previous step are the states of (col - 1, r)
+            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
+            if (lane == 0) {
+                fl_d = fl_m = kSpotInf;
+                if (s0 != 0 && t < M) {  // column s0 - 1: this launch's last sweep, or the saved column (none for column 0)
+                    const ulonglong2 v = s_col[t];
+                    fl_d = v.x;
+                    fl_m = v.y;
+                }
+            }
+            if (live && r >= 0 && r < (int)M) {
+                const Row32 fm = row_from(oglw_smem[2 * r], oglw_smem[2 * r + 1]);
+                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
+                uint64_t cd = kSpotInf, cn;
+                if (r > 0) {
+                    cd = spot_add(diag, d);
+                    cn = spot_add(spot_min(fl_d, up_d), d);
+                } else {  // row 0: a charged start, of the non-diagonal kind
+                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
+                }
+                up_d = cd;
+                up_m = spot_min(cd, cn);
+                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
+                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
+                if (r == (int)M - 1) end_v = up_m;
+            }
+            diag = fl_m;
+        }
+        wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
+
+        // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1, target); col + 1 <= cN <= utt_frames
+        if (live && col >= c0 && end_v != kSpotInf) {
+            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.o.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
+            atomicMin(&A[col + 1], (unsigned long long)key);
+        }
+    }
+}
+
+// k_onepass_gram_close per (channel, kept state) and channel block; grid (channels, kept states).  A state that no key arrived
+// in is closed all the same: its filler, or unreachable.  Before it, the workgroups of the first kept state append the block's
+// frames to the kept feature row.
+__global__ void __launch_bounds__(256) k_onepass_gram_live_close(const OnePassGramLiveArgs a, const uint32_t b)
+{
+    __shared__ uint64_t s_tot[4];
+    const uint32_t c = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t state = opgl_state(a, blockIdx.y);
+    const SpotLiveChan ch = a.o.chan[c];
+    uint32_t c0, cN;
+    if (!opgl_block(a, ch, b, &c0, &cN)) return;  // (uniform)
+    if (blockIdx.y == 0) {  // 24-byte rows as three 8-byte words each; both sides are 8-byte aligned
+        const uint2 *src = (const uint2 *)(a.o.mfcc + (uint64_t)c * a.o.row_stride + (size_t)(c0 - ch.x0) * kCoef);
+        uint2 *dst = (uint2 *)(a.o.feat + ((size_t)c * (a.o.P - 1u) + c0) * kCoef);
+        for (uint32_t i = threadIdx.x; i < (cN - c0) * 3u; i += 256) dst[i] = src[i];
+    }
+    const unsigned long long *A = opgl_A(a, c, state);
+    uint32_t *E = opgl_E(a, c, state);
+    if (a.o.skip_cost == kChainNone) {  // no skipping: the costs themselves (all ones stays SR_DIS_ERR)
+        for (uint32_t p = c0 + 1 + threadIdx.x; p <= cN; p += 256) E[p] = (uint32_t)(A[p] >> 32);
+        return;
+    }
+    const uint64_t skip = a.o.skip_cost;
+    const uint32_t e_c0 = E[c0];  // (written by the last block's close, in this push or the last; the invariant at frame 0)
+    uint64_t carry = e_c0 == kChainNone ? kSpotInf : (uint64_t)e_c0 + (uint64_t)(cN - c0) * skip;
+    for (uint32_t p0 = c0 + 1; p0 <= cN; p0 += 256) {  // (uniform)
+        const uint32_t p = p0 + threadIdx.x;
+        uint64_t v = kSpotInf;
+        if (p <= cN) {
+            const uint64_t key = A[p];
+            if (key != kSpotInf) v = (key >> 32) + (uint64_t)(cN - p) * skip;
+        }
+#pragma unroll
+        for (uint32_t by = 1; by < 64; by <<= 1) {
+            const uint64_t o = spot_shfl_up(v, by);
+            if (lane >= by) v = spot_min(v, o);
+        }
+        if (lane == 63) s_tot[w] = v;
+        __syncthreads();
+        uint64_t m = spot_min(v, carry);
+        for (uint32_t i = 0; i < w; i++) m = spot_min(m, s_tot[i]);
+        if (p <= cN) E[p] = m != kSpotInf ? (uint32_t)(m - (uint64_t)(cN - p) * skip) : kChainNone;
+        for (uint32_t i = 0; i < 4; i++) carry = spot_min(carry, s_tot[i]);
+        __syncthreads();  // s_tot is read before the next round overwrites it
+    }
+}
+
+// the item (slot, t) by bisection of the items, which ascend by (slot, target): its index, or n_items
+__device__ __forceinline__ uint32_t opgl_item_of(const OnePassGramLiveArgs &a, uint32_t slot, uint32_t t)
+{
+    uint32_t lo = 0, hi = a.n_items;
+    const uint64_t want = ((uint64_t)slot << 32) | t;
+    while (lo < hi) {  // (uniform)
+        const uint32_t mid = lo + (hi - lo) / 2;
+        const GramItem it = a.items[mid];
+        if ((((uint64_t)it.slot << 32) | it.target) < want) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < a.n_items) {
+        const GramItem it = a.items[lo];
+        if (it.slot == slot && it.target == t) return lo;
+    }
+    return a.n_items;
+}
+
+// One step of the walk, all lanes alike, as opg_step takes it: the word that closes E(., t) at or below p.  Returns its end
+// position q (0: the rest is filler) with its key, the charge it started from and the smallest state of its charge list that
+// carries that charge; wt null: no costs.  *bad is set where A, E and the items disagree, which cannot happen.
+__device__ __forceinline__ uint32_t opgl_step(const OnePassGramLiveArgs &a, const GramCosts *wt, uint32_t c, uint32_t p, uint32_t t, uint32_t lane,
+                                              uint64_t *key, uint32_t *charge, uint32_t *src, bool *bad)
+{
+    *key = kSpotInf;
+    const uint32_t q = onepass_word_at(opgl_A(a, c, t), opgl_E(a, c, t), p, lane, key);
+    if (!q) return 0u;
+    const uint32_t slot = (uint32_t)*key & 0xFFFFu, start = (uint32_t)(*key >> 16) & 0xFFFFu;
+    const uint32_t at = opgl_item_of(a, slot, t);
+    if (at == a.n_items) {
+        *bad = true;
+        return 0u;
+    }
+    const uint32_t set = a.items[at].set;
+    const uint32_t *ac = wt ? wt->cost + wt->cost_off[set] : nullptr;
+    uint32_t cst = kChainNone, s0 = 0;
+    for (unsigned long long m = a.masks[set]; m; m &= m - 1) {  // (uniform; ascending states)
+        const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+        const uint32_t e = opgl_E(a, c, s)[start], v = ac ? e + *ac++ : e;
+        if (e != kChainNone && v < cst) cst = v, s0 = s;
+    }
+    *charge = cst;
+    *src = s0;
+    return q;
+}
+
+// one wave per emitting channel: the end state, then the history of its N = x0 + n frames walked twice, first for the count,
+// then for the words in spoken order -- the first words_cap of them, or (tail) the last, where the second walk ends as soon as
+// they are written
+__device__ __forceinline__ void opgl_trace_chan(const OnePassGramLiveArgs &a, const GramCosts *wt, uint32_t c, uint32_t lane)
+{
+    const SpotLiveChan ch = a.o.chan[c];
+    if (!ch.first_win) return;
+    const uint32_t W = a.o.words_cap, N = ch.x0 + ch.n;
+    sr_chain_rec *rec = a.o.rec + ch.row_base;
+    sr_chain_word *words = a.o.words + (size_t)ch.row_base * W;
+    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    // the cheapest final state, its final cost included, the smallest state among equals (the kept states ascend)
+    uint32_t total = kChainNone, fin = 0;
+    for (uint32_t i = 0; N && i < a.n_keep_states; i++) {  // (uniform)
+        const uint32_t f = opgl_state(a, i);
+        if (!a.final_state[f]) continue;
+        const uint32_t e = opgl_E(a, c, f)[N];
+        if (e == kChainNone) continue;  // an unreachable state takes no cost
+        const uint32_t v = wt ? e + wt->final_cost[f] : e;
+        if (v < total) total = v, fin = f;
+    }
+    if (total == kChainNone) {  // (uniform) an empty channel or no parse
+        for (uint32_t i = lane; i < W; i += 64) words[i] = none;
+        if (lane == 0) *rec = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
+        return;
+    }
+    uint32_t n = 0, in_words = 0;
+    bool bad = false;
+    for (uint32_t p = N, t = fin; p;) {  // (uniform) the count; every start lies below its end position: the walk ends
+        uint64_t key;
+        uint32_t charge = 0, src = 0;
+        const uint32_t q = opgl_step(a, wt, c, p, t, lane, &key, &charge, &src, &bad);
+        if (!q) break;
+        const uint32_t start = (uint32_t)(key >> 16) & 0xFFFFu;
+        n++;
+        in_words += q - start;  // frames start .. q - 1
+        p = start;
+        t = src;
+    }
+    if (bad) {  // leave a whole record that says so
+        for (uint32_t i = lane; i < W; i += 64) words[i] = none;
+        if (lane == 0) *rec = sr_chain_rec{kChainNone, 0u, 0u, SR_CH_NONE};
+        return;
+    }
+    const uint32_t shown = n < W ? n : W, first = a.o.tail ? n - shown : 0u;  // the words first .. first + shown - 1 are written
+    for (uint32_t i = shown + lane; i < W; i += 64) words[i] = none;
+    uint32_t i = n;
+    for (uint32_t p = N, t = fin; p && i > first;) {  // (uniform)
+        uint64_t key;
+        uint32_t charge = 0, src = 0;
+        const uint32_t q = opgl_step(a, wt, c, p, t, lane, &key, &charge, &src, &bad);
+        if (!q) break;
+        const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu, end = q - 1;
+        i--;
+        if (lane == 0 && i - first < shown) {
+            const uint32_t cum = (uint32_t)(key >> 32), acc = cum - a.o.word_cost - charge;
+            words[i - first] =
+                sr_chain_word{a.o.word_id[a.o.group_of_slot[slot]], slot, start, end, acc, acc / (end - start + 1 + a.o.tpl_frames[slot]), cum, t};
+        }
+        p = start;
+        t = src;
+    }
+    if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, n > W ? SR_CH_TRUNCATED : SR_CH_OK};
+}
+
+__global__ void __launch_bounds__(64) k_onepass_gram_live_trace(const OnePassGramLiveArgs a) { opgl_trace_chan(a, nullptr, blockIdx.x, threadIdx.x); }
+// under costs: the final cost at the end, the charge and the source state of a word judged on E + the arc cost
+__global__ void __launch_bounds__(64) k_onepass_gram_live_trace_w(const OnePassGramLiveArgs a, const GramCosts wt)
+{
+    opgl_trace_chan(a, &wt, blockIdx.x, threadIdx.x);
+}
+
+// grid (channels, states of the dense layout): the keys of every listed channel are all ones again over the positions it had
+// reached (0..aux, aux <= utt_frames = P - 1), in EVERY state -- which covers every state a key can have been written in,
+// whatever was kept -- and the prefix cost of position 0 is the empty channel's
+__global__ void __launch_bounds__(256) k_onepass_gram_live_wipe(const OnePassGramLiveArgs a)
+{
+    const uint32_t c = blockIdx.x, state = blockIdx.y;
+    const SpotLiveChan ch = a.o.chan[c];
+    if (!ch.first_win) return;
+    unsigned long long *A = opgl_A(a, c, state);
+    for (uint32_t p = threadIdx.x; p <= ch.aux; p += 256) A[p] = kSpotInf;
+    if (threadIdx.x == 0) opgl_E(a, c, state)[0] = state ? kChainNone : 0u;
+}
+
+static void opgl_launch_trace(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s)
+{
+    if (w) {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_live_trace_w");
+        hipLaunchKernelGGL(k_onepass_gram_live_trace_w, dim3(a.o.C), dim3(64), 0, s, a, *w);
+    } else {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_live_trace");
+        hipLaunchKernelGGL(k_onepass_gram_live_trace, dim3(a.o.C), dim3(64), 0, s, a);
+    }
+}
+
+void launch_onepass_gram_live(const OnePassGramLiveArgs &a, const GramCosts *w, uint32_t n_blocks, hipStream_t s)
+{
+    if (!a.o.C) return;
+    const size_t lds = spot_lds_bytes(a.o.tpl_len);
+    const dim3 grid(a.n_keep_items, (a.o.C + kSpotWaves - 1) / kSpotWaves);
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        if (a.n_keep_items) {
+            if (w) {
+                SR_LAUNCH_POINT(s, "k_onepass_gram_live_words_w");
+                hipLaunchKernelGGL(k_onepass_gram_live_words_w, grid, dim3(64 * kSpotWaves), lds, s, a, *w, b);
+            } else {
+                SR_LAUNCH_POINT(s, "k_onepass_gram_live_words");
+                hipLaunchKernelGGL(k_onepass_gram_live_words, grid, dim3(64 * kSpotWaves), lds, s, a, b);
+            }
+        }
+        if (a.n_keep_states) {
+            SR_LAUNCH_POINT(s, "k_onepass_gram_live_close");
+            hipLaunchKernelGGL(k_onepass_gram_live_close, dim3(a.o.C, a.n_keep_states), dim3(256), 0, s, a, b);
+        }
+    }
+    opgl_launch_trace(a, w, s);
+}
+void launch_onepass_gram_live_wipe(const OnePassGramLiveArgs &a, hipStream_t s)
+{
+    if (!a.o.C || !a.n_states) return;
+    SR_LAUNCH_POINT(s, "k_onepass_gram_live_wipe");
+    hipLaunchKernelGGL(k_onepass_gram_live_wipe, dim3(a.o.C, a.n_states), dim3(256), 0, s, a);
+}
+void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s)
+{
+    if (!a.o.C) return;
+    opgl_launch_trace(a, w, s);
+    launch_onepass_gram_live_wipe(a, s);
+}
+const char *onepass_gram_live_allow_lds(uint32_t bytes)
+{
+    return allow_dynamic_lds({{(const void *)k_onepass_gram_live_words, "k_onepass_gram_live_words"},
+                              {(const void *)k_onepass_gram_live_words_w, "k_onepass_gram_live_words_w"}},
+                             bytes);
+}
+
+}  // namespace sr

@@ -37,7 +37,7 @@ enum DevHook {
     kHookForcedPruneOff,  // "forced_prune_off": the forced aligner sweeps every end frame of every level (no column bound; read per call)
     kHookOnePassBlock,    // "onepass_block": frames per block of the one-pass decoder, clamped to 1..L (read per call and push, and by the two one-pass geometry calls)
     kHookOnePassRows,     // "onepass_rows": rows per launch group of the one-pass decoder (read per call and by sr_decode_onepass_geometry)
-    kHookOnePassGramPruneOff,  // "onepass_gram_prune_off": one-pass grammar decoding keeps every item and every state (no static pruning; read per call and by sr_onepass_grammar_plan)
+    kHookOnePassGramPruneOff,  // "onepass_gram_prune_off": one-pass grammar decoding keeps every item and every state (no static pruning; read per call and by sr_onepass_grammar_plan; the live session reads it when it adopts a grammar)
     kHookLiveOrigin,      // "live_origin": samples a fresh sr_live channel behaves as having consumed before (a multiple of hop; read at open / end)
     kHookSpotLiveOrigin,  // "spot_live_origin": frames a fresh sr_spot_live channel stands at (up to 0xFFFF0000; read at open / end)
     kHookLdsPoisonLaunches,  // "lds_poison_launches": k_lds_poison in front of every kernel launch (SR_LAUNCH_POINT): bits 0..31 seed, 32..33 pattern
@@ -631,6 +631,30 @@ struct OnePassGramArgs {
 };
 // init, per block of the host's list (sweep, close), trace; w null: the unweighted kernels, otherwise the weighted sweep and trace
 void launch_onepass_gram(const OnePassGramArgs &a, const GramCosts *w, const OnePassBlock *blocks, uint32_t n_blocks, hipStream_t s);
+
+// live one-pass grammar decoding (k_onepass_gram_live.hip): k_onepass_gram.hip's blocks with the boundaries set by the caller's
+// pushes.  o is the live one-pass decoder's argument block with the history in the grammar's layout, dense by state index:
+// o.A[C][n_states][P] and o.E[C][n_states][P], P = utt_frames + 1, and o.cols[C][kept item][tpl_len]; o.feat is the channels'
+// feature rows as there; o.K is not read.  A position of A no push has reached holds all ones, E(0, 0) = 0 and E(0, s) is
+// unreachable for s != 0 (set at open and when a grammar is adopted, put back by the end call).  keep_items / keep_states as in
+// OnePassGramArgs.
+struct OnePassGramLiveArgs {
+    OnePassLiveArgs o;
+    uint32_t n_states, n_items;
+    uint32_t n_keep_items, n_keep_states;
+    const unsigned long long *masks;  // [n_sets]: the states of each charge list
+    const GramItem *items;            // [n_items], ascending (slot, target)
+    const uint8_t *final_state;       // [n_states]
+    const uint32_t *keep_items;       // [n_keep_items] indices into items, or null
+    const uint32_t *keep_states;      // [n_keep_states] states, or null
+};
+// n_blocks x (sweep where an item is kept, close where a state is kept), trace; w null: the unweighted kernels
+void launch_onepass_gram_live(const OnePassGramLiveArgs &a, const GramCosts *w, uint32_t n_blocks, hipStream_t s);
+// sr_onepass_gram_live_end: the trace of the listed channels (n = 0, x0 = the frames to parse), then the wipe
+void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s);
+// the wipe alone, over every state of the dense layout: the keys of every listed channel (first_win != 0) all ones over the
+// positions 0..aux, E(0, 0) = 0 and E(0, s) unreachable (the end call; open and a grammar switch list every channel)
+void launch_onepass_gram_live_wipe(const OnePassGramLiveArgs &a, hipStream_t s);
 
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the

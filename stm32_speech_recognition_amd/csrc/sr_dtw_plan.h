@@ -171,6 +171,7 @@ const char *forced_allow_lds(uint32_t bytes);
 const char *onepass_allow_lds(uint32_t bytes);
 const char *onepass_live_allow_lds(uint32_t bytes);
 const char *onepass_gram_allow_lds(uint32_t bytes);
+const char *onepass_gram_live_allow_lds(uint32_t bytes);
 inline const char *allow_dynamic_lds(std::initializer_list<std::pair<const void *, const char *>> kernels, uint32_t bytes)
 {
     for (const auto &k : kernels)

@@ -272,7 +272,7 @@ int sr_create(const sr_config *cfg, sr_engine **out)
     // the DTW kernels may take more than the default 64 KiB of dynamic LDS: allowed once here, for every instance
     for (auto allow : {dtw_lds_allow_lds, dtw_cells_allow_lds, dtw_quad_allow_lds, dtw_dp_allow_lds, spot_allow_lds, spot_live_allow_lds, align_allow_lds,
                        chain_allow_lds, chain_live_allow_lds, gram_allow_lds, gram_live_allow_lds, span_allow_lds, cluster_allow_lds,
-                       forced_allow_lds, onepass_allow_lds, onepass_live_allow_lds, onepass_gram_allow_lds}) {
+                       forced_allow_lds, onepass_allow_lds, onepass_live_allow_lds, onepass_gram_allow_lds, onepass_gram_live_allow_lds}) {
         if (const char *kernel = allow(h->lds.per_wg)) {
             delete h;
             return fail(SR_ERR_HIP, std::string("hipFuncSetAttribute(") + kernel + ", MaxDynamicSharedMemorySize): " + hipGetErrorString(hipGetLastError()));

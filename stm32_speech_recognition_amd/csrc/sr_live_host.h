@@ -1,7 +1,7 @@
-// What the live sessions (sr_spot_live.cpp, sr_decode_live.cpp, sr_gram_live.cpp, sr_onepass_live.cpp) do alike on the host:
-// the session core -- engine, channel plan, the PCM front end's buffers, the event that orders pushes on different streams --
+// What the live sessions (sr_spot_live.cpp, sr_decode_live.cpp, sr_gram_live.cpp, sr_onepass_live.cpp, sr_onepass_gram_live.cpp)
+// do alike on the host: the session core -- engine, channel plan, the PCM front end's buffers, the event that orders pushes on different streams --
 // with its open and release; the checks of a push's input; ONE push sequence for frames or samples, on the device or from
-// host buffers; and for the three decoders the output checks, the host forms' device copies of their outputs, the choice
+// host buffers; and for the four decoders the output checks, the host forms' device copies of their outputs, the choice
 // between the device and the host form of a push and the sequence of an end call.  A session supplies its plan, its launch and its advance; nothing here knows a session type.
 // HOST ONLY.
 #pragma once

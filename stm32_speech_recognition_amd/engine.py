@@ -919,6 +919,13 @@ class Engine:
         words_cap words of the parse (OP_LIVE_TAIL) instead of the first.  mid as for decode_live."""
         return OnePassSession(self, n_channels, chunk_max, utt_frames, words_cap, tail, skip_cost, word_cost, mid)
 
+    def decode_onepass_grammar_live(self, gram, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0,
+                                    mid=None):
+        """sr_onepass_gram_live_open: an OnePassGrammarSession -- decode_onepass_grammar() push by push, no word cap; the
+        session's set_grammar() switches the grammar between recordings.  tail and mid as for decode_onepass_live.  Close the
+        session before the grammar."""
+        return OnePassGrammarSession(self, gram, n_channels, chunk_max, utt_frames, words_cap, tail, skip_cost, word_cost, mid)
+
     # ---- full-DP alignment and word models from many examples -----------------------------------------
     def align(self, mfcc, frames, ref, ref_frames, ref_of_row=None, want_span=True):
         """OPT-IN (sr_dtw_dp_align): the optimal warping path of the full-DP scorer for every (row, reference) pair.  mfcc int16
@@ -2071,7 +2078,8 @@ class OnePassSession(DecodeSession):
 
     _PREFIX = "sr_onepass_live_"
 
-    def __init__(self, eng, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0, mid=None):
+    def __init__(self, eng, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0, mid=None, _first=()):
+        """_first: what the session's open call takes between the engine and n_channels (subclasses)"""
         self.eng, self.L, self.n_channels, self.chunk_max, self.utt_frames = eng, eng.L, n_channels, chunk_max, utt_frames
         self.max_words = self.words_cap = words_cap
         self._fn("close").restype = None
@@ -2081,7 +2089,7 @@ class OnePassSession(DecodeSession):
         self.pcm = md is not None
         self._frames = np.zeros(n_channels, np.uint32)
         l = C.c_void_p()
-        eng._check(self._fn("open")(eng.h, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames), C.c_uint32(words_cap),
+        eng._check(self._fn("open")(eng.h, *_first, C.c_uint32(n_channels), C.c_uint32(chunk_max), C.c_uint32(utt_frames), C.c_uint32(words_cap),
                                     C.c_uint32(OP_LIVE_TAIL if tail else 0), C.c_uint32(Engine._skip(skip_cost)), C.c_uint32(word_cost),
                                     _vp(md), C.byref(l)))
         self.l = l
@@ -2127,6 +2135,34 @@ class OnePassSession(DecodeSession):
         self.eng._check(self._fn("end")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(rec), _vp(words), _vp(rows), C.byref(n)))
         self._frames[rows[:n.value]["channel"]] = 0
         return dict(rec=rec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+
+def onepass_grammar_live_geometry(gram, utt_frames, chunk_max):
+    """Host-only sr_onepass_gram_live_geometry: dict(state_bytes on the device per channel, max_tpl_rows that fit, block = L,
+    launches a feature push of chunk_max frames enqueues, items and states = what the decoder keeps of the grammar)"""
+    out = (C.c_uint32 * 6)()
+    gram.eng._check(gram.L.sr_onepass_gram_live_geometry(gram.g, C.c_uint32(utt_frames), C.c_uint32(chunk_max), out))
+    return dict(state_bytes=out[0], max_tpl_rows=out[1], block=out[2], launches=out[3], items=out[4], states=out[5])
+
+
+class OnePassGrammarSession(OnePassSession):
+    """One sr_onepass_gram_live handle (Engine.decode_onepass_grammar_live): an OnePassSession under a Grammar.  After every
+    push the row of a channel is Engine.decode_onepass_grammar on everything pushed to it as one row, the grammar state after
+    each word in `reserved` (include/sr_engine.h, "live one-pass grammar decoding").  push, push_dev, push_pcm, push_pcm_dev,
+    end, frames and close are OnePassSession's; set_grammar switches the grammar while every channel is empty.  Close the
+    session before its grammar."""
+
+    _PREFIX = "sr_onepass_gram_live_"
+
+    def __init__(self, eng, gram, n_channels, chunk_max, utt_frames, words_cap, tail=False, skip_cost=None, word_cost=0, mid=None):
+        super().__init__(eng, n_channels, chunk_max, utt_frames, words_cap, tail, skip_cost, word_cost, mid, _first=(gram.g,))
+        self.gram = gram  # kept alive: the session is closed before its grammar
+
+    def set_grammar(self, gram):
+        """sr_onepass_gram_live_set_grammar: the grammar of the next dialogue state, or a fresh one in the place of a stale
+        one; raises unless every channel is empty (freshly opened or ended)"""
+        self.eng._check(self._fn("set_grammar")(self.l, gram.g))
+        self.gram = gram
 
 
 def grammar_live_geometry(gram, max_words, utt_frames, chunk_max):
