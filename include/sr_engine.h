@@ -1299,8 +1299,29 @@ int sr_decode_onepass_geometry(uint32_t tpl_rows, uint32_t K, uint32_t max_frame
  * and changes no state; a push on another stream than the last push's is ordered behind it by an event; a push to a channel
  * whose store has been replaced returns SR_ERR_BAD_ARG until that channel is ended, and it ends with the SR_CH_NONE record.
  * The session uses its engine's scratch buffers: the engine's one-caller-at-a-time rule covers its sessions.
- * Out of scope: recordings past 16 383 frames (committing and forgetting a prefix), grammars, n_words_exact, N-best
- * sequences, a "stable prefix" marker. */
+ * COMMITTED WORDS (sr_onepass_live_commit[_dev], below): the parse at N frames may change at N + 10, whole words included; a
+ * commit call says which of its words are final.  With A, E as the one-pass section defines them:
+ *   node     a position q >= 1 with A(q) reachable and A(q).cost == E(q), or 0.  end(p) = the largest node <= p: where the
+ *            trace, started at p, finds its first word.  The walk from p is end(p) -> end(start(A(end(p)))) -> ... -> 0, its
+ *            words are the words the trace writes from p.  A(p) and E(p) depend on frames < p only: a walk never changes.
+ *   window   a word over M template frames covers at most 2M - 1 input frames (one start column, then at most one
+ *            horizontal step per diagonal step), so with W = 2 * max_k M_k - 1 over the valid slots of the store the channel
+ *            is bound to, every hypothesis alive in column N - 1 started at or after N - W.
+ *   entries  the positions x in [max(0, N - W), N] where E(x) is reachable; if there are none, the single largest reachable
+ *            x <= N (position 0 always qualifies; such a recording can no longer parse).
+ *   c(N)     the deepest node shared by the walks from all entries.  The committed words are the words on the walk from
+ *            c(N), and frames = c(N): every frame below it is decided.
+ * Why they are final: the trace at any N' >= N goes down through positions where E is reachable, by one frame (a skipped
+ * frame) or from a node to the start of its word.  Let x be the first of them that is <= N.  It was reached by a one-frame
+ * step, then x = N; or as the start of a word that ends at or after frame N, then x = N or the word is alive in column N - 1
+ * and x >= N - W.  Either way x is an entry, and from x on the trace is the walk from x, which runs through c(N).  So every
+ * later parse of the recording, the end call's included, BEGINS with exactly the committed word rows, byte for byte, acc,
+ * score and cum included; c(N) never moves backwards; and c(N) is a function of the recording and N alone, so it does not
+ * depend on the chunking.  The rule is conservative by up to W frames: while N <= W nothing is committed.
+ * Out of scope: recordings past 16 383 frames (forgetting a committed prefix), n_words_exact, N-best sequences; a tighter,
+ * frontier-based marker (it needs the exact column at N - 1, which the device never has -- blocks charge nothing behind their
+ * first frame -- and would depend on the chunking); commits in grammar sessions (the node is then (position, state) and
+ * nothing else changes). */
 #define SR_OP_LIVE_TAIL 1u
 typedef struct sr_onepass_live sr_onepass_live;
 /* host-only, no device: a store of K slots whose longest template has tpl_rows rows and whose shortest valid one has
@@ -1345,6 +1366,33 @@ int sr_onepass_live_push_pcm(sr_onepass_live *l, const uint16_t *pcm, uint64_t p
  * sr_decode_live_end. */
 int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
                         sr_chain_live_row *rows, uint32_t *n_rows);
+/* The committed words of the listed channels (COMMITTED WORDS above), for feature and PCM sessions alike.  channels: a HOST
+ * list as in the end call; one row per DISTINCT listed channel at its first mention, compact.  rows[n_ch] and *n_rows are
+ * HOST outputs filled from the host mirror before the call returns -- the channel and its frames N; nothing is read back.
+ *   n_committed  the true count of committed words at N
+ *   first        the words earlier commit calls delivered for this recording
+ *   n_new        min(n_committed - first, words_cap) (the session's words_cap)
+ *   frames       c(N)
+ * d_cwords[r*words_cap + i], i < n_new, are the words first .. first + n_new - 1 in spoken order, as the trace writes them;
+ * the entries from n_new on are the all-ones row.  Per channel the session keeps a cursor on the device (8 bytes, outside
+ * sr_onepass_live_geometry's state bytes): it advances by n_new, so the words delivered over the calls, concatenated, are
+ * every committed word exactly once and in order, whatever words_cap is; a backlog drains over later calls.  A call with no
+ * push in between returns n_new 0 (once drained) and the same n_committed; an empty channel gives {0, 0, 0, 0}.
+ * sr_onepass_live_end returns what it always did and puts the cursors of the channels it ends back to zero; a caller that
+ * wants the undelivered rest at the end opens the session with SR_OP_LIVE_TAIL and words_cap >= the words it can fall behind
+ * by: the end call's record says n_words, so the rest are the last n_words - (first + n_new) entries of its row.
+ * DEVICE form: ONE asynchronous operation on `stream`, no host synchronisation; it runs behind the session's last push by
+ * the event rule of the pushes, and later pushes run behind it.  The HOST form writes host buffers and waits.
+ * Refused (SR_ERR_BAD_ARG) before anything is enqueued, nothing written, no state changed: a null required pointer, a
+ * channel past the session's last, a channel bound to a replaced store (end it first), a word map that does not fit, outputs
+ * that overlap (the host form: rows inside crec or cwords too). */
+typedef struct sr_commit_rec {
+    uint32_t n_committed, first, n_new, frames;
+} sr_commit_rec; /* 16 bytes */
+int sr_onepass_live_commit_dev(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *d_crec, sr_chain_word *d_cwords,
+                               sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_onepass_live_commit(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *crec, sr_chain_word *cwords,
+                           sr_chain_live_row *rows, uint32_t *n_rows);
 
 /* ------------------------------------------------------------------ one-pass grammar decoding: word networks without a word cap
  * OPT-IN EXTENSION, NO REFERENCE COUNTERPART.  Grammar decoding (the grammar-constrained decoding and weighted grammars
@@ -1458,7 +1506,8 @@ int sr_onepass_grammar_plan(const sr_grammar *g, uint32_t frames_cap, uint32_t o
  * Refusals come in the order stale grammar, counts, inputs, outputs, device; a refused call writes nothing and changes no
  * state.  Stream ordering is the live connected-word decoding section's.
  * Out of scope: a grammar per channel; a history compacted to the kept states; a row for the best non-final state while an
- * utterance is incomplete; n_words_exact; N-best sequences; recordings past 16 383 frames; a "stable prefix" marker. */
+ * utterance is incomplete; n_words_exact; N-best sequences; recordings past 16 383 frames; committed words
+ * (sr_onepass_live_commit's rule with (position, state) for a node: a follow-up). */
 typedef struct sr_onepass_gram_live sr_onepass_gram_live;
 /* host-only, no device.  out[0] = device state bytes per channel, S x (utt_frames + 1) x 12 + kept items x tpl_len x 16 +
  * utt_frames x 24, saturating; out[1] = the longest template that fits (sr_spot_geometry's out[2]); out[2] = L; out[3] = the

@@ -15,6 +15,8 @@
 //                          sweep of this push reads at those columns;
 //   k_onepass_live_trace   k_onepass_trace with N = x0 + n into the compact row the host assigned, the first words_cap words
 //                          or (tail) the last.
+//   k_onepass_live_commit  (sr_onepass_live_commit, a call of its own behind a push) the words of the listed channels that no
+//                          later frame can change, from A, E and N alone: see the kernel.
 // No init launch: a position of A that no push has reached holds all ones from the open call on, and the end call puts that
 // back (k_onepass_live_wipe); E(0) = 0 never changes.  No workgroup waits on another: the blocks are ordered by the stream
 // alone.  Plain vector stores; the atomic minimum on A is the only atomic, and it does not depend on the order of the waves, so
@@ -217,14 +219,120 @@ __global__ void __launch_bounds__(64) k_onepass_live_trace(const OnePassLiveArgs
     if (lane == 0) *rec = sr_chain_rec{total, n, N - in_words, n > W ? SR_CH_TRUNCATED : SR_CH_OK};
 }
 
-// sr_onepass_live_end, behind the trace: the keys of every listed channel are all ones again over the positions it had reached
-__global__ void __launch_bounds__(256) k_onepass_live_wipe(const OnePassLiveArgs a)
+// sr_onepass_live_end, behind the trace: the keys of every listed channel are all ones again over the positions it had reached,
+// and its commit cursor says "nothing delivered"
+__global__ void __launch_bounds__(256) k_onepass_live_wipe(const OnePassLiveArgs a, uint2 *cursor)
 {
     const uint32_t c = blockIdx.x;
     const SpotLiveChan ch = a.chan[c];
     if (!ch.first_win) return;
     unsigned long long *A = a.A + (size_t)c * a.P;
     for (uint32_t p = 1 + threadIdx.x; p <= ch.aux; p += 256) A[p] = kSpotInf;  // aux <= utt_frames = P - 1
+    if (threadIdx.x == 0) cursor[c] = uint2{0u, 0u};
+}
+
+// ---- sr_onepass_live_commit: the words that can no longer change ------------------------------------------------------------
+// A NODE is a position q >= 1 whose own word closes E there (onepass_word_at's hit), or 0; end(p) = the first node at or below
+// p; the parent of a node is end(the start of its word).  Parents lie strictly below their children, and A(p), E(p) depend on
+// frames < p only, so the tree never changes where it stands.  The rule (include/sr_engine.h): every hypothesis alive in the last
+// column started inside the window [lo, N], lo = max(0, N - W); the entries are the positions of the window where E is
+// reachable (none: the last reachable position below it); the commit node c is the deepest node shared by the walks from
+// end(x) of all entries x.
+//
+// What the kernel makes of it, one wave per listed channel, every loop wave-uniform (N, W, ballots and shuffled keys only):
+//   * a hit is reachable, so the entry nodes are the hits of the window and -- unless the lowest reachable position of the
+//     window is itself a hit -- end(lo - 1), the node below the window.  With nothing reachable in the window that node is c.
+//   * a hit whose word starts at or above the window's first hit has its parent inside the window: the parent is an entry node
+//     too, and the child adds nothing to what all walks share.  The others are the ROOTS, where a walk leaves the window.
+//   * c = the common node of the roots and the node below, folded pair by pair: while two nodes differ, the one at the higher
+//     position goes to its parent.  That cannot step over the common node: the common node is a proper ancestor of any node
+//     above it on either walk, and a parent lies below its child.
+// Then two walks from c down to the cursor's node, as the trace walks: the count, then the earliest words_cap pending words.
+
+// the parent of the node whose key is *key; *key becomes the parent's (unchanged garbage for node 0, which has no word)
+__device__ __forceinline__ uint32_t commit_parent(const unsigned long long *A, const uint32_t *E, uint32_t lane, uint64_t *key)
+{
+    const uint32_t start = (uint32_t)(*key >> 16) & 0xFFFFu;  // < the node's position: the walk ends
+    return onepass_word_at(A, E, start, lane, key);
+}
+
+// (*cur, *cur_key) becomes the common node of itself and (q, key); kChainNone: no node yet
+__device__ __forceinline__ void commit_join(const unsigned long long *A, const uint32_t *E, uint32_t lane, uint32_t *cur, uint64_t *cur_key,
+                                            uint32_t q, uint64_t key)
+{
+    if (*cur == kChainNone) {
+        *cur = q;
+        *cur_key = key;
+        return;
+    }
+    while (*cur != q) {  // (uniform)
+        if (*cur > q)
+            *cur = commit_parent(A, E, lane, cur_key);
+        else
+            q = commit_parent(A, E, lane, &key);
+    }
+}
+
+__global__ void __launch_bounds__(64) k_onepass_live_commit(const OnePassCommitArgs a)
+{
+    const uint32_t lane = threadIdx.x, cap = a.words_cap;
+    const sr_chain_live_row row = a.rows[blockIdx.x];
+    const uint32_t c = row.channel, N = row.frames;  // N <= utt_frames = P - 1: no position past the history is read
+    const unsigned long long *A = a.A + (size_t)c * a.P;
+    const uint32_t *E = a.E + (size_t)c * a.P;
+    sr_chain_word *words = a.cwords + (size_t)blockIdx.x * cap;
+    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const uint32_t lo = N > a.W ? N - a.W : 0u;
+
+    uint32_t first_hit = kChainNone, low_reach = kChainNone;  // of the window
+    uint32_t cur = kChainNone;                                // the common node so far
+    uint64_t cur_key = kSpotInf;
+    for (uint32_t x0 = lo; x0 <= N; x0 += 64) {  // (uniform) the window, 64 positions per round, coalesced
+        const uint32_t x = x0 + lane;
+        const bool in = x <= N;
+        const uint32_t e = in ? E[x] : kChainNone;
+        const uint64_t ky = in && x ? A[x] : kSpotInf;  // position 0 ends no word
+        const bool hit = ky != kSpotInf && (uint32_t)(ky >> 32) == e;
+        const unsigned long long hits = __ballot(hit), reach = __ballot(e != kChainNone);
+        if (low_reach == kChainNone && reach) low_reach = x0 + (uint32_t)__ffsll((long long)reach) - 1u;
+        if (first_hit == kChainNone && hits) first_hit = x0 + (uint32_t)__ffsll((long long)hits) - 1u;
+        unsigned long long roots = __ballot(hit && ((uint32_t)(ky >> 16) & 0xFFFFu) < first_hit);
+        while (roots) {  // (uniform)
+            const uint32_t b = (uint32_t)__ffsll((long long)roots) - 1u;
+            roots &= roots - 1;
+            commit_join(A, E, lane, &cur, &cur_key, x0 + b, spot_shfl(ky, b));
+        }
+    }
+    if (first_hit == kChainNone || low_reach != first_hit) {  // (uniform) the node below the window is an entry node, or c itself
+        uint64_t key = kSpotInf;
+        const uint32_t below = lo ? onepass_word_at(A, E, lo - 1u, lane, &key) : 0u;
+        commit_join(A, E, lane, &cur, &cur_key, below, key);
+    }
+
+    const uint2 cu = a.cursor[c];  // {delivered, the last delivered word's node}: an ancestor of c, or c
+    uint32_t pending = 0;
+    {
+        uint64_t key = cur_key;
+        for (uint32_t q = cur; q > cu.y; q = commit_parent(A, E, lane, &key)) pending++;  // (uniform)
+    }
+    const uint32_t n_new = pending < cap ? pending : cap;
+    for (uint32_t i = n_new + lane; i < cap; i += 64) words[i] = none;
+    uint32_t last_node = cu.y, j = pending;  // the words on the walk are pending words j - 1 .. 0, the earliest n_new are written
+    uint64_t key = cur_key;
+    for (uint32_t q = cur; q > cu.y; q = commit_parent(A, E, lane, &key)) {  // (uniform)
+        j--;
+        if (j >= n_new) continue;
+        if (j == n_new - 1u) last_node = q;
+        if (lane == 0) {
+            const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu, end = q - 1;
+            const uint32_t acc = (uint32_t)(key >> 32) - a.word_cost - E[start];
+            words[j] = sr_chain_word{a.word_id[a.group_of_slot[slot]], slot, start, end, acc, acc / (end - start + 1 + a.tpl_frames[slot]), E[q], 0u};
+        }
+    }
+    if (lane == 0) {
+        a.crec[blockIdx.x] = sr_commit_rec{cu.x + pending, cu.x, n_new, cur};
+        a.cursor[c] = uint2{cu.x + n_new, last_node};
+    }
 }
 
 void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_t s)
@@ -241,13 +349,19 @@ void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_
     SR_LAUNCH_POINT(s, "k_onepass_live_trace");
     hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
 }
-void launch_onepass_live_end(const OnePassLiveArgs &a, hipStream_t s)
+void launch_onepass_live_end(const OnePassLiveArgs &a, uint2 *cursor, hipStream_t s)
 {
     if (!a.C) return;
     SR_LAUNCH_POINT(s, "k_onepass_live_trace");
     hipLaunchKernelGGL(k_onepass_live_trace, dim3(a.C), dim3(64), 0, s, a);
     SR_LAUNCH_POINT(s, "k_onepass_live_wipe");
-    hipLaunchKernelGGL(k_onepass_live_wipe, dim3(a.C), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_onepass_live_wipe, dim3(a.C), dim3(256), 0, s, a, cursor);
+}
+void launch_onepass_live_commit(const OnePassCommitArgs &a, hipStream_t s)
+{
+    if (!a.n_rows) return;
+    SR_LAUNCH_POINT(s, "k_onepass_live_commit");
+    hipLaunchKernelGGL(k_onepass_live_commit, dim3(a.n_rows), dim3(64), 0, s, a);
 }
 const char *onepass_live_allow_lds(uint32_t bytes)
 {

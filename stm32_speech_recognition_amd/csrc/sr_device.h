@@ -531,7 +531,29 @@ struct OnePassLiveArgs {
 void launch_onepass_live(const OnePassLiveArgs &a, uint32_t n_blocks, hipStream_t s);  // n_blocks x (words, close), trace
 // sr_onepass_live_end: the trace of the listed channels (n = 0, x0 = the frames to parse), then all ones over their keys again
 // (positions 1..aux: the frames the channel held)
-void launch_onepass_live_end(const OnePassLiveArgs &a, hipStream_t s);
+// cursor[C]: the commit cursors (below), which the wipe zeroes for the listed channels
+void launch_onepass_live_end(const OnePassLiveArgs &a, uint2 *cursor, hipStream_t s);
+
+// sr_onepass_live_commit[_dev] (k_onepass_live_commit): the words of the listed channels that can no longer change.  It reads the
+// history A / E of OnePassLiveArgs and the host's rows -- the channel and its frames N -- and keeps per channel a cursor
+// {words delivered so far, the position of the last delivered word's node}, all zero for a channel without a recording.
+struct OnePassCommitArgs {
+    const sr_chain_live_row *rows;  // [n_rows] on the device: the distinct listed channels and their N
+    uint32_t n_rows;
+    uint32_t P;                     // utt_frames + 1: positions of the history
+    uint32_t W;                     // the window: 2 * (the longest valid template's frames) - 1, 0 without a valid slot
+    uint32_t words_cap;
+    uint32_t word_cost;
+    const unsigned long long *A;
+    const uint32_t *E;
+    uint2 *cursor;                  // [C]
+    const uint32_t *tpl_frames;
+    const uint32_t *group_of_slot;
+    const uint32_t *word_id;
+    sr_commit_rec *crec;            // [n_rows]
+    sr_chain_word *cwords;          // [n_rows][words_cap]
+};
+void launch_onepass_live_commit(const OnePassCommitArgs &a, hipStream_t s);
 
 // grammar-constrained decoding (k_gram.hip): k_chain's levels over a word network of n_states states.  c is the decoder's
 // argument block with the scratch in the grammar's layout: c.A[row][level 1..max_words][state][max_frames + 1], c.E[row][level

@@ -22,6 +22,9 @@ struct sr_onepass_live : LiveCore {
     DevBuf<unsigned long long> A;         // [C][utt_frames + 1]
     DevBuf<uint32_t> E;                   // [C][utt_frames + 1]
     DevBuf<int16_t> hist;                 // [C][utt_frames][12]: the channels' feature rows
+    // sr_onepass_live_commit: per channel {words delivered, the last delivered word's node}, and the rows of the call in flight
+    DevBuf<uint2> cursor;                 // [C]
+    DevBuf<sr_chain_live_row> commit_rows;  // [C]
 };
 
 namespace {
@@ -102,6 +105,48 @@ int push(sr_onepass_live *l, const LiveIn &in, bool device, void *stream, const 
         [&] { onepass_live_advance(l->om, pl, rows, n_rows); });
 }
 
+// a commit call up to its launch: the rows of the distinct listed channels from the mirror, then the checks -- nothing is
+// enqueued, written or changed before all of them pass.  host: rows is a host buffer like crec and cwords (the host form)
+int plan_commit(const sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, const sr_commit_rec *crec, const sr_chain_word *cwords,
+                const sr_chain_live_row *rows, bool host, std::vector<sr_chain_live_row> *order)
+{
+    if (!l || (n_ch && !channels)) return fail(SR_ERR_BAD_ARG, "null argument");
+    std::string why;
+    if (!onepass_live_commit_list(l->om, l->h->store_serial, channels, n_ch, order, &why)) return fail(SR_ERR_BAD_ARG, why);
+    const size_t n_out = order->size();
+    if (!n_out) return SR_OK;
+    if (!crec || !cwords || !rows) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (int rc = check_store(l)) return rc;
+    const size_t n_c = n_out * sizeof *crec, n_w = n_out * l->words_cap * sizeof *cwords, n_r = n_out * sizeof *rows;
+    if (live_overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
+    if (host && (live_overlap(rows, n_r, crec, n_c) || live_overlap(rows, n_r, cwords, n_w)))
+        return fail(SR_ERR_BAD_ARG, "rows overlaps crec or cwords");
+    return SR_OK;
+}
+
+// ... and the launch on s: behind the session's last push or commit, and the next one runs behind it
+int enqueue_commit(sr_onepass_live *l, const std::vector<sr_chain_live_row> &order, sr_commit_rec *d_crec, sr_chain_word *d_cwords, hipStream_t s)
+{
+    const sr_engine *h = l->h;
+    if (int rc = l->order_after_last_push(s)) return rc;
+    // (a pageable source is staged before the call returns: the list may go out of scope)
+    HIP_TRY(hipMemcpyAsync(l->commit_rows.p, order.data(), order.size() * sizeof(sr_chain_live_row), hipMemcpyHostToDevice, s));
+    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    launch_onepass_live_commit(
+        OnePassCommitArgs{l->commit_rows.p, (uint32_t)order.size(), l->om.d.utt_frames + 1u, onepass_commit_window(h->tpl_len_host.data(), h->K),
+                          l->words_cap, l->word_cost, l->A.p, l->E.p, l->cursor.p, h->tpl_frames.p, t + h->K + 2 * (size_t)h->wg_words + 1,
+                          t + h->K + h->wg_words + 1, d_crec, d_cwords},
+        s);
+    HIP_TRY(hipGetLastError());
+    return l->mark_push(s);
+}
+
+void label_commit(const std::vector<sr_chain_live_row> &order, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    for (size_t r = 0; r < order.size(); r++) rows[r] = order[r];
+    if (n_rows) *n_rows = (uint32_t)order.size();
+}
+
 }  // namespace
 
 extern "C" {
@@ -151,10 +196,13 @@ int sr_onepass_live_open(sr_engine *h, uint32_t n_channels, uint32_t chunk_max, 
     if (!rc) rc = l->A.reserve((size_t)n_channels * P);
     if (!rc) rc = l->E.reserve((size_t)n_channels * P);
     if (!rc) rc = l->hist.reserve((size_t)n_channels * utt_frames * kCoef);
+    if (!rc) rc = l->cursor.reserve(n_channels);
+    if (!rc) rc = l->commit_rows.reserve(n_channels);
     // no word yet anywhere, E(0) = 0: the state of an empty channel, which a push finds without a launch of its own (every other
     // position of E is written before it is read)
     if (!rc && (hipMemsetAsync(l->A.p, 0xFF, (size_t)n_channels * P * 8, nullptr) != hipSuccess ||
-                hipMemsetAsync(l->E.p, 0, (size_t)n_channels * P * 4, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
+                hipMemsetAsync(l->E.p, 0, (size_t)n_channels * P * 4, nullptr) != hipSuccess ||
+                hipMemsetAsync(l->cursor.p, 0, (size_t)n_channels * sizeof(uint2), nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
         rc = fail(SR_ERR_HIP, "clearing the session's history failed");
     if (rc) {
         (void)hipGetLastError();
@@ -175,6 +223,8 @@ void sr_onepass_live_close(sr_onepass_live *l)
     l->A.release();
     l->E.release();
     l->hist.release();
+    l->cursor.release();
+    l->commit_rows.release();
     delete l;
 }
 
@@ -220,8 +270,43 @@ int sr_onepass_live_end(sr_onepass_live *l, const uint32_t *channels, uint32_t n
     return live_end(
         *l, chan, order, l->words_cap, rec, words, nullptr, rows, n_rows,
         [&] { return l->layout_serial != h->store_serial ? relayout(l) : SR_OK; },
-        [&](sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) { launch_onepass_live_end(live_args(l, nullptr, 0, 1u, d_rec, d_words), nullptr); },
+        [&](sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+            launch_onepass_live_end(live_args(l, nullptr, 0, 1u, d_rec, d_words), l->cursor.p, nullptr);
+        },
         [&] { onepass_live_reset(l->om, h->store_serial, order); });
+}
+
+int sr_onepass_live_commit_dev(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *d_crec, sr_chain_word *d_cwords,
+                               sr_chain_live_row *rows, uint32_t *n_rows, void *stream)
+{
+    std::vector<sr_chain_live_row> order;
+    if (int rc = plan_commit(l, channels, n_ch, d_crec, d_cwords, rows, false, &order)) return rc;
+    if (!order.empty()) {
+        ENTER_DEVICE(l->h);
+        if (int rc = enqueue_commit(l, order, d_crec, d_cwords, (hipStream_t)stream)) return rc;
+    }
+    label_commit(order, rows, n_rows);
+    return SR_OK;
+}
+
+int sr_onepass_live_commit(sr_onepass_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *crec, sr_chain_word *cwords,
+                           sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    std::vector<sr_chain_live_row> order;
+    if (int rc = plan_commit(l, channels, n_ch, crec, cwords, rows, true, &order)) return rc;
+    if (!order.empty()) {
+        ENTER_HOST_CALL(l->h);
+        const size_t n_out = order.size(), n_w = n_out * l->words_cap;
+        TmpDevBuf<sr_commit_rec> d_crec;  // per-call device copies of the outputs, reserved before anything is enqueued
+        TmpDevBuf<sr_chain_word> d_cwords;
+        if (int rc = d_crec.reserve(n_out)) return rc;
+        if (int rc = d_cwords.reserve(n_w)) return rc;
+        if (int rc = enqueue_commit(l, order, d_crec.p, d_cwords.p, nullptr)) return rc;
+        COPY_DOWN(crec, d_crec.p, n_out * sizeof *crec);
+        COPY_DOWN(cwords, d_cwords.p, n_w * sizeof *cwords);
+    }
+    label_commit(order, rows, n_rows);
+    return SR_OK;
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // The host mirror of a live one-pass decoding session (sr_onepass_live.cpp) and what it says about a call before anything
 // reaches the device: which channels a push touches, where each stands, which compact output row it gets, how its new frames
-// are cut into blocks, and why a push is refused; the distinct channels of an end list.  The host knows every count -- and the
-// first frame of the block each channel's saved columns are of -- so nothing is read back.
-// HOST ONLY, and free of HIP calls: tests/onepass_live_plan/plan_check.cpp runs it on the CPU under the sanitizers.
+// are cut into blocks, and why a push is refused; the distinct channels of an end list and of a commit list.  The host knows
+// every count -- and the first frame of the block each channel's saved columns are of -- so nothing is read back.
+// HOST ONLY, and free of HIP calls: tests/onepass_live_plan/plan_check.cpp and tests/onepass_commit_plan/plan_check.cpp run it
+// on the CPU under the sanitizers.
 //
 // The cut.  The decode session's mirror and rules (sr_decode_live_plan.h) serve unchanged; on top of them a push's new frames
 // [x0, x0 + n) of a channel are cut into blocks of `block` frames, block = min(L, the testing hook) with L the block length of
@@ -84,6 +85,43 @@ inline void onepass_live_reset(OnePassLiveMirror &m, uint64_t store_serial, cons
 {
     decode_live_reset(m.d, store_serial, order);
     for (const sr_chain_live_row &r : order) m.c0_prev[r.channel] = 0;
+}
+
+// sr_onepass_live_commit: the window of the commit rule for a store, W = 2 * (the longest valid template's frames) - 1 -- a
+// word over M template frames covers at most 2M - 1 input frames -- with tpl_len[k] = the frames of a valid slot, 0 for an
+// invalid one.  0: no valid slot
+inline uint32_t onepass_commit_window(const uint32_t *tpl_len, uint32_t K)
+{
+    uint32_t longest = 0;
+    for (uint32_t k = 0; k < K; k++) longest = std::max(longest, tpl_len[k]);
+    return longest ? 2u * longest - 1u : 0u;
+}
+
+// ... and its rows: one per DISTINCT listed channel, in the order of first mention, with the frames the channel holds.  The
+// mirror is not changed.  Returns false for a channel past the session's last and for one bound to a replaced store (its
+// history speaks of slots that are gone: end it first).
+inline bool onepass_live_commit_list(const OnePassLiveMirror &m, uint64_t store_serial, const uint32_t *channels, uint32_t n_ch,
+                                     std::vector<sr_chain_live_row> *order, std::string *why)
+{
+    order->clear();
+    for (uint32_t i = 0; i < n_ch; i++) {
+        if (channels[i] >= m.d.C) {
+            *why = "channel " + std::to_string(channels[i]) + " is past the session's last";
+            return false;
+        }
+        if (m.d.bound[channels[i]] != store_serial) {
+            *why = "the template store changed: end channel " + std::to_string(channels[i]) + " before committing on it";
+            return false;
+        }
+    }
+    std::vector<uint8_t> listed(m.d.C, 0);
+    for (uint32_t i = 0; i < n_ch; i++) {
+        const uint32_t c = channels[i];
+        if (listed[c]) continue;  // listed before: it counts once
+        listed[c] = 1;
+        order->push_back(sr_chain_live_row{c, m.d.frames[c]});
+    }
+    return true;
 }
 
 // sr_onepass_live_geometry's out[0]: per channel the history (u64 keys and u32 prefix costs over utt_frames + 1 positions), one

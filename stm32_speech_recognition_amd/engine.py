@@ -53,6 +53,10 @@ OP_LIVE_TAIL = 1  # sr_onepass_live_open flag: the last words_cap words instead
 VAD_MASK_WORDS, VAD_MASK_FRAMES = 16, 63
 # sr_chain_live_row: which channel an emitted row of a live decoding session holds, and its frames after the push
 CHAIN_LIVE_ROW_DTYPE = np.dtype([("channel", "<u4"), ("frames", "<u4")])
+# sr_commit_rec: the committed words of a channel of a live one-pass session -- how many, how many of them earlier calls
+# delivered, how many this call delivers, and the position below which every frame is decided
+COMMIT_REC_DTYPE = np.dtype([("n_committed", "<u4"), ("first", "<u4"), ("n_new", "<u4"), ("frames", "<u4")])
+assert COMMIT_REC_DTYPE.itemsize == 16
 # sr_score_word_spans / sr_decode_words_alts modes: a span score row holds path costs, or costs / (L + M)
 SPAN_ACC, SPAN_DIS = 0, 1
 assert RESULT_DTYPE.itemsize == 16 and VAD_DTYPE.itemsize == 48 and SPOT_DTYPE.itemsize == 16
@@ -2074,7 +2078,8 @@ class OnePassSession(DecodeSession):
     """One sr_onepass_live handle (Engine.decode_onepass_live): one-pass connected-word decoding over chunked features or
     samples, no word cap.  After every push the row of a channel is Engine.decode_onepass on everything pushed to it as one row
     (include/sr_engine.h, "live one-pass connected-word decoding").  push, push_dev, push_pcm, push_pcm_dev, frames and close
-    are DecodeSession's; the rows carry no level costs: dict(rec, words [n_rows, words_cap], rows, n_rows)."""
+    are DecodeSession's; the rows carry no level costs: dict(rec, words [n_rows, words_cap], rows, n_rows).  commit and
+    commit_dev say which words of a channel's parse no later frame can change."""
 
     _PREFIX = "sr_onepass_live_"
 
@@ -2136,6 +2141,41 @@ class OnePassSession(DecodeSession):
         self._frames[rows[:n.value]["channel"]] = 0
         return dict(rec=rec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
 
+    def _commit_list(self, channels):
+        ch = np.arange(self.n_channels, dtype=np.uint32) if channels is None else np.ascontiguousarray(np.atleast_1d(channels), dtype=np.uint32)
+        return ch, max(len(ch), 1)
+
+    def commit(self, channels=None):
+        """sr_onepass_live_commit: the words of the listed channels (None: every channel) that no later frame can change.
+        Returns dict(crec COMMIT_REC_DTYPE [n_rows], words CHAIN_WORD_DTYPE [n_rows, words_cap], rows CHAIN_LIVE_ROW_DTYPE
+        [n_rows], n_rows): one row per distinct listed channel; words holds the crec["n_new"] committed words that no earlier
+        call delivered, crec["first"] the index of the first of them."""
+        ch, cap = self._commit_list(channels)
+        crec, words = np.zeros(cap, dtype=COMMIT_REC_DTYPE), np.zeros((cap, self.words_cap), dtype=CHAIN_WORD_DTYPE)
+        rows, n = np.zeros(cap, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(self._fn("commit")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(crec), _vp(words), _vp(rows), C.byref(n)))
+        return dict(crec=crec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
+
+    def commit_dev(self, channels=None, stream=None):
+        """sr_onepass_live_commit_dev: as commit(), asynchronous on `stream` (a torch.cuda.Stream, or the current one) behind the
+        session's last push.  Returns dict(crec int32 [n_rows, 4], words int32 [n_rows, words_cap, 8] -- device tensors -- rows,
+        n_rows on the host)."""
+        import torch
+        ch, cap = self._commit_list(channels)
+        d = self.eng.cfg.device
+        dev = torch.device("cuda", d if d >= 0 else torch.cuda.current_device())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        crec = torch.empty(cap, 4, dtype=torch.int32, device=dev)
+        words = torch.empty(cap, self.words_cap, 8, dtype=torch.int32, device=dev)
+        rows, n = np.zeros(cap, dtype=CHAIN_LIVE_ROW_DTYPE), C.c_uint32(0)
+        self.eng._check(self._fn("commit_dev")(self.l, _vp(ch), C.c_uint32(len(ch)), _vp(crec), _vp(words), _vp(rows), C.byref(n),
+                                               C.c_void_p(getattr(stream, "cuda_stream", stream))))
+        if isinstance(stream, torch.cuda.Stream):
+            for t in (crec, words):
+                t.record_stream(stream)  # allocated on the current stream, used on `stream`
+        return dict(crec=crec[:n.value], words=words[:n.value], rows=rows[:n.value], n_rows=n.value)
+
 
 def onepass_grammar_live_geometry(gram, utt_frames, chunk_max):
     """Host-only sr_onepass_gram_live_geometry: dict(state_bytes on the device per channel, max_tpl_rows that fit, block = L,
@@ -2163,6 +2203,11 @@ class OnePassGrammarSession(OnePassSession):
         one; raises unless every channel is empty (freshly opened or ended)"""
         self.eng._check(self._fn("set_grammar")(self.l, gram.g))
         self.gram = gram
+
+    def commit(self, channels=None, stream=None):
+        raise SrError("grammar sessions have no commit call (include/sr_engine.h, live one-pass section: out of scope)")
+
+    commit_dev = commit
 
 
 def grammar_live_geometry(gram, max_words, utt_frames, chunk_max):
