@@ -5,10 +5,6 @@
 
 #include <type_traits>
 
-#ifndef SR_MEL_CHUNKED
-#define SR_MEL_CHUNKED 1  // experiment switch (profiles/experiments/RESULTS.md, round 6): 0 = bin-major scratch order of round 5
-#endif
-
 namespace sr {
 
 // ------------------------------------------------------------------------------------------------
@@ -45,7 +41,8 @@ static_assert(SR_MFCC_PIPE_VMCNT == 0 || (SR_MFCC_PIPE_VMCNT == 3 && SR_MFCC_PIP
 constexpr bool mfcc_pipelined(int fpw) { return SR_MFCC_PIPE && mfcc_tab_bins(fpw) == 8; }
 // switches of round 11, which cut the cycles a frame keeps the CU's LDS pipe busy (RESULTS.md, round 11):
 // SR_MFCC_TM_REGS 1 = the batch form keeps the QUIET tier's sixteen filterbank multipliers in VGPRs, not in s_tm;
-// SR_MFCC_PREFIX_TID: below.  Kept together: alone they are worth +0.7 % and -0.5 % of the step, the two -2.0 %.
+// the other half of that round is mel_prefix_store below.  Kept together: alone they are worth +0.7 % and -0.5 % of the step,
+// the two -2.0 %.
 #ifndef SR_MFCC_TM_REGS
 #define SR_MFCC_TM_REGS 1
 #endif
@@ -59,34 +56,18 @@ constexpr bool mfcc_tm_regs(int fpw) { return SR_MFCC_TM_REGS && mfcc_pipelined(
 // 6 different frames x 12 different coefficients rows at the same column, and a stride of 24 folds those onto 4 banks
 constexpr int kMelPad = kMel + 1;
 // the windowed frame aliases the exchange area; the last 64 words hold the odd filters' lane offsets
-// Scratch order of the filterbank stage (energies, then the in-lane prefixes): bin j = 8 l + k sits in chunk k >> 2 (256 words
-// each) at 16-byte slot l ^ (4 (k >> 2)), word k & 3.  Lane l's two 16-byte reads and its prefix stores are then lane-contiguous
-// chunks (conflict-free; bin-major order put two lanes of every service group on the same banks), and the slot swizzle of
-// chunk 1 makes the magnitude stage's 4-byte stores -- 32 consecutive bins per service group = 4 lanes' slots x both chunks --
-// hit 32 different banks as well.
-__device__ __forceinline__ constexpr int mel_chunk_word(int j) { return 256 * ((j >> 2) & 1) + 4 * ((j >> 3) ^ (4 * ((j >> 2) & 1))) + (j & 3); }
-// SR_MFCC_PREFIX_TID 1 (round 11): the sixteen in-lane prefixes of a lane leave as sixteen lane-contiguous 4-byte stores
-// (ds_write_addtid_b32, 2 cycles of the CU's store path each) instead of four ds_write_b128 (13 each): prefix P[j] of bin
-// j = 8 l + k sits at word 64 k + l of its poly-line's half.  The look-up's addresses are lane constants in any order; in
-// this one its 24 lanes meet on a bank two at a time at most (three in the chunked order).  The energies keep their order.
-#ifndef SR_MFCC_PREFIX_TID
-#define SR_MFCC_PREFIX_TID 1
-#endif
-__device__ __forceinline__ constexpr int mel_prefix_word(int j)
-{
-#if SR_MFCC_PREFIX_TID
-    return 64 * (j & 7) + (j >> 3);
-#elif SR_MEL_CHUNKED
-    return mel_chunk_word(j);
-#else
-    return j;
-#endif
-}
+// Scratch order of the filterbank stage.  Both of its stores are lane-contiguous (ds_write_addtid_b32, 2 cycles of the CU's
+// store path each; a 4-byte store with an address register takes 4, a 16-byte one 13):
+//   energies  (round 12) bin b at word energy_word(b) of sr_fft_layout.h -- mel_energy_store below
+//   prefixes  (round 11) the in-lane prefix P[j] of bin j = 8 l + k at word 64 k + l of its poly-line's half.  The look-up's
+//             addresses are lane constants in any order; in this one its 24 lanes meet on a bank two at a time at most.
+__device__ __forceinline__ constexpr int mel_prefix_word(int j) { return 64 * (j & 7) + (j >> 3); }
 // The stores: lane l writes pe[k] to word 64 k + l and po[k] to word kBins + 64 k + l of the area at LDS byte address `base`
 // (wave-uniform).  ds_write_addtid_b32's address is M0 + offset + 4 * lane: no address VGPR goes to the LDS.  M0 is set in
 // the same statement (one wait state before an add-TID instruction reads it) and named as clobbered.  The compiler treats M0
 // as reserved and says so about the clobber; it has no use of M0 of its own in this kernel -- no LDS bounds on gfx9+, no
-// movrel, no message, no LDS-DMA: `m0` occurs in the kernel's assembly in this statement only.  Look again after adding any
+// movrel, no message, no LDS-DMA: `m0` occurs in the kernel's assembly in the three add-TID statements only (this one,
+// mel_energy_store, fft_exchange_tid of sr_fft_dev.h).  Look again after adding any
 // of those.  The wave's LDS operations complete in issue order, so a wait the compiler counts for its own reads, which does
 // not know of these stores, can only come out stricter.
 #pragma clang diagnostic push
@@ -104,6 +85,22 @@ __device__ __forceinline__ void mel_prefix_store(uint32_t base, const uint32_t (
                  :
                  : "v"(pe[0]), "v"(pe[1]), "v"(pe[2]), "v"(pe[3]), "v"(pe[4]), "v"(pe[5]), "v"(pe[6]), "v"(pe[7]), "v"(po[0]),
                    "v"(po[1]), "v"(po[2]), "v"(po[3]), "v"(po[4]), "v"(po[5]), "v"(po[6]), "v"(po[7]), "s"(base)
+                 : "m0", "memory");
+}
+// The energies, stored the same way (sr_fft_layout.h): magnitude lane l' holds en[2 e3 + half] of bin l' + 64 e3 + 256 half,
+// plane q = e3 + 4 half lies at word energy_plane(q) + l'.  Filter lane l then reads its bins 8 l .. 8 l + 7 as two 16-byte
+// words from energy_read_base(l) on; the plane bases keep those reads conflict-free.
+__device__ __forceinline__ void mel_energy_store(uint32_t base, const uint32_t (&en)[8])
+{
+    static_assert(4 * energy_plane(1) == 256 && 4 * energy_plane(2) == 528 && 4 * energy_plane(3) == 784 && 4 * energy_plane(4) == 1040 &&
+                      4 * energy_plane(5) == 1296 && 4 * energy_plane(6) == 1568 && 4 * energy_plane(7) == 1824 && kBins == kEnergyBins,
+                  "the offsets below are written out for these plane bases");
+    asm volatile("s_mov_b32 m0, %8\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %0\n\tds_write_addtid_b32 %1 offset:256\n\tds_write_addtid_b32 %2 offset:528\n\t"
+                 "ds_write_addtid_b32 %3 offset:784\n\tds_write_addtid_b32 %4 offset:1040\n\tds_write_addtid_b32 %5 offset:1296\n\t"
+                 "ds_write_addtid_b32 %6 offset:1568\n\tds_write_addtid_b32 %7 offset:1824"
+                 :
+                 : "v"(en[0]), "v"(en[2]), "v"(en[4]), "v"(en[6]), "v"(en[1]), "v"(en[3]), "v"(en[5]), "v"(en[7]), "s"(base)
                  : "m0", "memory");
 }
 #pragma clang diagnostic pop
@@ -167,12 +164,13 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
 
     // ---- lane-invariant constants --------------------------------------------------------------
     LaneTw tw;
-    load_lane_tw(a.t, lane, tw);
+    load_lane_tw(a.t, lane, lane >> 4, tw);  // front lane = d3 + 4 d4 + 16 d0 (sr_fft_layout.h)
     real_leg_tw(tw);  // pass 2 multiplies duplicated real legs (sr_fft_dev.h window_store)
-    if (w == 0 && lane < 4) {
+    if (w == 0 && (lane & 15) == 0) {  // the four pass-3 rows, from lanes with d0 = 0..3
         const uint32_t *f = &tw.s3[0][0][0];
+        const int d0 = lane >> 4;
 #pragma unroll
-        for (int c = 0; c < 8; c++) s_tw3[lane * kTw3Row + c] = u32x4{f[4 * c], f[4 * c + 1], f[4 * c + 2], f[4 * c + 3]};
+        for (int c = 0; c < 8; c++) s_tw3[d0 * kTw3Row + c] = u32x4{f[4 * c], f[4 * c + 1], f[4 * c + 2], f[4 * c + 3]};
     }
     if (w == 1 % kMfccWaves) store_tw32(s_tw5, lane, tw.s5);
     // triangle weights of bins 8*lane .. 8*lane+7 of both poly-lines as fused multipliers ceil(tri * 2^28 / 100)
@@ -238,16 +236,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
     const uint64_t mag_p = (uint64_t)a.mag_q;
     const u32x4 mag_rs = {(uint32_t)mag_p, (uint32_t)(mag_p >> 32) | (2u << 16), kMagTabEntries, 0x00027000u};
     const uint32_t tw_off = 32u * (uint32_t)lane;  // byte offset of the lane's eight raw filterbank weights (LOUD / MID tiers)
-    // bin lane + 64 e3 (+ 256) of the magnitude stage in the same order: word e_base + 32 e3 (+ 128)
-#if SR_MEL_CHUNKED
-    const int e_base = mel_chunk_word(lane);  // bins lane + 64 e3 (+ 256): 8 e3 (+ 32) slots further on, bit 2 of the slot untouched
-    constexpr int kEs = 32, kEh = 128;
-    const int c0 = mel_chunk_word(8 * lane), c1 = mel_chunk_word(8 * lane + 4);
-#else
-    const int e_base = lane;
-    constexpr int kEs = 64, kEh = 256;
-    const int c0 = 8 * lane, c1 = 8 * lane + 4;
-#endif
+    // the energies of the filter lane's bins 8 lane .. 8 lane + 7: two 16-byte words of the energies image (sr_fft_layout.h)
+    const int c0 = energy_read_base(lane), c1 = c0 + 4;
 
     // the per-utterance record of the NEXT work item is fetched while the current one is processed
     uint32_t item = blockIdx.x;
@@ -290,16 +280,10 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
         }
         // the in-lane prefixes of the lane's eight bins, both poly-lines (mel_prefix_word; every lane has read its energies: the
         // wave's LDS operations complete in order)
-        auto store_prefixes = [&](const uint32_t (&pe)[8], const uint32_t (&po)[8]) {
-#if SR_MFCC_PREFIX_TID
-            mel_prefix_store(buf_lds, pe, po);
-#else
-            *(uint4 *)(buf + c0) = make_uint4(pe[0], pe[1], pe[2], pe[3]);
-            *(uint4 *)(buf + c1) = make_uint4(pe[4], pe[5], pe[6], pe[7]);
-            *(uint4 *)(buf + kBins + c0) = make_uint4(po[0], po[1], po[2], po[3]);
-            *(uint4 *)(buf + kBins + c1) = make_uint4(po[4], po[5], po[6], po[7]);
-#endif
-        };
+        auto store_prefixes = [&](const uint32_t (&pe)[8], const uint32_t (&po)[8]) { mel_prefix_store(buf_lds, pe, po); };
+        // the squares of the lane's eight magnitudes, en[2 e3 + half] of bin lane + 64 e3 + 256 half, into the energies image
+        auto store_energies = [&](const uint32_t (&en)[8]) { mel_energy_store(buf_lds, en); };
+        auto exchange = [&](const uint32_t (&v)[4][4], uint32_t (&u)[4][4]) { fft_exchange_tid(buf, buf_lds, lane, v, u); };
         if constexpr (!kPipe)  // the forms without the table (and the feature variants of those): one frame at a time
         for (uint32_t fi = 0; fi < nf; fi++) {
             // ---- pre-emphasis + Hamming (MFCC.C:115-124); x[-1] is the sample before the frame
@@ -322,7 +306,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             // ---- FFT passes 1-3 in registers, exchange, passes 4-5 in registers
             uint32_t v[4][4], u[4][4];
             fft_front_real160(xw, lane, tw, s_tw3, v);
-            fft_exchange(buf, lane, v, u);
+            exchange(v, u);
 #pragma unroll
             for (int e4 = 0; e4 < 4; e4++) fft_pass4_dbl(u, e4, tw);
             // pass 5: only x[j] and x[j+q] (bins < 512) are consumed (MFCC.C:49)
@@ -375,8 +359,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                 // never read on this path: "defined" by an empty asm so that the quiet frame does not pay 16 register clears
                 asm volatile("" : "=v"(tw_e[0]), "=v"(tw_e[1]), "=v"(tw_o[0]), "=v"(tw_o[1]));
             }
-            // energies go to the wave's scratch in the chunked order the filterbank reads them in (mel_chunk_word)
-            uint32_t *eb = buf + e_base;
+            // energies go to the wave's scratch in the order the filterbank reads them in (store_energies)
+            uint32_t en[8];
             if (kTabBins > 0 && quiet) {
                 // QUIET-tier magnitudes << 2 from the table: eight gathers on the vector-memory path, which take no VALU issue
                 // slot -- the SIMD's other waves issue under them.  Requested only once the frame is known to be QUIET: gathered
@@ -411,8 +395,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                         fr[0] = q0 >> 2;
                         fr[256] = q1 >> 2;
                     }
-                    eb[kEs * e3] = umul24(q0, q0);
-                    eb[kEs * e3 + kEh] = umul24(q1, q1);
+                    en[2 * e3] = umul24(q0, q0);
+                    en[2 * e3 + 1] = umul24(q1, q1);
                 }
             } else if (cheap) {
 #pragma unroll
@@ -425,8 +409,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                         fr[0] = m0;
                         fr[256] = m1;
                     }
-                    eb[kEs * e3] = umul24(m0, m0);
-                    eb[kEs * e3 + kEh] = umul24(m1, m1);
+                    en[2 * e3] = umul24(m0, m0);
+                    en[2 * e3 + 1] = umul24(m1, m1);
                 }
             } else {
 #pragma unroll
@@ -439,10 +423,11 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                         fr[0] = m0;
                         fr[256] = m1;
                     }
-                    eb[kEs * e3] = umul24(m0, m0);
-                    eb[kEs * e3 + kEh] = umul24(m1, m1);
+                    en[2 * e3] = umul24(m0, m0);
+                    en[2 * e3 + 1] = umul24(m1, m1);
                 }
             }
+            store_energies(en);
             wave_sync();
             // ---- Mel filterbank as prefix sums over bins (each term /100 before summing, u32 wrap)
             uint32_t pe[8], po[8], xe, xo;
@@ -532,7 +517,7 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             // exchange .. tier decision of frame fi (`more`: frame fi+1 exists); comments of the stages: the serial loop below
             auto middle = [&](uint32_t fi, uint32_t (&v)[4][4], bool more) {
                 uint32_t u[4][4];
-                fft_exchange(buf, lane, v, u);
+                exchange(v, u);
 #pragma unroll
                 for (int e4 = 0; e4 < 4; e4++) fft_pass4_dbl(u, e4, tw);
                 wave_sync();
@@ -587,8 +572,8 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
             // behind the gathers on every path that leads here, so the wait may leave them in flight.
             auto back_end = [&](uint32_t r, auto young) {
                 wave_sync();  // (the front's reads of xw are done: buf takes the energies)
-                auto energies = [&]() {  // squares of the carried magnitudes, in the chunked order the filterbank reads them in
-                    uint32_t *eb = buf + e_base;
+                auto energies = [&]() {  // squares of the carried magnitudes, in the order the filterbank reads them in
+                    uint32_t en[8];
 #pragma unroll
                     for (int e3 = 0; e3 < 4; e3++) {
                         const uint32_t q0 = mq[2 * e3], q1 = mq[2 * e3 + 1];
@@ -598,9 +583,10 @@ __global__ void __launch_bounds__(64 * kMfccWaves, 4) k_mfcc(const Args a)
                             fr[0] = q0 >> sh;
                             fr[256] = q1 >> sh;
                         }
-                        eb[kEs * e3] = umul24(q0, q0);
-                        eb[kEs * e3 + kEh] = umul24(q1, q1);
+                        en[2 * e3] = umul24(q0, q0);
+                        en[2 * e3 + 1] = umul24(q1, q1);
                     }
+                    store_energies(en);
                     wave_sync();
                 };
                 // the two tiers' back ends are two whole branches: the literal form's sixteen raw weights are live in its own only

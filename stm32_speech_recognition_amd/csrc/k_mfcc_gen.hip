@@ -25,7 +25,7 @@ struct GenTw {
 };
 __device__ __forceinline__ void load_gen_tw(const DevTables &t, int lane, GenTw &g)
 {
-    load_lane_tw(t, lane, g.tw);
+    load_lane_tw(t, lane, lane & 3, g.tw);
     load_tw3(t, 0, lane & 3, g.k2);
 }
 __device__ __forceinline__ void fft_real_half(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t *buf, int lane,

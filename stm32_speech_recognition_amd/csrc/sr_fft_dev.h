@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "sr_dev.h"
+#include "sr_fft_layout.h"
 
 namespace sr {
 
@@ -214,7 +215,7 @@ __device__ __forceinline__ int rev2(int d) { return ((d & 1) << 1) | (d >> 1); }
 // With lane = d0 + 4*d3 + 16*d4 writing j = d0 + 4*d1 + 16*d2 + 64*d3 + 256*d4 the 32 lanes of a
 // ds_write_b32 group hit 32 distinct banks; reads by lane = j & 63 are consecutive words.
 __device__ __forceinline__ int xaddr(int j) { return j + ((j >> 6) << 2); }
-constexpr int kXchgWords = 1024 + 4 * 16;  // 1088
+// (kXchgWords = 1088, the size of the area: sr_fft_layout.h)
 
 // Coefficients a lane needs, all lane-invariant across frames -> loaded once per wave into VGPRs.
 struct LaneTw {
@@ -250,9 +251,9 @@ __device__ __forceinline__ void load_tw4(const DevTables &t, int base, int b, ui
     k[3][1] = pk_sub(0u, k3[2][1]);
 }
 
-__device__ __forceinline__ void load_lane_tw(const DevTables &t, int lane, LaneTw &tw)
+// d0: the digit of the FRONT lane order (passes 2 and 3); s4 and s5 belong to the reading lane = j & 63 of every order
+__device__ __forceinline__ void load_lane_tw(const DevTables &t, int lane, int d0, LaneTw &tw)
 {
-    const int d0 = lane & 3;
     {
         uint32_t k[3][2];
         load_tw3(t, 0, d0, k);
@@ -289,7 +290,8 @@ __device__ __forceinline__ void load_tw32(const u32x4 *lds, int lane, uint32_t (
         f[4 * c + 3] = q.w;
     }
 }
-// pass-3 coefficients depend on (d0, d1) only: 4 x 32 words, read with lane-broadcast by d0 = lane & 3.  The four rows are
+// pass-3 coefficients depend on (d0, d1) only: 4 x 32 words, read with lane-broadcast by d0 (k_mfcc: lane >> 4, two values per
+// service group of the read; the reasoning below was made for d0 = lane & 3 and holds for fewer rows per group).  The four rows are
 // kTw3Row = 9 chunks apart, not 8: the lanes of a ds_read_b128 service group hold all four d0, and with rows of 32 words
 // d0 = 0 / 2 (and 1 / 3) fall on the same banks with different addresses -- every one of the loads was a 2-way conflict
 // (round 6: 32 of k_mfcc's 53 conflict cycles per frame, profiles/experiments/RESULTS.md)
@@ -310,7 +312,9 @@ __device__ __forceinline__ void load_tw32_d0(const u32x4 *lds, int d0, uint32_t 
 // Passes 1-3 for the zero-padded real frame that get_mfcc feeds (MFCC.C:37-47): only x[0..159] are
 // non-zero and every imaginary part is 0.  Pass 1 (.s:226-232) then degenerates exactly to
 // out[4*idx+k] = x[bitrev8(idx)] >> 2 (k = 0..3), so it is folded into the gather.
-// lane = d0 + 4*d3 + 16*d4 ; v[d1][d2] <-> j = d0 + 4*d1 + 16*d2 + 64*d3 + 256*d4.
+// lane = d3 + 4*d4 + 16*d0 ; v[d1][d2] <-> j = d0 + 4*d1 + 16*d2 + 64*d3 + 256*d4.  (The lane order is the one the exchange image
+// behind it wants, fft_exchange_tid below: the lanes that hold one reading lane's sixteen words are consecutive.  The generic
+// transforms keep d0 + 4*d3 + 16*d4 and fft_exchange.  tw.s2, tw.s3 and the rows of tw3_lds are per d0: load_lane_tw(.., d0 = lane >> 4, ..).)
 // xw: the windowed frame as one 32-bit word per sample, written by window_store below: 4-byte stores of consecutive samples and
 // the reads below at word base + 16 m are both conflict-free; with two samples per word the stores of lanes 2 m / 2 m + 1 went
 // to one word.  Samples 0..63, the A legs of pass 2, are stored >> 2 once more (round 6), as the word (a, 2 a): butterfly
@@ -341,7 +345,7 @@ __device__ __forceinline__ void real_leg_tw(LaneTw &tw)
 __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, const LaneTw &tw, const u32x4 *tw3_lds,
                                                   uint32_t (&v)[4][4])
 {
-    const int d3 = (lane >> 2) & 3, d4 = lane >> 4;
+    const int d0 = lane >> 4, d3 = lane & 3, d4 = (lane >> 2) & 3;
     const int base = rev2(d4) + 4 * rev2(d3);
     // bitrev8(j>>2) = base + 16*rev2(d2) + 64*rev2(d1); >= 160 <=> zero padding
     uint32_t y[10];
@@ -380,7 +384,7 @@ __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, 
     }
     // pass-3 coefficients (24 words per lane) are parked in LDS, shared by the workgroup's waves
     uint32_t k3[4][4][2];
-    load_tw32_d0(tw3_lds, lane & 3, k3);
+    load_tw32_d0(tw3_lds, d0, k3);
     // pass 3: across the exchange an output's leg in pass 4 is d3 of THIS lane -- d3 = 0 writes A legs (m = 1), the others
     // doubled legs (m = 2)
     const uint32_t mul = d3 ? kPkTwo : kPkPlusMinus;
@@ -390,7 +394,7 @@ __device__ __forceinline__ void fft_front_real160(const uint32_t *xw, int lane, 
                                     k3[d1][2][0], k3[d1][2][1], k3[d1][3][0], k3[d1][3][1], mul);
 }
 
-// lane (d0,d3,d4) -> LDS -> lane' = j & 63 holding u[d3][d4]
+// lane (d0,d3,d4) -> LDS -> lane' = j & 63 holding u[d3][d4]: the generic transforms' exchange (lane = d0 + 4*d3 + 16*d4)
 __device__ __forceinline__ void fft_exchange(uint32_t *buf, int lane, const uint32_t (&v)[4][4], uint32_t (&u)[4][4])
 {
     const int d0 = lane & 3, d3 = (lane >> 2) & 3, d4 = lane >> 4;
@@ -405,6 +409,40 @@ __device__ __forceinline__ void fft_exchange(uint32_t *buf, int lane, const uint
 #pragma unroll
         for (int e4 = 0; e4 < 4; e4++) u[e3][e4] = buf[xaddr(lane + 64 * e3 + 256 * e4)];
 }
+
+// The same exchange behind fft_front_real160's lane order d3 + 4 d4 + 16 d0 (sr_fft_layout.h): register v[d1][d2] is plane
+// d1 + 4 d2 of the image, stored lane-contiguously at word 68 p + lane by ds_write_addtid_b32 (address = M0 + offset + 4 lane;
+// `base` = LDS byte address of buf, wave-uniform), and the reading lane's sixteen words u[e3][e4] are consecutive: four
+// ds_read_b128.  M0, the in-order completion of the wave's LDS operations and what the compiler knows of both: see
+// mel_prefix_store in k_mfcc.hip, the statement this one is modelled on.  EXEC is all ones wherever a frame is transformed.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void fft_exchange_tid(const uint32_t *buf, uint32_t base, int lane, const uint32_t (&v)[4][4], uint32_t (&u)[4][4])
+{
+    static_assert(4 * kXchgPlane == 272 && xchg_plane(1, 0) == 1 && xchg_plane(0, 1) == 4, "the offsets below are written out for planes d1 + 4 d2 of 68 words");
+    asm volatile("s_mov_b32 m0, %16\n\ts_nop 0\n\t"
+                 "ds_write_addtid_b32 %0\n\tds_write_addtid_b32 %1 offset:272\n\tds_write_addtid_b32 %2 offset:544\n\t"
+                 "ds_write_addtid_b32 %3 offset:816\n\tds_write_addtid_b32 %4 offset:1088\n\tds_write_addtid_b32 %5 offset:1360\n\t"
+                 "ds_write_addtid_b32 %6 offset:1632\n\tds_write_addtid_b32 %7 offset:1904\n\t"
+                 "ds_write_addtid_b32 %8 offset:2176\n\tds_write_addtid_b32 %9 offset:2448\n\tds_write_addtid_b32 %10 offset:2720\n\t"
+                 "ds_write_addtid_b32 %11 offset:2992\n\tds_write_addtid_b32 %12 offset:3264\n\tds_write_addtid_b32 %13 offset:3536\n\t"
+                 "ds_write_addtid_b32 %14 offset:3808\n\tds_write_addtid_b32 %15 offset:4080"
+                 :
+                 : "v"(v[0][0]), "v"(v[1][0]), "v"(v[2][0]), "v"(v[3][0]), "v"(v[0][1]), "v"(v[1][1]), "v"(v[2][1]), "v"(v[3][1]),
+                   "v"(v[0][2]), "v"(v[1][2]), "v"(v[2][2]), "v"(v[3][2]), "v"(v[0][3]), "v"(v[1][3]), "v"(v[2][3]), "v"(v[3][3]), "s"(base)
+                 : "m0", "memory");
+    wave_sync();
+    const u32x4 *rd = (const u32x4 *)(buf + xchg_read_base(lane));
+#pragma unroll
+    for (int e4 = 0; e4 < 4; e4++) {
+        const u32x4 q = rd[e4];
+        u[0][e4] = q.x;
+        u[1][e4] = q.y;
+        u[2][e4] = q.z;
+        u[3][e4] = q.w;
+    }
+}
+#pragma clang diagnostic pop
 
 // Pass-4 butterfly e4 behind fft_front_real160 + fft_exchange: its B, C and D legs u[1..3][e4] arrive doubled (written by the lanes
 // with d3 > 0).  Its outputs u[.][e4] are all leg e4 of pass 5, which takes only its B leg doubled (its HALF form needs p() of B
@@ -441,7 +479,7 @@ __device__ inline void fft_full_wave(const uint32_t *__restrict__ in, uint32_t *
     }
     wave_sync();
     LaneTw tw;
-    load_lane_tw(t, lane, tw);
+    load_lane_tw(t, lane, lane & 3, tw);
     uint32_t k2[3][2];
     load_tw3(t, 0, lane & 3, k2);
     const int d0 = lane & 3, d3 = (lane >> 2) & 3, d4 = lane >> 4;
