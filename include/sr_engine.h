@@ -1320,8 +1320,8 @@ int sr_decode_onepass_geometry(uint32_t tpl_rows, uint32_t K, uint32_t max_frame
  * depend on the chunking.  The rule is conservative by up to W frames: while N <= W nothing is committed.
  * Out of scope: recordings past 16 383 frames (forgetting a committed prefix), n_words_exact, N-best sequences; a tighter,
  * frontier-based marker (it needs the exact column at N - 1, which the device never has -- blocks charge nothing behind their
- * first frame -- and would depend on the chunking); commits in grammar sessions (the node is then (position, state) and
- * nothing else changes). */
+ * first frame -- and would depend on the chunking).  Grammar sessions commit by the same rule over (position, state) nodes:
+ * sr_onepass_gram_live_commit[_dev], the live one-pass grammar decoding section. */
 #define SR_OP_LIVE_TAIL 1u
 typedef struct sr_onepass_live sr_onepass_live;
 /* host-only, no device: a store of K slots whose longest template has tpl_rows rows and whose shortest valid one has
@@ -1505,12 +1505,53 @@ int sr_onepass_grammar_plan(const sr_grammar *g, uint32_t frames_cap, uint32_t o
  * sr_decode_onepass_grammar_batch(X_c, 1, R, mid[c]).
  * Refusals come in the order stale grammar, counts, inputs, outputs, device; a refused call writes nothing and changes no
  * state.  Stream ordering is the live connected-word decoding section's.
+ * COMMITTED WORDS (sr_onepass_gram_live_commit[_dev], below): under a sequence or a looping grammar the row of a push is
+ * SR_CH_NONE for most of an utterance -- no final state is reachable yet -- so a session tells its caller nothing until the
+ * utterance completes.  A commit call says which words every parse this recording can still get begins with, from the state
+ * the session keeps and without a sweep.  With A(p, t), E(p, t), the charge C(x; t, w) and the source state of a word as the
+ * one-pass grammar section defines them:
+ *   kept     the kept states and kept items are the grammar's static pruning lists, as sr_onepass_grammar_plan counts them.
+ *            They do not depend on the testing hook "onepass_gram_prune_off": the hook changes what is swept, never what the
+ *            rule ranges over.
+ *   node     a pair (q, t), t a kept state, q >= 1, A(q, t) reachable and A(q, t).cost == E(q, t); or the root (0, 0).
+ *            end(p, t) = the node (q, t) with the largest q <= p, the root if state t has none.  The parent of (q, t), whose
+ *            word starts at x with source state s, is end(x, s); parents lie strictly below their children.  The walk from
+ *            (p, t) is end(p, t), its parent, and so on down to the root; its words are what the trace writes from (p, t).
+ *            A and E at p depend on frames < p only: a walk never changes.
+ *   window   W = 2 * max M_k - 1 over the slots of the kept items (0 if none are kept): a word over M template frames covers at
+ *            most 2M - 1 input frames.  The grammar changes only while every channel is empty, so W is constant over a
+ *            recording.
+ *   entries  the pairs (x, s), s a kept state, x in [max(0, N - W), N], with E(x, s) reachable; if there are none, every
+ *            reachable (x, s) at the largest x <= N that has one ((0, 0) always qualifies where state 0 is kept; such a
+ *            recording can no longer parse).
+ *   c(N)     the deepest node shared by the walks from all entries.  Shared nodes lie on one chain and a walk holds one node
+ *            per position, so it is the shared node at the largest position.  The committed words are the words on the walk
+ *            from c(N), and frames = the position of c(N).
+ * Why they are final: a later trace starts in a reachable final state and goes down through pairs whose E is reachable.  Take
+ * its first pair (x, s) with x <= N.  If it was reached by a skipped frame, x = N.  Otherwise it is the start of a word that
+ * ends at or after frame N: that word is alive in column N - 1, so x >= N - W.  Every state on a trace is kept: it is reachable
+ * from state 0, and it is final or named by the charge list of an item whose target reaches a final state.  So (x, s) is an
+ * entry, and from there the trace is the walk from (x, s), which passes through c(N).  Hence every later row of the recording
+ * whose status is not SR_CH_NONE, the end call's included, BEGINS with exactly the committed word rows, byte for byte, acc,
+ * score, cum and reserved included; c(N) never moves back; c(N) depends on the recording, the grammar and N only, not on the
+ * chunking; and the rule is conservative by up to W frames.
+ * How much it commits is the grammar's: a node is shared only where every hypothesis still alive runs through it.  With
+ * skipping on, a start state that no word leads back into stays reachable at every frame -- everything so far skipped --
+ * and the walk from there is the root alone: a later parse may still begin that way, and such a grammar commits nothing
+ * while it skips.  States that count words (a sequence grammar's) keep the hypotheses of different word counts apart: they
+ * share nothing before no state is reachable in the window any more, and then the fallback commits the whole sequence at
+ * once.  States that words lead back into (loops, the anchor grammar's one state) are where walks merge and words commit
+ * about W frames behind the speaker.
+ * Words are committed WHILE THE ROW ITSELF IS STILL SR_CH_NONE.  They mean "if this recording ever parses, it begins thus"; if
+ * the grammar's end is never reached, the caller has still been told the truth.  Under the anchor grammar every byte of the
+ * commit outputs is sr_onepass_live_commit_dev's on the same pushes.
  * Out of scope: a grammar per channel; a history compacted to the kept states; a row for the best non-final state while an
- * utterance is incomplete; n_words_exact; N-best sequences; recordings past 16 383 frames; committed words
- * (sr_onepass_live_commit's rule with (position, state) for a node: a follow-up). */
+ * utterance is incomplete; n_words_exact; N-best sequences; recordings past 16 383 frames (forgetting a committed prefix); a
+ * frontier-based marker; commits in the level-building sessions (sr_gram_live, sr_decode_live). */
 typedef struct sr_onepass_gram_live sr_onepass_gram_live;
 /* host-only, no device.  out[0] = device state bytes per channel, S x (utt_frames + 1) x 12 + kept items x tpl_len x 16 +
- * utt_frames x 24, saturating; out[1] = the longest template that fits (sr_spot_geometry's out[2]); out[2] = L; out[3] = the
+ * utt_frames x 24, saturating (the commit cursor, 8 bytes per channel, lies outside these state bytes);
+ * out[1] = the longest template that fits (sr_spot_geometry's out[2]); out[2] = L; out[3] = the
  * kernel launches a feature push of chunk_max frames enqueues, per_block x ceil(chunk_max / L) + 1 with per_block = (kept items ?
  * 1 : 0) + (kept states ? 1 : 0); out[4] = kept items; out[5] = kept states.  utt_frames 1..16 383, chunk_max 1..utt_frames. */
 int sr_onepass_gram_live_geometry(const sr_grammar *g, uint32_t utt_frames, uint32_t chunk_max, uint32_t out[6]);
@@ -1541,6 +1582,26 @@ int sr_onepass_gram_live_push_pcm(sr_onepass_gram_live *l, const uint16_t *pcm, 
  * are then empty, and their keys are wiped all the same. */
 int sr_onepass_gram_live_end(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_chain_rec *rec, sr_chain_word *words,
                              sr_chain_live_row *rows, uint32_t *n_rows);
+/* The committed words of the listed channels (COMMITTED WORDS above): sr_onepass_live_commit[_dev]'s arguments, outputs and
+ * delivery on a grammar session.  One row per DISTINCT listed channel at its first mention; rows and *n_rows are HOST outputs
+ * filled from the host mirror before the call returns; the sr_commit_rec says n_committed, first, n_new = min(n_committed -
+ * first, words_cap) and frames = the position of c(N); d_cwords[r*words_cap + i], i < n_new, are the words first .. first +
+ * n_new - 1 as the trace writes them, `reserved` = the state after the word, the entries from n_new on the all-ones row.  Per
+ * channel the session keeps a cursor on the device -- the words delivered and the last delivered word's node WITH its state, 8
+ * bytes, outside sr_onepass_gram_live_geometry's state bytes -- so every committed word is delivered exactly once and in order,
+ * and a backlog drains over later calls.  An empty channel gives {0, 0, 0, 0}; a grammar that keeps no state gives {0, 0, 0, 0}
+ * for every channel.  sr_onepass_gram_live_end (dropped recordings of a stale grammar included) and
+ * sr_onepass_gram_live_set_grammar put the cursors back to zero.
+ * DEVICE form: ONE asynchronous operation on `stream`, no host synchronisation, nothing read back; it runs behind the
+ * session's last push by the event rule of the pushes, and later pushes run behind it.  The HOST form writes host buffers and
+ * waits.  A weighted grammar takes the kernel that judges charges with the arc costs; any other grammar the plain one.
+ * Refused (SR_ERR_BAD_ARG) before anything is enqueued, nothing written, no state changed: a stale grammar (first, as in the
+ * pushes), a null required pointer, a channel past the session's last, a word map that does not fit, outputs that overlap
+ * (the host form: rows inside crec or cwords too). */
+int sr_onepass_gram_live_commit_dev(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *d_crec,
+                                    sr_chain_word *d_cwords, sr_chain_live_row *rows, uint32_t *n_rows, void *stream);
+int sr_onepass_gram_live_commit(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *crec, sr_chain_word *cwords,
+                                sr_chain_live_row *rows, uint32_t *n_rows);
 
 /* EXTENSION, NO REFERENCE COUNTERPART (the thesis that accompanies the reference, p.32, lists difference cepstra as
  * future work; the firmware computes none): delta MFCC by the standard two-frame regression over the s16 rows,

@@ -16,9 +16,11 @@
 //                               the block's frames to the kept feature row, which no sweep of this push reads at those columns;
 //   k_onepass_gram_live_trace   opg_trace_row's walk with N = x0 + n into the compact row the host assigned, the first words_cap
 //                               words or (tail) the last.
-// A WEIGHTED grammar takes k_onepass_gram_live_words_w and k_onepass_gram_live_trace_w; a grammar without a nonzero cost launches
-// the unweighted kernels only.  No init launch: a position of A that no push has reached holds all ones, E(0, 0) = 0 and E(0, s)
-// is unreachable for s != 0 from the open call (or the adoption of a grammar) on, and the end call puts that back
+//   k_onepass_gram_live_commit  (sr_onepass_gram_live_commit, a call of its own behind a push) the words of the listed channels
+//                               that no later frame can change, from A, E, N and the grammar's static lists: see the kernel.
+// A WEIGHTED grammar takes k_onepass_gram_live_words_w, k_onepass_gram_live_trace_w and k_onepass_gram_live_commit_w; a grammar
+// without a nonzero cost launches the unweighted kernels only.  No init launch: a position of A that no push has reached holds
+// all ones, E(0, 0) = 0 and E(0, s) is unreachable for s != 0 from the open call (or the adoption of a grammar) on, and the end call puts that back
 // (k_onepass_gram_live_wipe).  Where no state is kept no item is kept either (a kept item's charge list is kept): nothing sweeps,
 // nothing closes, nothing parses, and the feature row is neither written nor read.  No workgroup waits on another: the blocks are
 // ordered by the stream alone.  Plain vector stores; the atomic minimum on A is the only atomic, and it does not depend on the
@@ -430,6 +432,238 @@ __global__ void __launch_bounds__(256) k_onepass_gram_live_wipe(const OnePassGra
     if (threadIdx.x == 0) opgl_E(a, c, state)[0] = state ? kChainNone : 0u;
 }
 
+// sr_onepass_gram_live_end, behind the wipe: the commit cursors of the listed channels say "nothing delivered" again
+__global__ void __launch_bounds__(256) k_onepass_gram_live_uncommit(const OnePassGramLiveArgs a, uint2 *cursor)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c < a.o.C && a.o.chan[c].first_win) cursor[c] = uint2{0u, 0u};
+}
+
+// ---- sr_onepass_gram_live_commit: the words that can no longer change -------------------------------------------------------
+// k_onepass_live_commit's rule (include/sr_engine.h, COMMITTED WORDS of the live one-pass grammar section) with a NODE a pair
+// (q, t): t a kept state, q >= 1 and the word A(q, t) closes E(q, t); or the root (0, 0).  end(p, t) = the first node of state t
+// at or below p, the root if there is none; the parent of a node whose word starts at x with source state s is end(x, s).
+// Parents lie strictly below their children, and A(p, .), E(p, .) depend on frames < p only: the tree never changes where it
+// stands.  The entries are the (x, s), s kept, x in the window [lo, N], lo = max(0, N - W), with E(x, s) reachable (none: every
+// reachable (x, s) at the last position that has one); the commit node c is the deepest node shared by the walks from end(x, s)
+// of all entries.
+//
+// What the kernel makes of it, one wave per listed channel, every loop with a wave operation in it wave-uniform.  A walk is a
+// chain of PAIRS (x, s) with E(x, s) reachable at falling positions: from a pair that is no node to (x - 1, s) -- E came from
+// the frame skipped -- and from a node to (the start of its word, its source state).  A grammar has at most 64 states, so the
+// pairs of one position that some walk passes are ONE 64-bit mask, and the masks of the positions not yet swept live in an LDS
+// ring (a pair's successor lies at most W below it).  The entries are marked, then the positions are swept from the top down
+// in blocks of at most min(64, L) positions, lane = position:
+//   * a word covers at least L frames, so the successor of a node lies below its block: inside a block only the skipped
+//     frames chain, p(x) = marks(x) | (p(x + 1) & ~hits(x + 1)), a prefix scan over the lanes;
+//   * the nodes of the block, p & hits, are expanded lane by lane -- the item, its charge list, the source state, as opgl_step
+//     finds them -- and mark their successors; what is pending at the block's last position and is no node goes one down;
+//   * T counts the marked pairs.  Walks that meet share a mark, so T falls; with one pair left that is a node, that node is c:
+//     every walk runs through it, and none did through any node above (T was larger there).  Position 0 is the root.
+// The work is the number of distinct pairs above c, not the sum of the walks' lengths.  Before the sweep one case is settled
+// at once: a state that is reachable in the window below its first hit there and has no node below the window either -- with
+// skipping on, a start state no word leads back into -- contributes the root, and the root is shared with everything.
+// Then two walks from c down to the cursor's node, as the trace walks: the count, then the earliest words_cap pending words.
+// The cursor's node is c of an earlier call, and c never leaves the chain it once stood on: the walk from c meets it at its
+// position.
+struct OpglNode {
+    uint32_t q, t;       // (0, 0): the root
+    uint32_t charge, src;  // of the node's word: what it started from, and in which state
+    uint64_t key;
+};
+
+// end(p, t)
+__device__ __forceinline__ OpglNode opgl_end(const OnePassGramLiveArgs &a, const GramCosts *wt, uint32_t c, uint32_t p, uint32_t t, uint32_t lane)
+{
+    OpglNode n{0u, 0u, 0u, 0u, kSpotInf};
+    bool bad = false;  // (set where A, E and the items disagree, which cannot happen: the walk ends in the root then)
+    n.q = opgl_step(a, wt, c, p, t, lane, &n.key, &n.charge, &n.src, &bad);
+    n.t = n.q ? t : 0u;
+    return n;
+}
+__device__ __forceinline__ OpglNode opgl_parent(const OnePassGramLiveArgs &a, const GramCosts *wt, uint32_t c, const OpglNode &n, uint32_t lane)
+{
+    return opgl_end(a, wt, c, (uint32_t)(n.key >> 16) & 0xFFFFu, n.src, lane);  // the start lies below n.q: the walk ends
+}
+
+// the source state of the word `key` into state t, as opgl_step finds it, for ONE lane (no wave operation: the lanes of a
+// block expand different nodes); 64: A, E and the items disagree, which cannot happen
+__device__ __forceinline__ uint32_t opgl_source(const OnePassGramLiveArgs &a, const GramCosts *wt, uint32_t c, uint32_t t, uint64_t key)
+{
+    const uint32_t slot = (uint32_t)key & 0xFFFFu, start = (uint32_t)(key >> 16) & 0xFFFFu;
+    const uint32_t at = opgl_item_of(a, slot, t);
+    if (at == a.n_items) return 64u;
+    const uint32_t set = a.items[at].set;
+    const uint32_t *ac = wt ? wt->cost + wt->cost_off[set] : nullptr;
+    uint32_t cst = kChainNone, s0 = 64u;
+    for (unsigned long long m = a.masks[set]; m; m &= m - 1) {  // (ascending states)
+        const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
+        const uint32_t e = opgl_E(a, c, s)[start], v = ac ? e + *ac++ : e;
+        if (e != kChainNone && v < cst) cst = v, s0 = s;
+    }
+    return s0;
+}
+
+__device__ __forceinline__ uint64_t opgl_wave_or(uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= ((uint64_t)__shfl_xor((uint32_t)(v >> 32), d, 64) << 32) | __shfl_xor((uint32_t)v, d, 64);
+    return v;
+}
+
+__device__ __forceinline__ void opgl_commit_chan(const OnePassGramCommitArgs &a, const GramCosts *wt, uint32_t r, uint32_t lane)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long opgl_ring[];  // [a.ring] the marks of the positions not yet swept
+    const OnePassGramLiveArgs &g = a.g;
+    const uint32_t cap = g.o.words_cap, rmask = a.ring - 1u;  // (a power of two, at least W + 64)
+    const sr_chain_live_row row = a.rows[r];
+    const uint32_t c = row.channel, N = row.frames;  // N <= utt_frames = P - 1: no position past the history is read
+    sr_chain_word *words = a.cwords + (size_t)r * cap;
+    const sr_chain_word none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    const uint32_t lo = N > a.W ? N - a.W : 0u;
+    for (uint32_t i = lane; i < a.ring; i += 64) opgl_ring[i] = 0ull;
+    wave_sync();
+
+    // the entries: per kept state the reachable positions of the window, marked (a lane owns its positions: no conflict)
+    uint32_t T = 0, top = N;
+    bool at_root = false;
+    for (uint32_t i = 0; i < a.n_kept && !at_root; i++) {  // (uniform)
+        const uint32_t s = a.states[i];
+        const unsigned long long *A = opgl_A(g, c, s);
+        const uint32_t *E = opgl_E(g, c, s);
+        uint32_t first_hit = kChainNone, low_reach = kChainNone;  // of state s in the window
+        for (uint32_t x0 = lo; x0 <= N; x0 += 64) {  // (uniform) 64 positions per round, coalesced
+            const uint32_t x = x0 + lane;
+            const bool in = x <= N;
+            const uint32_t e = in ? E[x] : kChainNone;
+            const uint64_t ky = in && x ? A[x] : kSpotInf;  // position 0 ends no word
+            const bool hit = ky != kSpotInf && (uint32_t)(ky >> 32) == e;
+            const unsigned long long hits = __ballot(hit), reach = __ballot(e != kChainNone);
+            if (low_reach == kChainNone && reach) low_reach = x0 + (uint32_t)__ffsll((long long)reach) - 1u;
+            if (first_hit == kChainNone && hits) first_hit = x0 + (uint32_t)__ffsll((long long)hits) - 1u;
+            if (e != kChainNone) opgl_ring[x & rmask] |= 1ull << s;
+            T += (uint32_t)__popcll(reach);
+        }
+        // reachable below its first hit of the window: such a walk ends in end(lo - 1, s).  No node there: the root
+        if (low_reach != kChainNone && low_reach != first_hit) {
+            uint64_t key = kSpotInf;
+            at_root = !lo || !onepass_word_at(A, E, lo - 1u, lane, &key);
+        }
+    }
+    if (!T && !at_root) {  // (uniform) an empty window: the last position below it where a kept state is reachable, and its states
+        uint32_t xs = kChainNone;
+        for (uint32_t hi = lo; hi && xs == kChainNone; hi = hi > 64u ? hi - 64u : 0u) {  // (uniform) positions hi - 1 - lane
+            for (uint32_t i = 0; i < a.n_kept; i++) {
+                const uint32_t e = lane < hi ? opgl_E(g, c, a.states[i])[hi - 1u - lane] : kChainNone;
+                const unsigned long long reach = __ballot(e != kChainNone);
+                if (!reach) continue;
+                const uint32_t x = hi - (uint32_t)__ffsll((long long)reach);
+                xs = xs == kChainNone || x > xs ? x : xs;
+            }
+        }
+        unsigned long long at = 0ull;
+        for (uint32_t i = 0; xs != kChainNone && i < a.n_kept; i++)  // (uniform)
+            if (opgl_E(g, c, a.states[i])[xs] != kChainNone) at |= 1ull << a.states[i];
+        if (at) {
+            if (lane == 0) opgl_ring[xs & rmask] = at;
+            T = (uint32_t)__popcll(at);
+            top = xs;
+        }
+    }
+    wave_sync();
+
+    // the sweep.  cq, ct: the commit node; the root where the sweep reaches position 0 or nothing is marked
+    uint32_t cq = 0, ct = 0;
+    for (uint32_t y = at_root || !T ? 0u : top; y;) {  // (uniform) the block y - B + 1 .. y, lane i at x = y - i
+        const uint32_t B = y < a.block ? y : a.block, x = y - lane;
+        const bool in = lane < B;
+        unsigned long long m = 0ull;
+        if (in) {
+            m = opgl_ring[x & rmask];
+            opgl_ring[x & rmask] = 0ull;
+        }
+        const unsigned long long live = opgl_wave_or(m);  // only these states can be pending in the block
+        unsigned long long h = 0ull;
+        for (unsigned long long sb = live; sb; sb &= sb - 1) {  // (uniform)
+            const uint32_t s = (uint32_t)__ffsll((long long)sb) - 1u;
+            const uint64_t ky = in ? opgl_A(g, c, s)[x] : kSpotInf;
+            const uint32_t e = in ? opgl_E(g, c, s)[x] : kChainNone;
+            if (ky != kSpotInf && (uint32_t)(ky >> 32) == e) h |= 1ull << s;
+        }
+        // p(lane) = m | (p(lane - 1) & ~h(lane - 1)): what is pending above and is no node there comes one position down
+        const unsigned long long h_above = spot_shfl_up(h, 1);  // (by every lane: lane 1 reads lane 0)
+        unsigned long long G = m, K = lane ? ~h_above : 0ull;
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const unsigned long long Gd = spot_shfl_up(G, d), Kd = spot_shfl_up(K, d);
+            if (lane >= d) {
+                G |= K & Gd;
+                K &= Kd;
+            }
+        }
+        const unsigned long long nodes = in ? G & h : 0ull;
+        const unsigned long long down = spot_shfl(G & ~h, B - 1u);  // pending at the block's last position and no node
+        const uint32_t n_nodes = wave_sum((uint32_t)__popcll(nodes)), x_below = y - B;
+        // (position 0 holds the root alone: whatever comes down to it is the pair (0, 0))
+        const unsigned long long down_bits = x_below ? down : (down ? 1ull : 0ull), below = opgl_ring[x_below & rmask];
+        T = T - wave_sum((uint32_t)__popcll(m)) + n_nodes + (uint32_t)__popcll(down_bits & ~below);
+        if (T == 1u && n_nodes == 1u) {  // (uniform) every walk runs through this node
+            const unsigned long long has = __ballot(nodes != 0ull);
+            const uint32_t l = (uint32_t)__ffsll((long long)has) - 1u;
+            cq = y - l;
+            ct = (uint32_t)__ffsll((long long)spot_shfl(nodes, l)) - 1u;
+            break;
+        }
+        wave_sync();
+        if (lane == 0 && down_bits) opgl_ring[x_below & rmask] = below | down_bits;
+        wave_sync();
+        uint32_t added = 0;
+        for (unsigned long long nb = nodes; nb; nb &= nb - 1) {  // (per lane) the successors of the block's nodes
+            const uint32_t t = (uint32_t)__ffsll((long long)nb) - 1u;
+            const uint64_t key = opgl_A(g, c, t)[x];
+            const uint32_t start = (uint32_t)(key >> 16) & 0xFFFFu, s0 = opgl_source(g, wt, c, t, key);
+            if (s0 == 64u) continue;
+            const unsigned long long bit = start ? 1ull << s0 : 1ull;
+            added += !(atomicOr(&opgl_ring[start & rmask], bit) & bit);
+        }
+        T = T - n_nodes + wave_sum(added);
+        wave_sync();
+        if (!T) break;  // (uniform; cannot happen)
+        y = x_below;
+    }
+    const OpglNode cur = cq ? opgl_end(g, wt, c, cq, ct, lane) : OpglNode{0u, 0u, 0u, 0u, kSpotInf};
+
+    const uint2 cu = a.cursor[c];  // {delivered, the last delivered word's node}: an ancestor of c, or c
+    const uint32_t cu_q = cu.y & ((1u << kOpgCommitStateShift) - 1u);
+    uint32_t pending = 0;
+    for (OpglNode n = cur; n.q > cu_q; n = opgl_parent(g, wt, c, n, lane)) pending++;  // (uniform)
+    const uint32_t n_new = pending < cap ? pending : cap;
+    for (uint32_t i = n_new + lane; i < cap; i += 64) words[i] = none;
+    uint32_t last_node = cu.y, j = pending;  // the words on the walk are pending words j - 1 .. 0, the earliest n_new are written
+    for (OpglNode n = cur; n.q > cu_q; n = opgl_parent(g, wt, c, n, lane)) {  // (uniform)
+        j--;
+        if (j >= n_new) continue;
+        if (j == n_new - 1u) last_node = n.q | n.t << kOpgCommitStateShift;
+        if (lane == 0) {
+            const uint32_t slot = (uint32_t)n.key & 0xFFFFu, start = (uint32_t)(n.key >> 16) & 0xFFFFu, end = n.q - 1;
+            const uint32_t cum = (uint32_t)(n.key >> 32), acc = cum - g.o.word_cost - n.charge;
+            words[j] =
+                sr_chain_word{g.o.word_id[g.o.group_of_slot[slot]], slot, start, end, acc, acc / (end - start + 1 + g.o.tpl_frames[slot]), cum, n.t};
+        }
+    }
+    if (lane == 0) {
+        a.crec[r] = sr_commit_rec{cu.x + pending, cu.x, n_new, cur.q};
+        a.cursor[c] = uint2{cu.x + n_new, last_node};
+    }
+}
+
+__global__ void __launch_bounds__(64) k_onepass_gram_live_commit(const OnePassGramCommitArgs a) { opgl_commit_chan(a, nullptr, blockIdx.x, threadIdx.x); }
+// under costs: the charge and the source state of a word judged on E + the arc cost
+__global__ void __launch_bounds__(64) k_onepass_gram_live_commit_w(const OnePassGramCommitArgs a, const GramCosts wt)
+{
+    opgl_commit_chan(a, &wt, blockIdx.x, threadIdx.x);
+}
+
 static void opgl_launch_trace(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s)
 {
     if (w) {
@@ -469,16 +703,33 @@ void launch_onepass_gram_live_wipe(const OnePassGramLiveArgs &a, hipStream_t s)
     SR_LAUNCH_POINT(s, "k_onepass_gram_live_wipe");
     hipLaunchKernelGGL(k_onepass_gram_live_wipe, dim3(a.o.C, a.n_states), dim3(256), 0, s, a);
 }
-void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s)
+void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, uint2 *cursor, hipStream_t s)
 {
     if (!a.o.C) return;
     opgl_launch_trace(a, w, s);
     launch_onepass_gram_live_wipe(a, s);
+    SR_LAUNCH_POINT(s, "k_onepass_gram_live_uncommit");
+    hipLaunchKernelGGL(k_onepass_gram_live_uncommit, dim3((a.o.C + 255u) / 256u), dim3(256), 0, s, a, cursor);
+}
+void launch_onepass_gram_live_commit(const OnePassGramCommitArgs &a, const GramCosts *w, hipStream_t s)
+{
+    if (!a.n_rows) return;
+    const size_t lds = (size_t)a.ring * 8;  // the ring of marks: 32 KiB under the longest template that fits the sweep's LDS image
+    if (w) {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_live_commit_w");
+        hipLaunchKernelGGL(k_onepass_gram_live_commit_w, dim3(a.n_rows), dim3(64), lds, s, a, *w);
+    } else {
+        SR_LAUNCH_POINT(s, "k_onepass_gram_live_commit");
+        hipLaunchKernelGGL(k_onepass_gram_live_commit, dim3(a.n_rows), dim3(64), lds, s, a);
+    }
 }
 const char *onepass_gram_live_allow_lds(uint32_t bytes)
 {
     return allow_dynamic_lds({{(const void *)k_onepass_gram_live_words, "k_onepass_gram_live_words"},
-                              {(const void *)k_onepass_gram_live_words_w, "k_onepass_gram_live_words_w"}},
+                              {(const void *)k_onepass_gram_live_words_w, "k_onepass_gram_live_words_w"},
+                              // (the commit's ring stays below 64 KiB under any store the sweeps accept)
+                              {(const void *)k_onepass_gram_live_commit, "k_onepass_gram_live_commit"},
+                              {(const void *)k_onepass_gram_live_commit_w, "k_onepass_gram_live_commit_w"}},
                              bytes);
 }
 

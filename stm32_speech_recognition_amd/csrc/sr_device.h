@@ -672,11 +672,34 @@ struct OnePassGramLiveArgs {
 };
 // n_blocks x (sweep where an item is kept, close where a state is kept), trace; w null: the unweighted kernels
 void launch_onepass_gram_live(const OnePassGramLiveArgs &a, const GramCosts *w, uint32_t n_blocks, hipStream_t s);
-// sr_onepass_gram_live_end: the trace of the listed channels (n = 0, x0 = the frames to parse), then the wipe
-void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, hipStream_t s);
+// sr_onepass_gram_live_end: the trace of the listed channels (n = 0, x0 = the frames to parse), then the wipe, then the commit
+// cursors (below) of the listed channels back to "nothing delivered"
+void launch_onepass_gram_live_end(const OnePassGramLiveArgs &a, const GramCosts *w, uint2 *cursor, hipStream_t s);
 // the wipe alone, over every state of the dense layout: the keys of every listed channel (first_win != 0) all ones over the
 // positions 0..aux, E(0, 0) = 0 and E(0, s) unreachable (the end call; open and a grammar switch list every channel)
 void launch_onepass_gram_live_wipe(const OnePassGramLiveArgs &a, hipStream_t s);
+
+// sr_onepass_gram_live_commit[_dev] (k_onepass_gram_live_commit[_w]): the words of the listed channels that can no longer
+// change.  g is the session's argument block as a push fills it (the history, the items and the charge lists; mfcc, chan, rec
+// and words are not read); states is the grammar's STATIC kept list whatever g.keep_states is -- the testing hook changes what
+// is swept, never what the rule ranges over.  Per channel the cursor is {words delivered so far, the last delivered word's
+// node as position | state << kOpgCommitStateShift}, all zero for a channel without a recording.
+constexpr uint32_t kOpgCommitStateShift = 16;  // positions take 14 bits, states 6
+struct OnePassGramCommitArgs {
+    OnePassGramLiveArgs g;
+    const sr_chain_live_row *rows;  // [n_rows] on the device: the distinct listed channels and their N
+    uint32_t n_rows;
+    uint32_t W;                     // the window: 2 * (the longest kept item's template frames) - 1, 0 where nothing is kept
+    uint32_t ring;                  // entries of the kernel's LDS ring of marks: a power of two, at least W + 64
+    uint32_t block;                 // positions swept at once: 1..64 and at most L, the frames the shortest word covers
+    const uint32_t *states;         // [n_kept] the kept states, ascending
+    uint32_t n_kept;
+    uint2 *cursor;                  // [C]
+    sr_commit_rec *crec;            // [n_rows]
+    sr_chain_word *cwords;          // [n_rows][words_cap]
+};
+// w null: the unweighted kernel
+void launch_onepass_gram_live_commit(const OnePassGramCommitArgs &a, const GramCosts *w, hipStream_t s);
 
 // full-DP alignment (k_align.hip): one wave per (feature row, reference) pair.  The launch covers rows [row0, row0 + n_pairs)
 // of the call; the record and the span of row r go to index r - out0 (0: the caller's buffers; row0: per-launch scratch), the

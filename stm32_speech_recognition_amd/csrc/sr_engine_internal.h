@@ -333,6 +333,7 @@ struct sr_grammar {
     // kept items u32 [op_n_items] (indices into items) | kept states u32 [op_n_states], both ascending
     size_t op_items_at = 0, op_states_at = 0;  // offsets in u64 units
     uint32_t op_n_items = 0, op_n_states = 0;
+    std::vector<uint32_t> op_item_slots;  // host: the slot of each kept item (the commit window of a live session)
     uint32_t max_arc_cost = 0, max_final_cost = 0;  // the largest of each: the decoder's cost bound
     GramCosts costs() const  // the weighted kernels' second argument
     {

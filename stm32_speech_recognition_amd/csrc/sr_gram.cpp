@@ -107,6 +107,7 @@ int sr_grammar_create_weighted(sr_engine *h, uint32_t n_states, const sr_gram_ar
     const OnePassGramKeep keep = onepass_gram_keep(S, arcs, n_arcs, net.finals, c.items.data(), g->n_items, c.masks.data(), true);
     g->op_n_items = (uint32_t)keep.items.size();
     g->op_n_states = (uint32_t)keep.states.size();
+    for (uint32_t i : keep.items) g->op_item_slots.push_back(c.items[i].slot);
     g->op_items_at = end;
     g->op_states_at = g->op_items_at + (keep.items.size() + 1) / 2;
     end = g->op_states_at + (keep.states.size() + 1) / 2;

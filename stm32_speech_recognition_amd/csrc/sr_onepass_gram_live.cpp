@@ -10,6 +10,7 @@
 // are every live session's (sr_live_host.h).  A push never synchronises; open, sr_onepass_gram_live_set_grammar and the end
 // call may: they establish and restore what lets a push run without an init launch (k_onepass_gram_live_wipe).
 #include "sr_live_host.h"
+#include "sr_onepass_gram_commit_plan.h"
 #include "sr_onepass_gram_live_plan.h"
 
 using namespace sr;
@@ -27,6 +28,11 @@ struct sr_onepass_gram_live : LiveCore {
     DevBuf<unsigned long long> A;         // [C][S][utt_frames + 1]
     DevBuf<uint32_t> E;                   // [C][S][utt_frames + 1]
     DevBuf<int16_t> hist;                 // [C][utt_frames][12]: the channels' feature rows
+    // sr_onepass_gram_live_commit: per channel {words delivered, the last delivered word's node}, the rows of the call in
+    // flight, and the window of the rule under g (from its kept items, whatever the pruning hook says)
+    DevBuf<uint2> cursor;                 // [C]
+    DevBuf<sr_chain_live_row> commit_rows;  // [C]
+    uint32_t commit_W = 0, commit_ring = 64, commit_block = 1;
 };
 
 namespace {
@@ -128,6 +134,9 @@ int adopt(sr_onepass_gram_live *l, const sr_grammar *g)
     l->pruned = k.pruned;
     l->tpl_len = g->tpl_len;
     l->g = g;
+    l->commit_W = onepass_gram_commit_window(g->op_item_slots.data(), (uint32_t)g->op_item_slots.size(), l->h->tpl_len_host.data(), l->h->K);
+    l->commit_ring = onepass_gram_commit_ring(l->commit_W);
+    l->commit_block = onepass_gram_commit_block(reach_of(l->h));
     std::vector<SpotLiveChan> all(l->C, SpotLiveChan{});
     for (SpotLiveChan &ch : all) {
         ch.first_win = 1u;
@@ -136,6 +145,7 @@ int adopt(sr_onepass_gram_live *l, const sr_grammar *g)
     if (int rc = l->upload_chan(all, nullptr)) return rc;
     launch_onepass_gram_live_wipe(live_args(l, nullptr, 0, 1u, nullptr, nullptr), nullptr);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(l->cursor.p, 0, C * sizeof(uint2), nullptr));  // no channel has delivered a word
     HIP_TRY(hipStreamSynchronize(nullptr));
     return SR_OK;
 }
@@ -183,6 +193,51 @@ int push(sr_onepass_gram_live *l, const LiveIn &in, bool device, void *stream, c
             return launch_push(l, pl, f, rs, d_rec, d_words, s);
         },
         [&] { onepass_live_advance(l->om, pl, rows, n_rows); });
+}
+
+// a commit call up to its launch: the stale grammar first, then the rows of the distinct listed channels from the mirror, then
+// the checks -- nothing is enqueued, written or changed before all of them pass.  host: rows is a host buffer like crec and
+// cwords (the host form)
+int plan_commit(const sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, const sr_commit_rec *crec, const sr_chain_word *cwords,
+                const sr_chain_live_row *rows, bool host, std::vector<sr_chain_live_row> *order)
+{
+    if (!l) return fail(SR_ERR_BAD_ARG, "null session");
+    std::string why_stale, why;
+    const bool is_stale = stale(l, &why_stale);
+    if (!is_stale && n_ch && !channels) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (!onepass_gram_commit_list(l->om, is_stale, why_stale, channels, n_ch, order, &why)) return fail(SR_ERR_BAD_ARG, why);
+    const size_t n_out = order->size();
+    if (!n_out) return SR_OK;
+    if (!crec || !cwords || !rows) return fail(SR_ERR_BAD_ARG, "null argument");
+    if (int rc = check_store(l)) return rc;
+    const size_t n_c = n_out * sizeof *crec, n_w = n_out * l->words_cap * sizeof *cwords, n_r = n_out * sizeof *rows;
+    if (live_overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
+    if (host && (live_overlap(rows, n_r, crec, n_c) || live_overlap(rows, n_r, cwords, n_w)))
+        return fail(SR_ERR_BAD_ARG, "rows overlaps crec or cwords");
+    return SR_OK;
+}
+
+// ... and the launch on s: behind the session's last push or commit, and the next one runs behind it
+int enqueue_commit(sr_onepass_gram_live *l, const std::vector<sr_chain_live_row> &order, sr_commit_rec *d_crec, sr_chain_word *d_cwords,
+                   hipStream_t s)
+{
+    const sr_grammar *g = l->g;
+    if (int rc = l->order_after_last_push(s)) return rc;
+    // (a pageable source is staged before the call returns: the list may go out of scope)
+    HIP_TRY(hipMemcpyAsync(l->commit_rows.p, order.data(), order.size() * sizeof(sr_chain_live_row), hipMemcpyHostToDevice, s));
+    const GramCosts w = g->costs();
+    launch_onepass_gram_live_commit(
+        OnePassGramCommitArgs{live_args(l, nullptr, 0, 1u, nullptr, nullptr), l->commit_rows.p, (uint32_t)order.size(), l->commit_W, l->commit_ring, l->commit_block,
+                              (const uint32_t *)(g->blob.p + g->op_states_at), g->op_n_states, l->cursor.p, d_crec, d_cwords},
+        g->weighted ? &w : nullptr, s);
+    HIP_TRY(hipGetLastError());
+    return l->mark_push(s);
+}
+
+void label_commit(const std::vector<sr_chain_live_row> &order, sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    for (size_t r = 0; r < order.size(); r++) rows[r] = order[r];
+    if (n_rows) *n_rows = (uint32_t)order.size();
 }
 
 }  // namespace
@@ -233,6 +288,8 @@ int sr_onepass_gram_live_open(sr_engine *h, const sr_grammar *g, uint32_t n_chan
     l->word_cost = word_cost;
     int rc = l->open_common(h, n_channels, chunk_max, mid);
     if (!rc) rc = l->hist.reserve((size_t)n_channels * utt_frames * kCoef);
+    if (!rc) rc = l->cursor.reserve(n_channels);
+    if (!rc) rc = l->commit_rows.reserve(n_channels);
     if (!rc) rc = adopt(l, g);
     if (rc) {
         (void)hipGetLastError();
@@ -253,6 +310,8 @@ void sr_onepass_gram_live_close(sr_onepass_gram_live *l)
     l->A.release();
     l->E.release();
     l->hist.release();
+    l->cursor.release();
+    l->commit_rows.release();
     delete l;
 }
 
@@ -315,9 +374,42 @@ int sr_onepass_gram_live_end(sr_onepass_gram_live *l, const uint32_t *channels, 
     return live_end(
         *l, chan, order, l->words_cap, rec, words, nullptr, rows, n_rows, [] { return SR_OK; },
         [&](sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
-            launch_onepass_gram_live_end(live_args(l, nullptr, 0, 1u, d_rec, d_words), l->g->weighted ? &w : nullptr, nullptr);
+            launch_onepass_gram_live_end(live_args(l, nullptr, 0, 1u, d_rec, d_words), l->g->weighted ? &w : nullptr, l->cursor.p, nullptr);
         },
         [&] { onepass_live_reset(l->om, kGramLiveBound, order); });
+}
+
+int sr_onepass_gram_live_commit_dev(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *d_crec,
+                                    sr_chain_word *d_cwords, sr_chain_live_row *rows, uint32_t *n_rows, void *stream)
+{
+    std::vector<sr_chain_live_row> order;
+    if (int rc = plan_commit(l, channels, n_ch, d_crec, d_cwords, rows, false, &order)) return rc;
+    if (!order.empty()) {
+        ENTER_DEVICE(l->h);
+        if (int rc = enqueue_commit(l, order, d_crec, d_cwords, (hipStream_t)stream)) return rc;
+    }
+    label_commit(order, rows, n_rows);
+    return SR_OK;
+}
+
+int sr_onepass_gram_live_commit(sr_onepass_gram_live *l, const uint32_t *channels, uint32_t n_ch, sr_commit_rec *crec, sr_chain_word *cwords,
+                                sr_chain_live_row *rows, uint32_t *n_rows)
+{
+    std::vector<sr_chain_live_row> order;
+    if (int rc = plan_commit(l, channels, n_ch, crec, cwords, rows, true, &order)) return rc;
+    if (!order.empty()) {
+        ENTER_HOST_CALL(l->h);
+        const size_t n_out = order.size(), n_w = n_out * l->words_cap;
+        TmpDevBuf<sr_commit_rec> d_crec;  // per-call device copies of the outputs, reserved before anything is enqueued
+        TmpDevBuf<sr_chain_word> d_cwords;
+        if (int rc = d_crec.reserve(n_out)) return rc;
+        if (int rc = d_cwords.reserve(n_w)) return rc;
+        if (int rc = enqueue_commit(l, order, d_crec.p, d_cwords.p, nullptr)) return rc;
+        COPY_DOWN(crec, d_crec.p, n_out * sizeof *crec);
+        COPY_DOWN(cwords, d_cwords.p, n_w * sizeof *cwords);
+    }
+    label_commit(order, rows, n_rows);
+    return SR_OK;
 }
 
 }  // extern "C"

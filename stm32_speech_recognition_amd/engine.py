@@ -2189,8 +2189,9 @@ class OnePassGrammarSession(OnePassSession):
     """One sr_onepass_gram_live handle (Engine.decode_onepass_grammar_live): an OnePassSession under a Grammar.  After every
     push the row of a channel is Engine.decode_onepass_grammar on everything pushed to it as one row, the grammar state after
     each word in `reserved` (include/sr_engine.h, "live one-pass grammar decoding").  push, push_dev, push_pcm, push_pcm_dev,
-    end, frames and close are OnePassSession's; set_grammar switches the grammar while every channel is empty.  Close the
-    session before its grammar."""
+    end, frames, commit and commit_dev are OnePassSession's; set_grammar switches the grammar while every channel is empty.
+    commit says which words every parse the recording can still get begins with, also while the row itself is still CH_NONE;
+    the state after each word is in `reserved`.  Close the session before its grammar."""
 
     _PREFIX = "sr_onepass_gram_live_"
 
@@ -2198,16 +2199,17 @@ class OnePassGrammarSession(OnePassSession):
         super().__init__(eng, n_channels, chunk_max, utt_frames, words_cap, tail, skip_cost, word_cost, mid, _first=(gram.g,))
         self.gram = gram  # kept alive: the session is closed before its grammar
 
+    def _fn(self, name):
+        fn = super()._fn(name)
+        if name in ("commit", "commit_dev"):  # OnePassSession's methods through _PREFIX: (l, channels, n_ch, crec, cwords, rows, n_rows[, stream])
+            fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * (4 + (name == "commit_dev"))
+        return fn
+
     def set_grammar(self, gram):
         """sr_onepass_gram_live_set_grammar: the grammar of the next dialogue state, or a fresh one in the place of a stale
         one; raises unless every channel is empty (freshly opened or ended)"""
         self.eng._check(self._fn("set_grammar")(self.l, gram.g))
         self.gram = gram
-
-    def commit(self, channels=None, stream=None):
-        raise SrError("grammar sessions have no commit call (include/sr_engine.h, live one-pass section: out of scope)")
-
-    commit_dev = commit
 
 
 def grammar_live_geometry(gram, max_words, utt_frames, chunk_max):
