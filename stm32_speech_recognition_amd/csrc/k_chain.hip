@@ -17,6 +17,7 @@
 // Costs are u32 and exact: d <= 65 536, at most 3L cells per word over L frames, N <= 16 383, 16 words of word_cost <= 2^24.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -53,13 +54,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_chain_words(const ChainArgs
     uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
     M = M < a.tpl_len ? M : a.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(ch_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot
-        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        ch_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        ch_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(ch_smem, a.tpl + (size_t)k * a.tpl_stride, M);
     __syncthreads();
     if (chunk >= a.n_chunks || !M) return;
 
@@ -77,52 +72,17 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_chain_words(const ChainArgs
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
         uint32_t charge = kChainNone;  // E_{l-1}(col): what a word that starts in this column builds on
         if (live) {
-            const uint2 *src = (const uint2 *)(in + (size_t)col * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
+            fi = sweep_frame(in + (size_t)col * kCoef);
             charge = e_prev[col];
         }
-        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
-        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
-        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
-        const uint32_t steps = M + (cN - x0 < 64u ? cN - x0 : 64u) - 1;
-        for (uint32_t t = 0; t < steps; t++) {
-            const int r = (int)t - (int)lane;
-            // the left lane's results of the previous step are the states of (col - 1, r)
-            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
-            if (lane == 0) {
-                fl_d = fl_m = kSpotInf;
-                if (x0 != cs && t < M) {
-                    const ulonglong2 v = s_col[t];
-                    fl_d = v.x;
-                    fl_m = v.y;
-                }
-            }
-            if (live && r >= 0 && r < (int)M) {
-                const Row32 fm = row_from(ch_smem[2 * r], ch_smem[2 * r + 1]);
-                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
-                uint64_t cd = kSpotInf, cn;
-                if (r > 0) {
-                    cd = spot_add(diag, d);
-                    cn = spot_add(spot_min(fl_d, up_d), d);
-                } else {  // row 0: a charged start, of the non-diagonal kind
-                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
-                }
-                up_d = cd;
-                up_m = spot_min(cd, cn);
-                if (lane == 63) s_col[r] = ulonglong2{up_d, up_m};
-                if (r == (int)M - 1) end_v = up_m;
-            }
-            diag = fl_m;
-        }
+        const uint32_t end_lane = (cN - x0 < 64u ? cN - x0 : 64u) - 1;  // the sweep's last live lane
+        SweepLane sw;
+        for (uint32_t t = 0; t < M + end_lane; t++)
+            sweep_step(ch_smem, s_col, nullptr, false, fi, charge, col, live, x0 != cs, 63, M, lane, t, sw);
         wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
 
         // the key of each end frame of the chunk: (cost + word_cost, start, slot) -> A_l(col + 1); col + 1 <= N <= max_frames
-        if (live && col >= c0 && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
+        if (live && col >= c0 && sw.end_v != kSpotInf) atomicMin(&A[col + 1], sweep_end_key(sw.end_v, a.word_cost, k));
     }
 }
 

@@ -19,14 +19,14 @@
 // There is no charge kernel and no row of charges: a push has few columns, a launch more per level would cost more than the
 // loads it saves.  No workgroup waits on another: the levels are ordered by the stream alone.  Plain vector stores; the atomic
 // minimum on A is the only atomic, and it does not depend on the order of the waves, so two runs give the same bytes.  The
-// sweep, the close and the walk are restated here and not shared: k_chain_live.hip and k_gram.hip stay byte for byte what
-// they were measured as.
+// staging, the frame load, the key and the close are sr_sweep_dev.h's; k_gram_live_words keeps its charge and its step loop.
 //
 // A WEIGHTED grammar (include/sr_engine.h, "weighted grammars") takes k_gram_live_words_w and k_gram_live_trace_w, with the
 // costs in a second argument block, in the places of the sweep and the trace; init and close serve it unchanged.  A grammar
 // without a nonzero cost launches exactly what it always has.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -57,6 +57,9 @@ __global__ void __launch_bounds__(256) k_gram_live_init(const GramLiveArgs a)
     }
 }
 
+// The sweep of one level.  This kernel holds its whole body, the charge of a column and the step loop included, and shares
+// only the staging, the frame load and the key (sr_sweep_dev.h): as one inline body with its weighted twin, behind a one-line
+// kernel, its step loop had one v_add more than unshared and it measured 0.2 to 0.5 % slower (profiles/experiments/RESULTS.md).
 __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words(const GramLiveArgs a, const uint32_t level)
 {
     extern __shared__ __attribute__((aligned(16))) u32x4 gl_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
@@ -66,13 +69,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words(const GramL
     uint32_t M = a.c.tpl_valid[k] ? a.c.tpl_frames[k] : 0u;
     M = M < a.c.tpl_len ? M : a.c.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(gl_smem + (size_t)a.c.tpl_len * 2) + (size_t)w * a.c.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.c.tpl + (size_t)k * a.c.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        gl_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        gl_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(gl_smem, a.c.tpl + (size_t)k * a.c.tpl_stride, M);
     __syncthreads();
     if (c >= a.c.C || !M) return;  // (a grammar keeps items of valid slots only)
     const SpotLiveChan ch = a.c.chan[c];
@@ -93,12 +90,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words(const GramL
         const bool live = col < cN;
         const uint32_t last = (cN - x0 < 64u ? cN - x0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {
-            const uint2 *src = (const uint2 *)(in + (size_t)(col - xs) * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
+        if (live) fi = sweep_frame(in + (size_t)(col - xs) * kCoef);
         // C_l(col): what a word that starts in this column builds on, the cheapest state of the from-set
         uint32_t charge = kChainNone;
         for (unsigned long long m = mask; m; m &= m - 1) {  // (wave-uniform; col <= utt_frames - 1 where live)
@@ -142,17 +134,15 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words(const GramL
         wave_sync();  // the boundary column is complete before the next sweep's lane 0, or the save below, reads it
 
         // the key of each new end frame: (cost + word_cost, start, slot) -> A_l(col + 1, target); col + 1 <= cN <= utt_frames
-        if (live && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.c.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
+        if (live && end_v != kSpotInf) atomicMin(&A[col + 1], sweep_end_key(end_v, a.c.word_cost, k));
     }
     // the state for the next push: column cN - 1 (16-byte stores, coalesced over template rows)
     for (uint32_t r = lane; r < M; r += 64) g_col[r] = s_col[r];
 }
 
+
 // k_gram_live_words under costs (include/sr_engine.h, "weighted grammars"): the same resumed sweep, the charge of a column
-// taken over the item's charge list with the arc costs added.  Restated: k_gram_live_words stays byte for byte.
+// taken over the item's charge list with the arc costs added (gram_charge), the step sweep_step.
 __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words_w(const GramLiveArgs a, const GramCosts wt, const uint32_t level)
 {
     extern __shared__ __attribute__((aligned(16))) u32x4 glw_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
@@ -162,13 +152,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words_w(const Gra
     uint32_t M = a.c.tpl_valid[k] ? a.c.tpl_frames[k] : 0u;
     M = M < a.c.tpl_len ? M : a.c.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(glw_smem + (size_t)a.c.tpl_len * 2) + (size_t)w * a.c.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.c.tpl + (size_t)k * a.c.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        glw_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        glw_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(glw_smem, a.c.tpl + (size_t)k * a.c.tpl_stride, M);
     __syncthreads();
     if (c >= a.c.C || !M) return;  // (a grammar keeps items of valid slots only)
     const SpotLiveChan ch = a.c.chan[c];
@@ -178,7 +162,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words_w(const Gra
     ulonglong2 *g_col = a.c.cols + (((size_t)c * a.columns + a.col_off[level - 1] + blockIdx.x)) * a.c.tpl_len;
     const uint32_t *e_prev = gram_live_E(a, c, level - 1, 0);  // state s at e_prev + s * P
     const unsigned long long mask = a.masks[it.set];
-    const uint32_t *cost = wt.cost + wt.cost_off[it.set];  // by ascending state, as the mask is walked
+    const uint32_t *cost = gram_costs_of(&wt, it.set);  // by ascending state, as the mask is walked
     unsigned long long *A = gram_live_A(a, c, level, it.target);
     if (xs) {  // resume: the saved column (16-byte loads, coalesced over template rows)
         for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
@@ -190,61 +174,16 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words_w(const Gra
         const bool live = col < cN;
         const uint32_t last = (cN - x0 < 64u ? cN - x0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {
-            const uint2 *src = (const uint2 *)(in + (size_t)(col - xs) * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
-        // C_l(col): what a word that starts in this column builds on, the cheapest E + arc cost of the charge list; an
-        // unreachable E takes no cost (all ones + c would wrap to c - 1 and win)
-        uint32_t charge = kChainNone;
-        uint32_t j = 0;
-        for (unsigned long long m = mask; m; m &= m - 1, j++) {  // (wave-uniform; col <= utt_frames - 1 where live)
-            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
-            const uint32_t e = live ? e_prev[(size_t)s * a.c.P + col] : kChainNone, v = e + cost[j];
-            charge = (e != kChainNone && v < charge) ? v : charge;
-        }
-        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
-        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
-        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
-        const uint32_t steps = M + last;
-        for (uint32_t t = 0; t < steps; t++) {
-            const int r = (int)t - (int)lane;
-            // the left lane's results of the previous step are the states of (col - 1, r)
-            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
-            if (lane == 0) {
-                fl_d = fl_m = kSpotInf;
-                if (x0 != 0 && t < M) {  // column x0 - 1: this call's last sweep, or the last push (none for a fresh channel)
-                    const ulonglong2 v = s_col[t];
-                    fl_d = v.x;
-                    fl_m = v.y;
-                }
-            }
-            if (live && r >= 0 && r < (int)M) {
-                const Row32 fm = row_from(glw_smem[2 * r], glw_smem[2 * r + 1]);
-                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
-                uint64_t cd = kSpotInf, cn;
-                if (r > 0) {
-                    cd = spot_add(diag, d);
-                    cn = spot_add(spot_min(fl_d, up_d), d);
-                } else {  // row 0: a charged start, of the non-diagonal kind
-                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
-                }
-                up_d = cd;
-                up_m = spot_min(cd, cn);
-                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
-                if (r == (int)M - 1) end_v = up_m;
-            }
-            diag = fl_m;
-        }
+        if (live) fi = sweep_frame(in + (size_t)(col - xs) * kCoef);
+        // C_l(col): the cheapest E + arc cost of the item's charge list (col <= utt_frames - 1 where live)
+        const uint32_t charge = gram_charge(e_prev, a.c.P, col, live, mask, cost);
+        SweepLane sw;
+        for (uint32_t t = 0; t < M + last; t++)
+            sweep_step(glw_smem, s_col, nullptr, false, fi, charge, col, live, x0 != 0, last, M, lane, t, sw);
         wave_sync();  // the boundary column is complete before the next sweep's lane 0, or the save below, reads it
 
         // the key of each new end frame: (cost + word_cost, start, slot) -> A_l(col + 1, target); col + 1 <= cN <= utt_frames
-        if (live && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.c.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
+        if (live && sw.end_v != kSpotInf) atomicMin(&A[col + 1], sweep_end_key(sw.end_v, a.c.word_cost, k));
     }
     // the state for the next push: column cN - 1 (16-byte stores, coalesced over template rows)
     for (uint32_t r = lane; r < M; r += 64) g_col[r] = s_col[r];
@@ -256,40 +195,14 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_gram_live_words_w(const Gra
 __global__ void __launch_bounds__(256) k_gram_live_close(const GramLiveArgs a, const uint32_t level)
 {
     __shared__ uint64_t s_tot[4];
-    const uint32_t c = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t c = blockIdx.x;
     const uint32_t state = a.lists[a.lv[level - 1].state0 + blockIdx.y];
     const SpotLiveChan ch = a.c.chan[c];
     if (!ch.n) return;  // (uniform)
     const uint32_t xs = ch.x0, cN = ch.x0 + ch.n;
     const unsigned long long *A = gram_live_A(a, c, level, state);
     uint32_t *E = gram_live_E(a, c, level, state);
-    if (a.c.skip_cost == kChainNone) {  // no skipping: the costs themselves (all ones stays SR_DIS_ERR)
-        for (uint32_t p = xs + 1 + threadIdx.x; p <= cN; p += 256) E[p] = (uint32_t)(A[p] >> 32);
-        return;
-    }
-    const uint64_t skip = a.c.skip_cost;
-    const uint32_t e_x0 = E[xs];  // (written by the last push's close or init, or by this push's init for a fresh channel)
-    uint64_t carry = e_x0 == kChainNone ? kSpotInf : (uint64_t)e_x0 + (uint64_t)(cN - xs) * skip;
-    for (uint32_t p0 = xs + 1; p0 <= cN; p0 += 256) {  // (uniform)
-        const uint32_t p = p0 + threadIdx.x;
-        uint64_t v = kSpotInf;
-        if (p <= cN) {
-            const uint64_t key = A[p];
-            if (key != kSpotInf) v = (key >> 32) + (uint64_t)(cN - p) * skip;
-        }
-#pragma unroll
-        for (uint32_t by = 1; by < 64; by <<= 1) {
-            const uint64_t o = spot_shfl_up(v, by);
-            if (lane >= by) v = spot_min(v, o);
-        }
-        if (lane == 63) s_tot[w] = v;
-        __syncthreads();
-        uint64_t m = spot_min(v, carry);
-        for (uint32_t i = 0; i < w; i++) m = spot_min(m, s_tot[i]);
-        if (p <= cN) E[p] = m != kSpotInf ? (uint32_t)(m - (uint64_t)(cN - p) * skip) : kChainNone;
-        for (uint32_t i = 0; i < 4; i++) carry = spot_min(carry, s_tot[i]);
-        __syncthreads();  // s_tot is read before the next block overwrites it
-    }
+    close_window(A, E, xs, cN, a.c.skip_cost, s_tot);
 }
 
 // One wave per emitting channel: k_gram_trace's level costs, count, end state and walk back through levels and states, with
@@ -390,7 +303,7 @@ __global__ void __launch_bounds__(64) k_gram_live_trace(const GramLiveArgs a)
 }
 
 // k_gram_live_trace under costs, as k_gram_trace_w: L_l adds the final cost, the charge and the source state of a word are
-// judged on E_{l-1} + the arc cost, both over reachable E only.  Restated: k_gram_live_trace stays byte for byte.
+// judged on E_{l-1} + the arc cost, both over reachable E only.  A kernel of its own beside k_gram_live_trace.
 __global__ void __launch_bounds__(64) k_gram_live_trace_w(const GramLiveArgs a, const GramCosts wt)
 {
     const uint32_t c = blockIdx.x, W = a.c.max_words, S = a.n_states, lane = threadIdx.x;

@@ -21,6 +21,7 @@
 // the only atomic, and it does not depend on the order of the waves, so two runs give the same bytes.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -47,13 +48,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_words(const OnePass
     uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
     M = M < a.tpl_len ? M : a.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(op_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        op_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        op_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(op_smem, a.tpl + (size_t)k * a.tpl_stride, M);
     __syncthreads();
     if (row >= a.n_rows || !M) return;  // (an invalid slot ends no word and keeps no column)
     const uint32_t N = onepass_frames(a, row);
@@ -76,53 +71,16 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_words(const OnePass
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
         uint32_t charge = kChainNone;  // E(col): what a word that starts in this column builds on; none yet inside the block
         if (live) {
-            const uint2 *src = (const uint2 *)(in + (size_t)col * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
+            fi = sweep_frame(in + (size_t)col * kCoef);
             if (col <= c0) charge = E[col];
         }
-        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
-        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
-        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
-        const uint32_t steps = M + last;
-        for (uint32_t t = 0; t < steps; t++) {
-            const int r = (int)t - (int)lane;
-            // the left lane's results of the previous step are the states of (col - 1, r)
-            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
-            if (lane == 0) {
-                fl_d = fl_m = kSpotInf;
-                if (x0 != 0 && t < M) {  // column x0 - 1: this call's last sweep, or the saved column (none for column 0)
-                    const ulonglong2 v = s_col[t];
-                    fl_d = v.x;
-                    fl_m = v.y;
-                }
-            }
-            if (live && r >= 0 && r < (int)M) {
-                const Row32 fm = row_from(op_smem[2 * r], op_smem[2 * r + 1]);
-                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
-                uint64_t cd = kSpotInf, cn;
-                if (r > 0) {
-                    cd = spot_add(diag, d);
-                    cn = spot_add(spot_min(fl_d, up_d), d);
-                } else {  // row 0: a charged start, of the non-diagonal kind
-                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
-                }
-                up_d = cd;
-                up_m = spot_min(cd, cn);
-                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
-                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
-                if (r == (int)M - 1) end_v = up_m;
-            }
-            diag = fl_m;
-        }
+        SweepLane sw;
+        for (uint32_t t = 0; t < M + last; t++)
+            sweep_step(op_smem, s_col, g_col, keep, fi, charge, col, live, x0 != 0, last, M, lane, t, sw);
         wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
 
         // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1); col + 1 <= cN <= max_frames
-        if (live && col >= c0 && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
+        if (live && col >= c0 && sw.end_v != kSpotInf) atomicMin(&A[col + 1], sweep_end_key(sw.end_v, a.word_cost, k));
     }
 }
 
@@ -132,39 +90,13 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_words(const OnePass
 __global__ void __launch_bounds__(256) k_onepass_close(const OnePassArgs a, const uint32_t c0, const uint32_t cN_blk)
 {
     __shared__ uint64_t s_tot[4];
-    const uint32_t row = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, P = a.max_frames + 1u;
+    const uint32_t row = blockIdx.x, P = a.max_frames + 1u;
     const uint32_t N = onepass_frames(a, row);
     if (N <= c0) return;  // (uniform)
     const uint32_t cN = cN_blk < N ? cN_blk : N;
     const unsigned long long *A = a.A + (size_t)row * P;
     uint32_t *E = a.E + (size_t)row * P;
-    if (a.skip_cost == kChainNone) {  // no skipping: the costs themselves (all ones stays SR_DIS_ERR)
-        for (uint32_t p = c0 + 1 + threadIdx.x; p <= cN; p += 256) E[p] = (uint32_t)(A[p] >> 32);
-        return;
-    }
-    const uint64_t skip = a.skip_cost;
-    const uint32_t e_c0 = E[c0];  // (written by the last block's close, or by init for the first block)
-    uint64_t carry = e_c0 == kChainNone ? kSpotInf : (uint64_t)e_c0 + (uint64_t)(cN - c0) * skip;
-    for (uint32_t p0 = c0 + 1; p0 <= cN; p0 += 256) {  // (uniform)
-        const uint32_t p = p0 + threadIdx.x;
-        uint64_t v = kSpotInf;
-        if (p <= cN) {
-            const uint64_t key = A[p];
-            if (key != kSpotInf) v = (key >> 32) + (uint64_t)(cN - p) * skip;
-        }
-#pragma unroll
-        for (uint32_t by = 1; by < 64; by <<= 1) {
-            const uint64_t o = spot_shfl_up(v, by);
-            if (lane >= by) v = spot_min(v, o);
-        }
-        if (lane == 63) s_tot[w] = v;
-        __syncthreads();
-        uint64_t m = spot_min(v, carry);
-        for (uint32_t i = 0; i < w; i++) m = spot_min(m, s_tot[i]);
-        if (p <= cN) E[p] = m != kSpotInf ? (uint32_t)(m - (uint64_t)(cN - p) * skip) : kChainNone;
-        for (uint32_t i = 0; i < 4; i++) carry = spot_min(carry, s_tot[i]);
-        __syncthreads();  // s_tot is read before the next round overwrites it
-    }
+    close_window(A, E, c0, cN, a.skip_cost, s_tot);
 }
 
 // one wave per row: the history is walked twice (onepass_word_at, sr_spot_dev.h), first for the count, then for the words in

@@ -24,10 +24,11 @@
 // (k_onepass_gram_live_wipe).  Where no state is kept no item is kept either (a kept item's charge list is kept): nothing sweeps,
 // nothing closes, nothing parses, and the feature row is neither written nor read.  No workgroup waits on another: the blocks are
 // ordered by the stream alone.  Plain vector stores; the atomic minimum on A is the only atomic, and it does not depend on the
-// order of the waves, so two runs give the same bytes.  The sweep, the close and the walk are restated here and not shared:
-// k_onepass_gram.hip, k_onepass_live.hip and k_gram_live.hip stay byte for byte what they were measured as.
+// order of the waves, so two runs give the same bytes.  The sweep, the close and the charge of a column are sr_sweep_dev.h's;
+// the two sweeps are one body (opgl_words), compiled with and without costs.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -49,8 +50,9 @@ __device__ __forceinline__ uint32_t *opgl_E(const OnePassGramLiveArgs &a, uint32
 }
 __device__ __forceinline__ uint32_t opgl_state(const OnePassGramLiveArgs &a, uint32_t i) { return a.keep_states ? a.keep_states[i] : i; }
 
-// block b of every (kept item, channel)
-__global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(const OnePassGramLiveArgs a, const uint32_t b)
+// block b of every (kept item, channel).  wt: null, or the costs of a weighted grammar (include/sr_engine.h, "weighted
+// grammars"): the charge of a column is then taken over the item's charge list with the arc costs added
+__device__ __forceinline__ void opgl_words(const OnePassGramLiveArgs &a, const GramCosts *wt, const uint32_t b)
 {
     extern __shared__ __attribute__((aligned(16))) u32x4 ogl_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
     const GramItem it = a.items[a.keep_items ? a.keep_items[blockIdx.x] : blockIdx.x];
@@ -59,13 +61,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(con
     uint32_t M = a.o.tpl_valid[k] ? a.o.tpl_frames[k] : 0u;
     M = M < a.o.tpl_len ? M : a.o.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(ogl_smem + (size_t)a.o.tpl_len * 2) + (size_t)w * a.o.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.o.tpl + (size_t)k * a.o.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        ogl_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        ogl_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(ogl_smem, a.o.tpl + (size_t)k * a.o.tpl_stride, M);
     __syncthreads();
     if (c >= a.o.C || !M) return;  // (a grammar keeps items of valid slots only)
     const SpotLiveChan ch = a.o.chan[c];
@@ -78,6 +74,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(con
     ulonglong2 *g_col = a.o.cols + ((size_t)c * a.n_keep_items + blockIdx.x) * a.o.tpl_len;
     const uint32_t *E = opgl_E(a, c, 0);  // state s at E + s * P
     const unsigned long long mask = a.masks[it.set];
+    const uint32_t *cost = gram_costs_of(wt, it.set);  // by ascending state, as the mask is walked
     unsigned long long *A = opgl_A(a, c, it.target);
     if (xs) {  // resume: the saved column, that of xs - 1 (16-byte loads, coalesced over template rows)
         for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
@@ -91,167 +88,24 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(con
         const uint32_t last = (cN - s0 < 64u ? cN - s0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
         const bool keep = col == c0;                                // the exact column the next block resumes from
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {
-            const uint2 *src = (const uint2 *)(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
+        if (live) fi = sweep_frame(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
         // C(col): what a word that starts in this column builds on, the cheapest state of the charge list; final for col <= c0,
-        // none yet inside the block
-        uint32_t charge = kChainNone;
-        const bool charged = live && col <= c0;  // (col <= c0 < utt_frames: inside the state's row)
-        for (unsigned long long m = mask; m; m &= m - 1) {  // (wave-uniform)
-            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
-            const uint32_t e = charged ? E[(size_t)s * P + col] : kChainNone;
-            charge = e < charge ? e : charge;
-        }
-        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
-        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
-        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
-        const uint32_t steps = M + last;
-        for (uint32_t t = 0; t < steps; t++) {
-            const int r = (int)t - (int)lane;
-            // the left lane's results of the previous step are the states of (col - 1, r)
-            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
-            if (lane == 0) {
-                fl_d = fl_m = kSpotInf;
-                if (s0 != 0 && t < M) {  // column s0 - 1: this launch's last sweep, or the saved column (none for column 0)
-                    const ulonglong2 v = s_col[t];
-                    fl_d = v.x;
-                    fl_m = v.y;
-                }
-            }
-            if (live && r >= 0 && r < (int)M) {
-                const Row32 fm = row_from(ogl_smem[2 * r], ogl_smem[2 * r + 1]);
-                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
-                uint64_t cd = kSpotInf, cn;
-                if (r > 0) {
-                    cd = spot_add(diag, d);
-                    cn = spot_add(spot_min(fl_d, up_d), d);
-                } else {  // row 0: a charged start, of the non-diagonal kind
-                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
-                }
-                up_d = cd;
-                up_m = spot_min(cd, cn);
-                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
-                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
-                if (r == (int)M - 1) end_v = up_m;
-            }
-            diag = fl_m;
-        }
+        // none yet inside the block (col <= c0 < utt_frames: inside the state's row)
+        const uint32_t charge = gram_charge(E, P, col, live && col <= c0, mask, cost);
+        SweepLane sw;
+        for (uint32_t t = 0; t < M + last; t++)
+            sweep_step(ogl_smem, s_col, g_col, keep, fi, charge, col, live, s0 != 0, last, M, lane, t, sw);
         wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
 
         // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1, target); col + 1 <= cN <= utt_frames
-        if (live && col >= c0 && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.o.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
+        if (live && col >= c0 && sw.end_v != kSpotInf) atomicMin(&A[col + 1], sweep_end_key(sw.end_v, a.o.word_cost, k));
     }
 }
 
-// k_onepass_gram_live_words under costs (include/sr_engine.h, "weighted grammars"): the same resumed sweep, the charge of a
-// column taken over the item's charge list with the arc costs added.  Restated: k_onepass_gram_live_words stays what it is.
+__global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words(const OnePassGramLiveArgs a, const uint32_t b) { opgl_words(a, nullptr, b); }
 __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words_w(const OnePassGramLiveArgs a, const GramCosts wt, const uint32_t b)
 {
-    extern __shared__ __attribute__((aligned(16))) u32x4 oglw_smem[];  // template rows [tpl_len][2], then the waves' boundary columns
-    const GramItem it = a.items[a.keep_items ? a.keep_items[blockIdx.x] : blockIdx.x];
-    const uint32_t k = it.slot, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t c = blockIdx.y * kSpotWaves + w;
-    uint32_t M = a.o.tpl_valid[k] ? a.o.tpl_frames[k] : 0u;
-    M = M < a.o.tpl_len ? M : a.o.tpl_len;
-    ulonglong2 *s_col = (ulonglong2 *)(oglw_smem + (size_t)a.o.tpl_len * 2) + (size_t)w * a.o.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.o.tpl + (size_t)k * a.o.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        oglw_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        oglw_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
-    __syncthreads();
-    if (c >= a.o.C || !M) return;  // (a grammar keeps items of valid slots only)
-    const SpotLiveChan ch = a.o.chan[c];
-    uint32_t c0, cN;
-    if (!opgl_block(a, ch, b, &c0, &cN)) return;  // (wave-uniform)
-    // the sweep starts behind the saved column: that of this push's last block, or of the last push's (none at frame 0)
-    const uint32_t xs = c0 ? (b ? c0 - a.o.block : ch.aux) + 1u : 0u;
-    const uint32_t P = a.o.P;
-
-    ulonglong2 *g_col = a.o.cols + ((size_t)c * a.n_keep_items + blockIdx.x) * a.o.tpl_len;
-    const uint32_t *E = opgl_E(a, c, 0);  // state s at E + s * P
-    const unsigned long long mask = a.masks[it.set];
-    const uint32_t *cost = wt.cost + wt.cost_off[it.set];  // by ascending state, as the mask is walked
-    unsigned long long *A = opgl_A(a, c, it.target);
-    if (xs) {  // resume: the saved column, that of xs - 1 (16-byte loads, coalesced over template rows)
-        for (uint32_t r = lane; r < M; r += 64) s_col[r] = g_col[r];
-        wave_sync();
-    }
-    const int16_t *kept = a.o.feat + (size_t)c * (P - 1u) * kCoef;  // the columns before the push
-    const int16_t *in = a.o.mfcc + (uint64_t)c * a.o.row_stride;     // the columns [x0, x0 + n)
-    for (uint32_t s0 = xs; s0 < cN; s0 += 64) {  // (wave-uniform)
-        const uint32_t col = s0 + lane;
-        const bool live = col < cN;
-        const uint32_t last = (cN - s0 < 64u ? cN - s0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
-        const bool keep = col == c0;                                // the exact column the next block resumes from
-        Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {
-            const uint2 *src = (const uint2 *)(col < ch.x0 ? kept + (size_t)col * kCoef : in + (size_t)(col - ch.x0) * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
-        // C(col): the cheapest E + arc cost of the charge list; an unreachable E takes no cost (all ones + c would wrap to
-        // c - 1 and win); final for col <= c0, none yet inside the block
-        uint32_t charge = kChainNone;
-        const bool charged = live && col <= c0;  // (col <= c0 < utt_frames: inside the state's row)
-        uint32_t j = 0;
-        for (unsigned long long m = mask; m; m &= m - 1, j++) {  // (wave-uniform)
-            const uint32_t s = (uint32_t)__ffsll((long long)m) - 1u;
-            const uint32_t e = charged ? E[(size_t)s * P + col] : kChainNone, v = e + cost[j];
-            charge = (e != kChainNone && v < charge) ? v : charge;
-        }
-        uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
-        uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
-        uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
-        const uint32_t steps = M + last;
-        for (uint32_t t = 0; t < steps; t++) {
-            const int r = (int)t - (int)lane;
-            // the left lane's results of the previous step are the states of (col - 1, r)
-            uint64_t fl_d = spot_shfl_up(up_d, 1), fl_m = spot_shfl_up(up_m, 1);
-            if (lane == 0) {
-                fl_d = fl_m = kSpotInf;
-                if (s0 != 0 && t < M) {  // column s0 - 1: this launch's last sweep, or the saved column (none for column 0)
-                    const ulonglong2 v = s_col[t];
-                    fl_d = v.x;
-                    fl_m = v.y;
-                }
-            }
-            if (live && r >= 0 && r < (int)M) {
-                const Row32 fm = row_from(oglw_smem[2 * r], oglw_smem[2 * r + 1]);
-                const uint32_t d = dis_from(fi.w[6], fm.w[6], dot_rows(fi, fm));
-                uint64_t cd = kSpotInf, cn;
-                if (r > 0) {
-                    cd = spot_add(diag, d);
-                    cn = spot_add(spot_min(fl_d, up_d), d);
-                } else {  // row 0: a charged start, of the non-diagonal kind
-                    cn = charge == kChainNone ? kSpotInf : ((uint64_t)(charge + d) << 32) | col;
-                }
-                up_d = cd;
-                up_m = spot_min(cd, cn);
-                if (lane == last) s_col[r] = ulonglong2{up_d, up_m};  // (lane 0 has read row r before it writes it)
-                if (keep) g_col[r] = ulonglong2{up_d, up_m};          // (the old saved column went to LDS before the first sweep)
-                if (r == (int)M - 1) end_v = up_m;
-            }
-            diag = fl_m;
-        }
-        wave_sync();  // the boundary column is complete before the next sweep's lane 0 reads it
-
-        // the key of each end frame of the block: (cost + word_cost, start, slot) -> A(col + 1, target); col + 1 <= cN <= utt_frames
-        if (live && col >= c0 && end_v != kSpotInf) {
-            const uint64_t key = ((uint64_t)((uint32_t)(end_v >> 32) + a.o.word_cost) << 32) | ((uint64_t)(uint32_t)end_v << 16) | k;
-            atomicMin(&A[col + 1], (unsigned long long)key);
-        }
-    }
+    opgl_words(a, &wt, b);
 }
 
 // k_onepass_gram_close per (channel, kept state) and channel block; grid (channels, kept states).  A state that no key arrived
@@ -260,7 +114,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_onepass_gram_live_words_w(c
 __global__ void __launch_bounds__(256) k_onepass_gram_live_close(const OnePassGramLiveArgs a, const uint32_t b)
 {
     __shared__ uint64_t s_tot[4];
-    const uint32_t c = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t c = blockIdx.x;
     const uint32_t state = opgl_state(a, blockIdx.y);
     const SpotLiveChan ch = a.o.chan[c];
     uint32_t c0, cN;
@@ -272,33 +126,7 @@ __global__ void __launch_bounds__(256) k_onepass_gram_live_close(const OnePassGr
     }
     const unsigned long long *A = opgl_A(a, c, state);
     uint32_t *E = opgl_E(a, c, state);
-    if (a.o.skip_cost == kChainNone) {  // no skipping: the costs themselves (all ones stays SR_DIS_ERR)
-        for (uint32_t p = c0 + 1 + threadIdx.x; p <= cN; p += 256) E[p] = (uint32_t)(A[p] >> 32);
-        return;
-    }
-    const uint64_t skip = a.o.skip_cost;
-    const uint32_t e_c0 = E[c0];  // (written by the last block's close, in this push or the last; the invariant at frame 0)
-    uint64_t carry = e_c0 == kChainNone ? kSpotInf : (uint64_t)e_c0 + (uint64_t)(cN - c0) * skip;
-    for (uint32_t p0 = c0 + 1; p0 <= cN; p0 += 256) {  // (uniform)
-        const uint32_t p = p0 + threadIdx.x;
-        uint64_t v = kSpotInf;
-        if (p <= cN) {
-            const uint64_t key = A[p];
-            if (key != kSpotInf) v = (key >> 32) + (uint64_t)(cN - p) * skip;
-        }
-#pragma unroll
-        for (uint32_t by = 1; by < 64; by <<= 1) {
-            const uint64_t o = spot_shfl_up(v, by);
-            if (lane >= by) v = spot_min(v, o);
-        }
-        if (lane == 63) s_tot[w] = v;
-        __syncthreads();
-        uint64_t m = spot_min(v, carry);
-        for (uint32_t i = 0; i < w; i++) m = spot_min(m, s_tot[i]);
-        if (p <= cN) E[p] = m != kSpotInf ? (uint32_t)(m - (uint64_t)(cN - p) * skip) : kChainNone;
-        for (uint32_t i = 0; i < 4; i++) carry = spot_min(carry, s_tot[i]);
-        __syncthreads();  // s_tot is read before the next round overwrites it
-    }
+    close_window(A, E, c0, cN, a.o.skip_cost, s_tot);
 }
 
 // the item (slot, t) by bisection of the items, which ascend by (slot, target): its index, or n_items

@@ -19,6 +19,7 @@
 
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -37,13 +38,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_span_words(const SpanArgs a
     uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
     M = M < a.tpl_len ? M : a.tpl_len;
     uint2 *s_col = (uint2 *)(sn_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot
-        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        sn_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        sn_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(sn_smem, a.tpl + (size_t)k * a.tpl_stride, M);
     __syncthreads();
     if (span >= a.n_spans) return;
 
@@ -65,12 +60,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_span_words(const SpanArgs a
         const uint32_t col = x0 + lane;
         const bool live = col <= e;
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {  // S <= col <= e < N: inside the row's frames
-            const uint2 *src = (const uint2 *)(in + (size_t)col * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
+        if (live) fi = sweep_frame(in + (size_t)col * kCoef);  // S <= col <= e < N: inside the row's frames
         uint32_t up_d = kSpanInf, up_m = kSpanInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
         uint32_t diag = kSpanInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
         const uint32_t steps = M + (e + 1 - x0 < 64u ? e + 1 - x0 : 64u) - 1;

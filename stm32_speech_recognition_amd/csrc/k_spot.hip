@@ -21,6 +21,7 @@
 // leaves a partial record that k_spot_finish reduces in chunk order.  No atomics; every record is written exactly once.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -40,13 +41,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_spot(const SpotArgs a)
     uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
     M = M < a.tpl_len ? M : a.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(sp_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as dp_wave64_stage
-        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        sp_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        sp_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(sp_smem, a.tpl + (size_t)k * a.tpl_stride, M);
     __syncthreads();
     if (chunk >= a.n_chunks) return;
 
@@ -89,12 +84,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_spot(const SpotArgs a)
             const uint32_t col = x0 + lane;
             const bool live = col < cN;
             Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-            if (live) {
-                const uint2 *src = (const uint2 *)(in + (size_t)col * kCoef);
-                const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-                fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-                fi.w[6] = (uint32_t)dot_rows(fi, fi);
-            }
+            if (live) fi = sweep_frame(in + (size_t)col * kCoef);
             uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
             uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
             uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)

@@ -14,6 +14,7 @@
 // the row the host assigned (it knows every count).  No atomics, no flags between workgroups, plain stores.
 #include "sr_dtw_plan.h"
 #include "sr_spot_dev.h"
+#include "sr_sweep_dev.h"
 
 namespace sr {
 
@@ -38,13 +39,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_spot_live(const SpotLiveArg
     uint32_t M = a.tpl_valid[k] ? a.tpl_frames[k] : 0u;
     M = M < a.tpl_len ? M : a.tpl_len;
     ulonglong2 *s_col = (ulonglong2 *)(sl_smem + (size_t)a.tpl_len * 2) + (size_t)w * a.tpl_len;  // (Dd, min(Dd, Dn)) per row
-    for (uint32_t r = threadIdx.x; r < M; r += blockDim.x) {  // 24-byte rows + squared norm, as k_spot stages them
-        const uint2 *src = (const uint2 *)(a.tpl + (size_t)k * a.tpl_stride + (size_t)r * kCoef);
-        const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-        Row32 f = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-        sl_smem[2 * r] = u32x4{q0.x, q0.y, q1.x, q1.y};
-        sl_smem[2 * r + 1] = u32x4{q2.x, q2.y, (uint32_t)dot_rows(f, f), 0u};
-    }
+    sweep_stage_tpl(sl_smem, a.tpl + (size_t)k * a.tpl_stride, M);
     __syncthreads();
     if (c >= a.C) return;
     const SpotLiveChan ch = a.chan[c];
@@ -86,12 +81,7 @@ __global__ void __launch_bounds__(64 * kSpotWaves) k_spot_live(const SpotLiveArg
         const bool live = col < cN;
         const uint32_t last = (cN - x0 < 64u ? cN - x0 : 64u) - 1;  // the sweep's last live lane: its column is handed on
         Row32 fi = row_from2(u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, 0u);
-        if (live) {
-            const uint2 *src = (const uint2 *)(in + (size_t)(col - xs) * kCoef);
-            const uint2 q0 = src[0], q1 = src[1], q2 = src[2];
-            fi = row_from2(u32x2{q0.x, q0.y}, u32x2{q1.x, q1.y}, u32x2{q2.x, q2.y}, 0u);
-            fi.w[6] = (uint32_t)dot_rows(fi, fi);
-        }
+        if (live) fi = sweep_frame(in + (size_t)(col - xs) * kCoef);
         uint64_t up_d = kSpotInf, up_m = kSpotInf;  // Dd and min(Dd, Dn) of (col, row - 1): the lane's last results
         uint64_t diag = kSpotInf;                   // min(Dd, Dn) of (col - 1, row - 1): last step's value from the left
         uint64_t end_v = kSpotInf;                  // min(Dd, Dn) of (col, M - 1)
