@@ -1,7 +1,8 @@
 // Full-DP alignment and DBA training (include/sr_engine.h, "full-DP alignment and word models from many examples"): the checks,
 // the launch plan (align_plan, sr_dtw_plan.h) and the sequencing of k_dp_align / k_align_accum / k_align_finalise.  A call is cut
-// into launches of as many pairs as the scratch budget holds; everything stays on the caller's stream.
-#include "sr_host_call.h"
+// into launches of as many pairs as the scratch budget holds; everything stays on the caller's stream.  The host forms stage
+// their rows through sr_stage_host.h.
+#include "sr_stage_host.h"
 
 using namespace sr;
 
@@ -21,12 +22,6 @@ AlignPlan plan_for(uint32_t max_frames, uint32_t ref_rows, const LdsBudget &lds,
     const int64_t pairs = dev_hook(kHookAlignPairs);  // testing build: a few pairs per launch put seams into small test shapes
     return align_plan(max_frames, ref_rows, lds, extra, dev_hook(kHookAlignGlobal) != 0,
                       pairs > 0 ? (uint32_t)std::min<int64_t>(pairs, kAlignMaxPairs) : 0u);
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
 }
 
 int check_align(const sr_engine *h, const AlignIn &in, const void *ref, const void *ref_frames, uint32_t ref_rows, uint32_t n_ref,
@@ -184,14 +179,10 @@ int sr_dtw_dp_align(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames
     TmpDevBuf<int16_t> d_ref;
     TmpDevBuf<uint32_t> d_rf, d_map, d_span;
     TmpDevBuf<sr_align_rec> d_rec;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_ref.reserve(n_refel)) ||
+    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows)) || (rc = d_ref.reserve(n_refel)) ||
         (rc = d_rf.reserve(n_ref)) || (rc = d_rec.reserve(n_rows)) || (ref_of_row && (rc = d_map.reserve(n_rows))) ||
         (span && (rc = d_span.reserve(n_span))))
         return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
     COPY_UP(d_ref.p, ref, n_refel * 2);
     COPY_UP(d_rf.p, ref_frames, (size_t)n_ref * 4);
     if (ref_of_row) COPY_UP(d_map.p, ref_of_row, (size_t)n_rows * 4);
@@ -230,15 +221,9 @@ int sr_train_models_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_fra
     TmpDevBuf<int16_t> d_in, d_out;
     TmpDevBuf<uint32_t> d_cf;
     TmpDevBuf<sr_train_stat> d_st;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(std::max(E, 1u)))) || (rc = h->s_u32a.reserve(std::max(E, 1u))) || (rc = d_in.reserve(n_cen)) ||
-        (rc = d_out.reserve(n_cen)) || (rc = d_cf.reserve(M)) || (stats && (rc = d_st.reserve(n_st))))
+    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, E)) || (rc = d_in.reserve(n_cen)) || (rc = d_out.reserve(n_cen)) ||
+        (rc = d_cf.reserve(M)) || (stats && (rc = d_st.reserve(n_st))))
         return rc;
-    std::vector<uint32_t> frames(E);
-    for (uint32_t r = 0; r < E; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    if (E) {
-        COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(E) * 2);
-        COPY_UP(h->s_u32a.p, frames.data(), (size_t)E * 4);
-    }
     COPY_UP(d_in.p, cen_in, n_cen * 2);
     COPY_UP(d_cf.p, cen_frames, (size_t)M * 4);
     if ((rc = run_train(h, AlignIn{h->s_mfcc.p, h->s_u32a.p, 1, E}, ex_start, M, d_in.p, d_cf.p, cen_rows, n_iter, d_out.p,

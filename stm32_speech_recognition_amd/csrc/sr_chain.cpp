@@ -1,13 +1,10 @@
 // Connected-word decoding (include/sr_engine.h, "connected-word decoding"): the checks, the launch plan (chain_plan,
 // sr_dtw_plan.h) and the slicing of a call into launch groups whose keys and prefix costs fit the engine's scratch.  Per group:
-// k_chain_init, max_words x (k_chain_words, k_chain_close), k_chain_trace, everything on the caller's stream.  The whole-path
-// host form is in sr_host.cpp, next to sr_spot_batch.
-#include "sr_host_call.h"
+// k_chain_init, max_words x (k_chain_words, k_chain_close), k_chain_trace, everything on the caller's stream.  The host form
+// stages its rows and outputs through sr_stage_host.h; the whole-path host form is in sr_host.cpp, next to sr_spot_batch.
+#include "sr_stage_host.h"
 
 using namespace sr;
-
-// the longest template of the store: upload_templates keeps one row of slack behind it
-static inline uint32_t chain_tpl_len(const sr_engine *h) { return h->tpl_rows - 1; }
 
 static ChainPlan plan_for(uint32_t tpl_len, uint32_t max_frames, uint32_t max_words)
 {
@@ -32,20 +29,14 @@ int check_chain(const sr_engine *h, uint32_t max_words, uint32_t n_words_exact, 
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
     if (int rc = check_limits(max_words, n_words_exact, skip_cost, word_cost)) return rc;
     if (h->K > kChainMaxSlots) return fail(SR_ERR_BAD_ARG, "the connected-word decoder takes a store of at most 65536 slots");
-    if (chain_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the connected-word decoder's LDS image");
+    if (store_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the connected-word decoder's LDS image");
     if (h->wg_K != h->K) return fail(SR_ERR_BAD_ARG, "the word map does not fit the template store");
     return SR_OK;
 }
 
-static bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
-static int check_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
-                       uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
-                       const uint32_t *level_cost)
+int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
+                      uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
+                      const uint32_t *level_cost)
 {
     if (!h || !mfcc || !frames || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc = check_chain(h, max_words, n_words_exact, skip_cost, word_cost)) return rc;
@@ -54,13 +45,6 @@ static int check_stage(const sr_engine *h, const void *mfcc, const void *frames,
     if (overlap(rec, n_rec, words, n_w) || overlap(rec, n_rec, level_cost, n_lc) || overlap(words, n_w, level_cost, n_lc))
         return fail(SR_ERR_BAD_ARG, "d_rec, d_words and d_level_cost overlap");
     return SR_OK;
-}
-
-int check_chain_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t max_words,
-                      uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, const sr_chain_rec *rec, const sr_chain_word *words,
-                      const uint32_t *level_cost)
-{
-    return check_stage(h, mfcc, frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
 }
 
 extern "C" {
@@ -82,22 +66,22 @@ int sr_decode_words_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *
                            uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *d_rec,
                            sr_chain_word *d_words, uint32_t *d_level_cost, void *stream)
 {
-    int rc = check_stage(h, d_mfcc, d_in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec, d_words,
-                         d_level_cost);
+    int rc = check_chain_stage(h, d_mfcc, d_in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec, d_words,
+                               d_level_cost);
     if (rc || !n_rows) return rc;
     ENTER_DEVICE(h);
     const hipStream_t s = (hipStream_t)stream;
-    const ChainPlan p = plan_for(chain_tpl_len(h), h->cfg.max_frames, max_words);
+    const ChainPlan p = plan_for(store_tpl_len(h), h->cfg.max_frames, max_words);
     const uint32_t per = std::min(p.rows, n_rows);
     if ((rc = order_after_scratch_users(h, s))) return rc;  // the keys and prefix costs are the engine's
     if ((rc = h->s_ch_a.reserve(per * p.a_row)) || (rc = h->s_ch_e.reserve(per * p.e_row))) return rc;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     for (uint32_t r0 = 0; r0 < n_rows; r0 += per) {  // the groups follow each other on s: one scratch serves them all
         launch_chain(ChainArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                                std::min(per, n_rows - r0), h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,
-                               chain_tpl_len(h), p.g.chunk_cols, p.g.n_chunks, max_words, n_words_exact, skip_cost, word_cost, h->s_ch_a.p,
-                               h->s_ch_e.p, t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0,
-                               d_words + (size_t)r0 * max_words, d_level_cost ? d_level_cost + (size_t)r0 * max_words : nullptr},
+                               store_tpl_len(h), p.g.chunk_cols, p.g.n_chunks, max_words, n_words_exact, skip_cost, word_cost, h->s_ch_a.p,
+                               h->s_ch_e.p, wt.group_of_slot, wt.word_id, d_rec + r0, d_words + (size_t)r0 * max_words,
+                               d_level_cost ? d_level_cost + (size_t)r0 * max_words : nullptr},
                      s);
     }
     HIP_TRY(hipGetLastError());
@@ -108,27 +92,13 @@ int sr_decode_words_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_fra
                        uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec,
                        sr_chain_word *words, uint32_t *level_cost)
 {
-    int rc = check_stage(h, mfcc, in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
+    int rc = check_chain_stage(h, mfcc, in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
     if (rc || !n_rows) return rc;
-    ENTER_HOST_CALL(h);
-    const size_t n_w = (size_t)n_rows * max_words;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    TmpDevBuf<uint32_t> d_lc;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_rec.reserve(n_rows)) ||
-        (rc = d_words.reserve(n_w)) || (level_cost && (rc = d_lc.reserve(n_w))))
-        return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    if ((rc = sr_decode_words_dp_dev(h, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec.p, d_words.p,
-                                     level_cost ? d_lc.p : nullptr, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
-    return SR_OK;
+    return decode_rows_host(h, mfcc, in_frames, frames_stride, n_rows, max_words, rec, words, level_cost,
+                            [&](const int16_t *d_mfcc, const uint32_t *d_frames, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_lc) {
+                                return sr_decode_words_dp_dev(h, d_mfcc, d_frames, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec,
+                                                              d_words, d_lc, nullptr);
+                            });
 }
 
 }  // extern "C"

@@ -2,18 +2,12 @@
 // (sr_cluster_plan.h) and the sequencing -- per iteration k_cluster_score over every (example, model of its word) pair,
 // k_cluster_assign, k_cluster_tally, then the DBA iteration of sr_align.cpp (k_dp_align on the chosen pairs, k_align_accum,
 // k_align_finalise) with the assignment as its example -> model map.  Everything stays on the caller's stream; the host
-// knows every count, nothing is read back.
-#include "sr_host_call.h"
+// knows every count, nothing is read back.  The host forms stage their rows through sr_stage_host.h.
+#include "sr_stage_host.h"
 
 using namespace sr;
 
 namespace {
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
 
 struct Buf {
     const void *p;
@@ -148,20 +142,6 @@ int run_models(sr_engine *h, const AlignIn &in, const uint32_t *word_start, cons
         // unassigned examples, whose map entry names no model, as failures of model 0xFFFFFFFF
         if ((rc = dba_iteration(h, in, map, M, cur, d_cen_frames, cen_rows, next, nullptr, ap, s))) return rc;
         cur = next;
-    }
-    return SR_OK;
-}
-
-// the feature rows of a host-buffer call, into s_mfcc and s_u32a (dense counts)
-int stage_rows(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t E)
-{
-    int rc;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(std::max(E, 1u)))) || (rc = h->s_u32a.reserve(std::max(E, 1u)))) return rc;
-    std::vector<uint32_t> frames(E);
-    for (uint32_t r = 0; r < E; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    if (E) {
-        COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(E) * 2);
-        COPY_UP(h->s_u32a.p, frames.data(), (size_t)E * 4);
     }
     return SR_OK;
 }

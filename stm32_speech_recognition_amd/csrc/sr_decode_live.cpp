@@ -26,7 +26,7 @@ namespace {
 int relayout(sr_decode_live *l)
 {
     const sr_engine *h = l->h;
-    const uint32_t tpl_len = h->tpl_rows - 1;
+    const uint32_t tpl_len = store_tpl_len(h);
     if (int rc = l->cols.reserve((size_t)l->C * l->max_words * h->K * tpl_len)) return rc;
     l->K = h->K;
     l->tpl_len = tpl_len;
@@ -54,10 +54,10 @@ ChainLiveArgs live_args(const sr_decode_live *l, const int16_t *d_mfcc, uint64_t
                         uint32_t *d_level_cost)
 {
     const sr_engine *h = l->h;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     return ChainLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, l->K, h->tpl_stride, l->tpl_len,
                          l->m.utt_frames + 1u, l->max_words, l->n_words_exact, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p,
-                         t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec, d_words, d_level_cost};
+                         wt.group_of_slot, wt.word_id, d_rec, d_words, d_level_cost};
 }
 
 // the levels over the new frames of every channel and the trace of every emitting one, enqueued on s

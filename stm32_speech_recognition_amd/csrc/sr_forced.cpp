@@ -1,9 +1,10 @@
 // Transcript-forced alignment and the span gather (include/sr_engine.h, "forced alignment against a transcript"): the
 // checks and the plan (sr_forced_plan.h: item lists, tail, launch groups -- host-only code), the upload of the plan's tables
 // and the sequencing.  Per launch group: k_chain_init, per level (k_forced_words over the level's items, k_chain_close),
-// k_forced_trace, everything on the caller's stream; the host knows every item and count, nothing is read back.
+// k_forced_trace, everything on the caller's stream; the host knows every item and count, nothing is read back.  The host
+// forms stage their rows (and the aligner's outputs) through sr_stage_host.h.
 #include "sr_forced_plan.h"
-#include "sr_host_call.h"
+#include "sr_stage_host.h"
 
 using namespace sr;
 
@@ -18,7 +19,7 @@ int check_forced(const sr_engine *h, const void *mfcc, const void *frames, uint3
     if (words_per_row < 1 || words_per_row > kForcedMaxWords) return fail(SR_ERR_BAD_ARG, "words_per_row must be 1..16");
     if (int rc = check_chain(h, words_per_row, 0, skip_cost, word_cost)) return rc;  // the decoder's own conditions
     if (!frames_stride) return fail(SR_ERR_BAD_ARG, "frames_stride must be at least 1");
-    if (forced_overlap(rec, (size_t)n_rows * sizeof *rec, words, (size_t)n_rows * words_per_row * sizeof *words))
+    if (overlap(rec, (size_t)n_rows * sizeof *rec, words, (size_t)n_rows * words_per_row * sizeof *words))
         return fail(SR_ERR_BAD_ARG, "d_rec and d_words overlap");
     std::vector<uint32_t> label(h->K);
     for (uint32_t k = 0; k < h->K; k++) label[k] = h->word_explicit ? h->word_labels[k] : k / h->word_spw;
@@ -37,7 +38,7 @@ int run_forced(sr_engine *h, const ForcedStore &store, const int16_t *d_mfcc, co
     // whose sweep this is) put seams and small groups into small test shapes
     const int64_t cc = dev_hook(kHookChainChunk), sc = dev_hook(kHookSpotChunk), rows = dev_hook(kHookChainRows);
     const int64_t cols = cc > 0 ? cc : sc;
-    const uint32_t tpl_len = h->tpl_rows - 1;
+    const uint32_t tpl_len = store_tpl_len(h);
     const ChainPlan p = chain_plan(tpl_len, h->cfg.max_frames, W, cols > 0 ? (uint32_t)std::min<int64_t>(cols, 16383) : 0u,
                                    rows > 0 ? (uint32_t)std::min<int64_t>(rows, kChainMaxRows) : 0u);
     const uint32_t per = std::min(p.rows, n_rows);
@@ -51,12 +52,12 @@ int run_forced(sr_engine *h, const ForcedStore &store, const int16_t *d_mfcc, co
     HIP_TRY(hipMemcpyAsync(h->s_fc_tab.p, fp.tab.data(), fp.items_at() * 4, hipMemcpyHostToDevice, s));
     if (fp.n_items)
         HIP_TRY(hipMemcpyAsync(h->s_fc_tab.p + items_at, fp.tab.data() + fp.items_at(), (size_t)fp.n_items * 8, hipMemcpyHostToDevice, s));
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     for (const ForcedGroup &g : fp.groups) {  // the groups follow each other on s: one scratch serves them all
         ForcedArgs a{};
         a.c = ChainArgs{d_mfcc + (size_t)g.row0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)g.row0 * frames_stride, frames_stride, g.n_rows,
                         h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride, tpl_len, p.g.chunk_cols, p.g.n_chunks, W,
-                        0u, skip_cost, word_cost, h->s_ch_a.p, h->s_ch_e.p, t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1,
+                        0u, skip_cost, word_cost, h->s_ch_a.p, h->s_ch_e.p, wt.group_of_slot, wt.word_id,
                         d_rec + g.row0, d_words + (size_t)g.row0 * W, nullptr};
         a.items = (const uint2 *)(h->s_fc_tab.p + items_at);
         a.tail = h->s_fc_tab.p + (size_t)g.row0 * W;
@@ -79,7 +80,7 @@ int check_gather(const sr_engine *h, const void *mfcc, const void *frames, uint3
     if (ex_rows < 1 || ex_rows > SR_ALIGN_MAX_FRAMES) return fail(SR_ERR_BAD_ARG, "ex_rows must be 1..SR_ALIGN_MAX_FRAMES");
     if ((uint64_t)n_rows * words_per_row >= 0xFFFFFFFFull) return fail(SR_ERR_BAD_ARG, "too many spans");
     if (((uintptr_t)mfcc | (uintptr_t)ex) & 3) return fail(SR_ERR_BAD_ARG, "the feature rows and d_ex must be 4-byte aligned");
-    if (forced_overlap(ex, (size_t)n_ex * ex_rows * kCoef * 2, ex_frames, (size_t)n_ex * 4)) return fail(SR_ERR_BAD_ARG, "d_ex and d_ex_frames overlap");
+    if (overlap(ex, (size_t)n_ex * ex_rows * kCoef * 2, ex_frames, (size_t)n_ex * 4)) return fail(SR_ERR_BAD_ARG, "d_ex and d_ex_frames overlap");
     std::string why;
     if (!forced_gather_table(dst_of_span, (size_t)n_rows * words_per_row, n_ex, src_of_ex, &why)) return fail(SR_ERR_BAD_ARG, why);
     return SR_OK;
@@ -97,20 +98,6 @@ int run_gather(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames,
                         s);
     HIP_TRY(hipGetLastError());
     return mark_scratch_user(h, s);
-}
-
-// the feature rows of a host-buffer call, into s_mfcc and s_u32a (dense counts)
-int stage_rows(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows)
-{
-    int rc;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(std::max(n_rows, 1u)))) || (rc = h->s_u32a.reserve(std::max(n_rows, 1u)))) return rc;
-    std::vector<uint32_t> frames(n_rows);
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    if (n_rows) {
-        COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-        COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    }
-    return SR_OK;
 }
 
 }  // namespace
@@ -137,17 +124,11 @@ int sr_align_transcripts_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *i
     ForcedStore store;
     int rc = check_forced(h, mfcc, in_frames, frames_stride, n_rows, transcript, n_words, words_per_row, skip_cost, word_cost, rec, words, &store);
     if (rc || !n_rows) return rc;
-    ENTER_HOST_CALL(h);
-    const size_t n_w = (size_t)n_rows * words_per_row;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows)) || (rc = d_rec.reserve(n_rows)) || (rc = d_words.reserve(n_w))) return rc;
-    if ((rc = run_forced(h, store, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, transcript, n_words, words_per_row, skip_cost, word_cost, d_rec.p, d_words.p,
-                         nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    return SR_OK;
+    return decode_rows_host(h, mfcc, in_frames, frames_stride, n_rows, words_per_row, rec, words, nullptr,
+                            [&](const int16_t *d_mfcc, const uint32_t *d_frames, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+                                return run_forced(h, store, d_mfcc, d_frames, 1, n_rows, transcript, n_words, words_per_row, skip_cost, word_cost, d_rec,
+                                                  d_words, nullptr);
+                            });
 }
 
 int sr_gather_word_spans_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_in_frames, uint32_t frames_stride, uint32_t n_rows,

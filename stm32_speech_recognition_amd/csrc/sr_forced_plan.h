@@ -12,6 +12,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "sr_overlap.h"  // overlap(): the buffer checks of sr_forced.cpp, exercised by plan_check.cpp with the rest
+
 namespace sr {
 
 constexpr uint32_t kForcedMaxWords = 16;          // words of one transcript at most (= the decoder's levels)
@@ -76,11 +78,8 @@ inline bool forced_check(const ForcedStore &s, const uint32_t *transcript, const
     return true;
 }
 
-inline bool forced_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
+// the buffer checks' overlap test under the name this header has always had for it: the one function of sr_overlap.h
+inline constexpr auto &forced_overlap = overlap;
 
 struct ForcedGroup {
     uint32_t row0, n_rows;

@@ -2,10 +2,10 @@
 // compiled against the engine's store and word map (the construction itself is host-only code, sr_gram_compile.h), the
 // checks, the plan (which items each level keeps, the scratch of a row) and the slicing of a call into launch groups.  Per
 // group: k_gram_init, per level that keeps items (k_gram_charge, k_gram_words, k_gram_close), k_gram_trace, everything on the
-// caller's stream; a grammar with a nonzero cost takes k_gram_charge_w and k_gram_trace_w in their places.  The whole-path
-// host form is in sr_host.cpp, next to sr_decode_words_batch.
+// caller's stream; a grammar with a nonzero cost takes k_gram_charge_w and k_gram_trace_w in their places.  The host form
+// stages its rows and outputs through sr_stage_host.h; the whole-path host form is in sr_host.cpp, next to sr_decode_words_batch.
 #include "sr_gram_compile.h"
-#include "sr_host_call.h"
+#include "sr_stage_host.h"
 #include "sr_onepass_gram_plan.h"
 
 using namespace sr;
@@ -89,7 +89,7 @@ int sr_grammar_create_weighted(sr_engine *h, uint32_t n_states, const sr_gram_ar
     g->n_sets = (uint32_t)c.masks.size();
     g->n_items = (uint32_t)c.items.size();
     g->max_frames = h->cfg.max_frames;
-    g->tpl_len = h->tpl_rows - 1;
+    g->tpl_len = store_tpl_len(h);
     g->weighted = net.weighted;
     std::copy(c.lv, c.lv + kChainMaxWords, g->lv);
 
@@ -185,7 +185,7 @@ int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d
     const uint32_t per = std::min(p.rows, n_rows);
     if ((rc = order_after_scratch_users(h, s))) return rc;  // the keys, prefix costs and charges are the engine's
     if ((rc = h->s_ch_a.reserve(per * p.a_row)) || (rc = h->s_ch_e.reserve(per * (p.e_row + p.c_row)))) return rc;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     GramArgs a{};
     a.n_states = g->n_states;
     a.n_sets = g->n_sets;
@@ -201,7 +201,7 @@ int sr_decode_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const int16_t *d
         a.c = ChainArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                         std::min(per, n_rows - r0), h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,
                         g->tpl_len, p.g.chunk_cols, p.g.n_chunks, max_words, n_words_exact, skip_cost, word_cost, h->s_ch_a.p,
-                        h->s_ch_e.p, t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0,
+                        h->s_ch_e.p, wt.group_of_slot, wt.word_id, d_rec + r0,
                         d_words + (size_t)r0 * max_words, d_level_cost ? d_level_cost + (size_t)r0 * max_words : nullptr};
         launch_gram(a, g->weighted ? &w : nullptr, s);
     }
@@ -215,25 +215,11 @@ int sr_decode_grammar_dp(sr_engine *h, const sr_grammar *g, const int16_t *mfcc,
 {
     int rc = check_chain_stage(h, mfcc, in_frames, frames_stride, n_rows, max_words, n_words_exact, skip_cost, word_cost, rec, words, level_cost);
     if (rc || (rc = check_grammar(h, g)) || !n_rows) return rc;
-    ENTER_HOST_CALL(h);
-    const size_t n_w = (size_t)n_rows * max_words;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    TmpDevBuf<uint32_t> d_lc;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_rec.reserve(n_rows)) ||
-        (rc = d_words.reserve(n_w)) || (level_cost && (rc = d_lc.reserve(n_w))))
-        return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    if ((rc = sr_decode_grammar_dp_dev(h, g, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec.p,
-                                       d_words.p, level_cost ? d_lc.p : nullptr, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
-    return SR_OK;
+    return decode_rows_host(h, mfcc, in_frames, frames_stride, n_rows, max_words, rec, words, level_cost,
+                            [&](const int16_t *d_mfcc, const uint32_t *d_frames, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_lc) {
+                                return sr_decode_grammar_dp_dev(h, g, d_mfcc, d_frames, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec,
+                                                                d_words, d_lc, nullptr);
+                            });
 }
 
 }  // extern "C"

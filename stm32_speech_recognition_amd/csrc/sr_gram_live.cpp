@@ -98,11 +98,11 @@ GramLiveArgs live_args(const sr_gram_live *l, const int16_t *d_mfcc, uint64_t ro
 {
     const sr_engine *h = l->h;
     const sr_grammar *g = l->g;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     GramLiveArgs a{};
     a.c = ChainLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride, l->tpl_len,
                         l->m.utt_frames + 1u, l->max_words, l->n_words_exact, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p,
-                        t ? t + h->K + 2 * (size_t)h->wg_words + 1 : nullptr, t ? t + h->K + h->wg_words + 1 : nullptr, d_rec, d_words,
+                        wt.group_of_slot, wt.word_id, d_rec, d_words,
                         d_level_cost};  // (no grouping: only a dropped recording is traced then, which reads neither)
     a.n_states = g->n_states;
     a.n_items = g->n_items;

@@ -2,8 +2,9 @@
 // the scalar helpers behind the reference-compatible symbols of sr_compat.cpp.  How buffers travel is sr_host_call.h's
 // business (HostCall: the pinned staging area and one synchronisation for small calls, blocking copies otherwise); an entry
 // point here decides the mode once and writes its launch sequence once, on hc.stream().  Only sr_recognize_batch knows a
-// third way up, the chunked upload of large batches overlapped with the kernels.
-#include "sr_host_call.h"
+// third way up, the chunked upload of large batches overlapped with the kernels.  The whole-path forms of the spotter and the
+// decoders share one front and one way down for their outputs (pcm_segments_host / pcm_decode_host, sr_stage_host.h).
+#include "sr_stage_host.h"
 
 using namespace sr;
 
@@ -233,40 +234,7 @@ int sr_vad_debug_masks(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, u
     return SR_OK;
 }
 
-// Per-item failure, as get_mfcc has it (MFCC.C:102-107: a segment shorter than a frame underflows the u32 frame count,
-// which then exceeds vv_frm_max -> frm_num = 0): one bad record yields frm_num[b] = 0, an all-zero MFCC record and
-// status[b] != 0; the other records of the batch are processed.
-// The per-utterance records the frame kernel consumes (what k_vad would have produced) for explicit segments.
-static int mfcc_records(const sr_engine *h, uint32_t buf_len, uint32_t B, const int32_t *start, const int32_t *end,
-                        const uint32_t *mid, uint32_t *frm_num, uint32_t *status, std::vector<sr_vad_rec> &recs)
-{
-    recs.resize(B);
-    for (uint32_t b = 0; b < B; b++) {
-        sr_vad_rec &r = recs[b];
-        std::memset(&r, 0, sizeof r);
-        // samples and mid are 16-bit quantities in the reference (u16 VcBuf, mid_val = a mean of u16 samples,
-        // VAD.C:41-47); the frame kernel's 24-bit multiplies rely on |sample - mid| < 2^23
-        if (mid[b] > 0xFFFFu) return fail(SR_ERR_BAD_ARG, "mid exceeds the u16 sample range");
-        r.atap.mid_val = mid[b];
-        for (int i = 0; i < 2 * SR_MAX_SEG; i++) r.seg[i] = -1;
-        r.seg[0] = start[b];
-        r.seg[1] = end[b];
-        if (start[b] < 1 || end[b] > (int32_t)buf_len || end[b] < start[b]) {
-            r.status = SR_ST_SEG_OOB;  // outside the buffer (start >= 1: MFCC.C:119 reads start[-1])
-        } else {
-            // MFCC.C:102: u32 arithmetic, u16 truncation -- a segment shorter than a frame wraps to a count above the cap
-            const uint32_t n = ((((uint32_t)(end[b] - start[b]) - h->frame_len) / h->hop) + 1) & 0xFFFF;
-            const bool shorter = (uint32_t)(end[b] - start[b]) < h->frame_len;  // the wrapped count may alias a small one
-            r.status = (shorter || n > h->cfg.max_frames) ? SR_ST_MFCC_FAIL : SR_ST_OK;  // MFCC.C:103-107
-            r.frm_num = r.status == SR_ST_OK ? n : 0;
-        }
-        if (r.status != SR_ST_OK) r.seg[0] = 1, r.seg[1] = 1;  // never dereferenced (no frames); keep the record harmless
-        if (frm_num) frm_num[b] = r.frm_num;
-        if (status) status[b] = r.status;
-    }
-    return SR_OK;
-}
-
+// (mfcc_records, the records of explicit segments, is sr_stage_host.h's: the whole-path forms below make them there)
 int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                          const int32_t *start, const int32_t *end, const uint32_t *mid, int16_t *mfcc, uint32_t *frm_num,
                          uint32_t *status)
@@ -291,8 +259,8 @@ int sr_mfcc_batch_status(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride,
     return hc.finish(rc);
 }
 
-// Word spotting, whole path (sr_spot.cpp has the stage): the records and the frame kernel of sr_mfcc_batch_status, then the
-// stage over the feature rows where they are, frame counts straight from the records (a failed one has frm_num 0: no hits)
+// Word spotting, whole path (sr_spot.cpp has the stage): the front of sr_stage_host.h -- the records and the frame kernel of
+// sr_mfcc_batch_status -- then the stage over the feature rows where they are (a failed record has frm_num 0: no hits)
 int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
                   const int32_t *end, const uint32_t *mid, uint32_t win_frames, sr_spot_hit *hits, uint32_t *scores, int16_t *mfcc,
                   uint32_t *frm_num, uint32_t *status)
@@ -300,32 +268,22 @@ int sr_spot_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32
     if (!h || !pcm || !start || !end || !mid || !hits) return fail(SR_ERR_BAD_ARG, "null argument");
     SpotGeom g;
     if (int rc_chk = check_spot(h, B, win_frames, &g)) return rc_chk;
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_HOST_CALL(h);
-    std::vector<sr_vad_rec> recs;
-    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
-    if (rc) return rc;
-    const size_t n_mfcc = h->mfcc_elems(B), n_rec = (size_t)B * g.n_win * h->K;
-    if ((rc = h->s_vad.reserve(B))) return rc;
-    if ((rc = h->s_mfcc.reserve(n_mfcc))) return rc;
-    if ((rc = h->s_spot_hits.reserve(n_rec))) return rc;
-    if (scores && (rc = h->s_spot_scores.reserve(n_rec))) return rc;
-    uint64_t ds = 0;
-    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
-    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
-    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
-    if ((rc = launch_spot_stage(h, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, g, h->s_spot_hits.p,
-                                scores ? h->s_spot_scores.p : nullptr, nullptr)))
-        return rc;
-    COPY_DOWN(hits, h->s_spot_hits.p, n_rec * sizeof(sr_spot_hit));
-    if (scores) COPY_DOWN(scores, h->s_spot_scores.p, n_rec * 4);
-    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
-    return SR_OK;
+    return pcm_segments_host(h, PcmSegments{pcm, pcm_stride, buf_len, B, start, end, mid, mfcc, frm_num, status},
+                             [&](const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t frames_stride) -> int {
+                                 const size_t n_rec = (size_t)B * g.n_win * h->K;
+                                 int rc;
+                                 if ((rc = h->s_spot_hits.reserve(n_rec)) || (scores && (rc = h->s_spot_scores.reserve(n_rec)))) return rc;
+                                 if ((rc = launch_spot_stage(h, d_mfcc, d_frames, frames_stride, B, g, h->s_spot_hits.p,
+                                                             scores ? h->s_spot_scores.p : nullptr, nullptr)))
+                                     return rc;
+                                 COPY_DOWN(hits, h->s_spot_hits.p, n_rec * sizeof(sr_spot_hit));
+                                 if (scores) COPY_DOWN(scores, h->s_spot_scores.p, n_rec * 4);
+                                 return SR_OK;
+                             });
 }
 
-// Connected-word decoding, whole path (sr_chain.cpp has the stage): as sr_spot_batch, the records and the frame kernel of
-// sr_mfcc_batch_status, then the stage over the feature rows where they are (a failed record has frm_num 0: no parse)
+// Connected-word decoding, whole path (sr_chain.cpp has the stage): the same front, then the public stage into per-call copies
+// of the outputs (a failed record has frm_num 0: no parse)
 int sr_decode_words_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
                           const int32_t *end, const uint32_t *mid, uint32_t max_words, uint32_t n_words_exact, uint32_t skip_cost,
                           uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words, uint32_t *level_cost, int16_t *mfcc,
@@ -333,62 +291,24 @@ int sr_decode_words_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride
 {
     if (!h || !pcm || !start || !end || !mid || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc_chk = check_chain(h, max_words, n_words_exact, skip_cost, word_cost)) return rc_chk;
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_HOST_CALL(h);
-    std::vector<sr_vad_rec> recs;
-    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
-    if (rc) return rc;
-    const size_t n_mfcc = h->mfcc_elems(B), n_w = (size_t)B * max_words;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    TmpDevBuf<uint32_t> d_lc;
-    if ((rc = h->s_vad.reserve(B)) || (rc = h->s_mfcc.reserve(n_mfcc)) || (rc = d_rec.reserve(B)) || (rc = d_words.reserve(n_w)) ||
-        (level_cost && (rc = d_lc.reserve(n_w))))
-        return rc;
-    uint64_t ds = 0;
-    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
-    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
-    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
-    if ((rc = sr_decode_words_dp_dev(h, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, max_words, n_words_exact,
-                                     skip_cost, word_cost, d_rec.p, d_words.p, level_cost ? d_lc.p : nullptr, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)B * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
-    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
-    return SR_OK;
+    return pcm_decode_host(h, PcmSegments{pcm, pcm_stride, buf_len, B, start, end, mid, mfcc, frm_num, status}, max_words, rec, words, level_cost,
+                           [&](const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t fs, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_lc) {
+                               return sr_decode_words_dp_dev(h, d_mfcc, d_frames, fs, B, max_words, n_words_exact, skip_cost, word_cost, d_rec, d_words,
+                                                             d_lc, nullptr);
+                           });
 }
 
-// One-pass connected-word decoding, whole path (sr_onepass.cpp has the stage): the same front, then the stage with frames_cap =
-// max_frames
+// One-pass connected-word decoding, whole path (sr_onepass.cpp has the stage): the same, the stage with frames_cap = max_frames
 int sr_decode_onepass_batch(sr_engine *h, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B, const int32_t *start,
                             const int32_t *end, const uint32_t *mid, uint32_t words_cap, uint32_t skip_cost, uint32_t word_cost,
                             sr_chain_rec *rec, sr_chain_word *words, int16_t *mfcc, uint32_t *frm_num, uint32_t *status)
 {
     if (!h || !pcm || !start || !end || !mid || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc_chk = check_onepass(h, 0u, words_cap, skip_cost, word_cost)) return rc_chk;
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_HOST_CALL(h);
-    std::vector<sr_vad_rec> recs;
-    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
-    if (rc) return rc;
-    const size_t n_mfcc = h->mfcc_elems(B), n_w = (size_t)B * words_cap;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    if ((rc = h->s_vad.reserve(B)) || (rc = h->s_mfcc.reserve(n_mfcc)) || (rc = d_rec.reserve(B)) || (rc = d_words.reserve(n_w))) return rc;
-    uint64_t ds = 0;
-    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
-    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
-    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
-    if ((rc = sr_decode_onepass_dp_dev(h, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, 0u, words_cap, skip_cost,
-                                       word_cost, d_rec.p, d_words.p, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)B * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
-    return SR_OK;
+    return pcm_decode_host(h, PcmSegments{pcm, pcm_stride, buf_len, B, start, end, mid, mfcc, frm_num, status}, words_cap, rec, words, nullptr,
+                           [&](const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t fs, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+                               return sr_decode_onepass_dp_dev(h, d_mfcc, d_frames, fs, B, 0u, words_cap, skip_cost, word_cost, d_rec, d_words, nullptr);
+                           });
 }
 
 // One-pass grammar decoding, whole path (sr_onepass_gram.cpp has the stage): sr_decode_onepass_batch under a grammar
@@ -398,30 +318,14 @@ int sr_decode_onepass_grammar_batch(sr_engine *h, const sr_grammar *g, const uin
 {
     if (!h || !pcm || !start || !end || !mid || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc_chk = check_onepass_grammar(h, g, 0u, words_cap, skip_cost, word_cost)) return rc_chk;
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_HOST_CALL(h);
-    std::vector<sr_vad_rec> recs;
-    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
-    if (rc) return rc;
-    const size_t n_mfcc = h->mfcc_elems(B), n_w = (size_t)B * words_cap;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    if ((rc = h->s_vad.reserve(B)) || (rc = h->s_mfcc.reserve(n_mfcc)) || (rc = d_rec.reserve(B)) || (rc = d_words.reserve(n_w))) return rc;
-    uint64_t ds = 0;
-    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
-    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
-    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
-    if ((rc = sr_decode_onepass_grammar_dp_dev(h, g, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, 0u, words_cap,
-                                               skip_cost, word_cost, d_rec.p, d_words.p, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)B * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
-    return SR_OK;
+    return pcm_decode_host(h, PcmSegments{pcm, pcm_stride, buf_len, B, start, end, mid, mfcc, frm_num, status}, words_cap, rec, words, nullptr,
+                           [&](const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t fs, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+                               return sr_decode_onepass_grammar_dp_dev(h, g, d_mfcc, d_frames, fs, B, 0u, words_cap, skip_cost, word_cost, d_rec, d_words,
+                                                                       nullptr);
+                           });
 }
 
-// the same under a grammar (sr_gram.cpp has the stage)
+// sr_decode_words_batch under a grammar (sr_gram.cpp has the stage)
 int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len,
                             uint32_t B, const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t max_words,
                             uint32_t n_words_exact, uint32_t skip_cost, uint32_t word_cost, sr_chain_rec *rec, sr_chain_word *words,
@@ -430,35 +334,16 @@ int sr_decode_grammar_batch(sr_engine *h, const sr_grammar *g, const uint16_t *p
     if (!h || !pcm || !start || !end || !mid || !rec || !words) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc_chk = check_chain(h, max_words, n_words_exact, skip_cost, word_cost)) return rc_chk;
     if (int rc_chk = check_grammar(h, g)) return rc_chk;
-    if (B == 0) return SR_OK;
-    if (buf_len > pcm_stride) return fail(SR_ERR_BAD_ARG, "buf_len exceeds pcm_stride");
-    ENTER_HOST_CALL(h);
-    std::vector<sr_vad_rec> recs;
-    int rc = mfcc_records(h, buf_len, B, start, end, mid, frm_num, status, recs);
-    if (rc) return rc;
-    const size_t n_mfcc = h->mfcc_elems(B), n_w = (size_t)B * max_words;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    TmpDevBuf<uint32_t> d_lc;
-    if ((rc = h->s_vad.reserve(B)) || (rc = h->s_mfcc.reserve(n_mfcc)) || (rc = d_rec.reserve(B)) || (rc = d_words.reserve(n_w)) ||
-        (level_cost && (rc = d_lc.reserve(n_w))))
-        return rc;
-    uint64_t ds = 0;
-    if ((rc = stage_pcm(h, pcm, pcm_stride, buf_len, B, &ds))) return rc;
-    COPY_UP(h->s_vad.p, recs.data(), (size_t)B * sizeof(sr_vad_rec));
-    if ((rc = sr_mfcc_batch_dev(h, h->s_pcm.p, ds, B, h->s_vad.p, h->s_mfcc.p, nullptr))) return rc;
-    if ((rc = sr_decode_grammar_dp_dev(h, g, h->s_mfcc.p, &h->s_vad.p[0].frm_num, (uint32_t)(sizeof(sr_vad_rec) / 4), B, max_words, n_words_exact,
-                                     skip_cost, word_cost, d_rec.p, d_words.p, level_cost ? d_lc.p : nullptr, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)B * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
-    if (mfcc) COPY_DOWN(mfcc, h->s_mfcc.p, n_mfcc * 2);
-    return SR_OK;
+    return pcm_decode_host(h, PcmSegments{pcm, pcm_stride, buf_len, B, start, end, mid, mfcc, frm_num, status}, max_words, rec, words, level_cost,
+                           [&](const int16_t *d_mfcc, const uint32_t *d_frames, uint32_t fs, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *d_lc) {
+                               return sr_decode_grammar_dp_dev(h, g, d_mfcc, d_frames, fs, B, max_words, n_words_exact, skip_cost, word_cost, d_rec,
+                                                               d_words, d_lc, nullptr);
+                           });
 }
 
 // the frame kernels' per-frame intermediate values for explicit segments: the records of sr_mfcc_batch_status, staged like
 // its large-batch path
+// (not pcm_segments_host: the stage here IS the frame kernel -- it reads the capture rows and the records, no feature rows)
 int sr_frame_features_batch(sr_engine *h, int kind, const uint16_t *pcm, uint64_t pcm_stride, uint32_t buf_len, uint32_t B,
                             const int32_t *start, const int32_t *end, const uint32_t *mid, uint32_t *feat, int16_t *mfcc,
                             uint32_t *frm_num, uint32_t *status)

@@ -1,13 +1,14 @@
 // What the live sessions (sr_spot_live.cpp, sr_decode_live.cpp, sr_gram_live.cpp, sr_onepass_live.cpp, sr_onepass_gram_live.cpp)
 // do alike on the host: the session core -- engine, channel plan, the PCM front end's buffers, the event that orders pushes on different streams --
 // with its open and release; the checks of a push's input; ONE push sequence for frames or samples, on the device or from
-// host buffers; and for the four decoders the output checks, the host forms' device copies of their outputs, the choice
-// between the device and the host form of a push and the sequence of an end call.  A session supplies its plan, its launch and its advance; nothing here knows a session type.
+// host buffers; and for the four decoders the output checks, the choice between the device and the host form of a push and
+// the sequence of an end call (the host forms' device copies of their outputs, HostOutputs, are the batch decoders' too:
+// sr_stage_host.h).  A session supplies its plan, its launch and its advance; nothing here knows a session type.
 // HOST ONLY.
 #pragma once
 #include "sr_decode_live_plan.h"
-#include "sr_host_call.h"
 #include "sr_live_pcm.h"
+#include "sr_stage_host.h"
 
 namespace sr {
 
@@ -188,12 +189,6 @@ int live_push_host(LiveCore &k, const LivePlan &pl, bool work, const LiveIn &in,
 }
 
 // ---- the decoders' outputs: a record, max_words word rows and (level sessions) max_words level costs per row ----------------
-inline bool live_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
-
 // store(): what the trace will read of the engine -- its store, its word map -- is fit for it (check_chain, where the session
 // has not lost its recordings anyway)
 template <typename Store>
@@ -206,7 +201,7 @@ int check_outputs(uint32_t max_words, uint32_t n_out, uint32_t max_rows, const s
     if (int rc = store()) return rc;
     if (!rec || !words || !rows) return fail(SR_ERR_BAD_ARG, "null argument");
     const size_t n_rec = (size_t)n_out * sizeof *rec, n_w = (size_t)n_out * max_words * sizeof *words, n_lc = (size_t)n_out * max_words * 4;
-    if (live_overlap(rec, n_rec, words, n_w) || live_overlap(rec, n_rec, level_cost, n_lc) || live_overlap(words, n_w, level_cost, n_lc))
+    if (overlap(rec, n_rec, words, n_w) || overlap(rec, n_rec, level_cost, n_lc) || overlap(words, n_w, level_cost, n_lc))
         return fail(SR_ERR_BAD_ARG, "rec, words and level_cost overlap");
     return SR_OK;
 }
@@ -216,40 +211,11 @@ inline int check_end_rows(uint32_t max_words, uint32_t n_out, const sr_chain_rec
                           const sr_chain_live_row *rows)
 {
     const size_t n_r = (size_t)n_out * sizeof *rows, n_w = (size_t)n_out * max_words;
-    if (live_overlap(rows, n_r, rec, (size_t)n_out * sizeof *rec) || live_overlap(rows, n_r, words, n_w * sizeof *words) ||
-        live_overlap(rows, n_r, level_cost, n_w * 4))
+    if (overlap(rows, n_r, rec, (size_t)n_out * sizeof *rec) || overlap(rows, n_r, words, n_w * sizeof *words) ||
+        overlap(rows, n_r, level_cost, n_w * 4))
         return fail(SR_ERR_BAD_ARG, "rows overlaps rec, words or level_cost");
     return SR_OK;
 }
-
-// host forms: per-call device copies of the outputs of n_out rows (lc only where the caller wants level costs), and their
-// way back to the caller's buffers
-struct HostOutputs {
-    const uint32_t n_out, max_words;
-    sr_chain_rec *const h_rec;
-    sr_chain_word *const h_words;
-    uint32_t *const h_lc;
-    TmpDevBuf<sr_chain_rec> rec;
-    TmpDevBuf<sr_chain_word> words;
-    TmpDevBuf<uint32_t> lc;
-    HostOutputs(uint32_t n, uint32_t mw, sr_chain_rec *r, sr_chain_word *w, uint32_t *l) : n_out(n), max_words(mw), h_rec(r), h_words(w), h_lc(l) {}
-    int reserve()
-    {
-        const size_t n_w = (size_t)std::max(n_out, 1u) * max_words;
-        if (int rc = rec.reserve(std::max(n_out, 1u))) return rc;
-        if (int rc = words.reserve(n_w)) return rc;
-        return h_lc ? lc.reserve(n_w) : SR_OK;
-    }
-    int down()
-    {
-        if (!n_out) return SR_OK;
-        const size_t n_w = (size_t)n_out * max_words;
-        COPY_DOWN(h_rec, rec.p, (size_t)n_out * sizeof *h_rec);
-        COPY_DOWN(h_words, words.p, n_w * sizeof *h_words);
-        if (h_lc) COPY_DOWN(h_lc, lc.p, n_w * 4);
-        return SR_OK;
-    }
-};
 
 // A push of a decoder in any of its four forms, after the session has planned it and checked its inputs and outputs: a push
 // enqueues work when a channel emits a row.  launch(features, row stride, rec, words, level_cost, s) is the session's launch

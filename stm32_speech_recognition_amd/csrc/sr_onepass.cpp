@@ -1,14 +1,11 @@
 // One-pass connected-word decoding (include/sr_engine.h, "one-pass connected-word decoding"): the checks, the plan
 // (sr_onepass_plan.h: the block length from the host mirror of the store's template lengths, the blocks, the launch groups --
 // host-only code) and the sequencing.  Per launch group: k_onepass_init, per block (k_onepass_words, k_onepass_close),
-// k_onepass_trace, everything on the caller's stream; frames_cap fixes the blocks, nothing is read back.  The whole-path host
-// form is in sr_host.cpp, next to sr_decode_words_batch.
-#include "sr_host_call.h"
+// k_onepass_trace, everything on the caller's stream; frames_cap fixes the blocks, nothing is read back.  The host form stages
+// its rows and outputs through sr_stage_host.h; the whole-path host form is in sr_host.cpp, next to sr_decode_words_batch.
+#include "sr_stage_host.h"
 
 using namespace sr;
-
-// the longest template of the store: upload_templates keeps one row of slack behind it
-static inline uint32_t onepass_tpl_len(const sr_engine *h) { return h->tpl_rows - 1; }
 
 static OnePassPlan plan_for(uint32_t tpl_len, uint32_t K, uint32_t max_frames, uint32_t frames_cap, uint32_t L)
 {
@@ -26,12 +23,6 @@ int check_onepass(const sr_engine *h, uint32_t frames_cap, uint32_t words_cap, u
     if (!onepass_cost_ok(cap, onepass_reach(h->tpl_len_host.data(), h->K), word_cost))
         return fail(SR_ERR_BAD_ARG, "(frames_cap / L) * word_cost must be at most 2^30, L = the shortest valid template's frames / 2 + 1");
     return SR_OK;
-}
-
-static bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
 }
 
 static int check_stage(const sr_engine *h, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows, uint32_t frames_cap,
@@ -68,17 +59,17 @@ int sr_decode_onepass_dp_dev(sr_engine *h, const int16_t *d_mfcc, const uint32_t
     if (rc || !n_rows) return rc;
     ENTER_DEVICE(h);
     const hipStream_t s = (hipStream_t)stream;
-    const uint32_t tpl_len = onepass_tpl_len(h);
+    const uint32_t tpl_len = store_tpl_len(h);
     const OnePassPlan p = plan_for(tpl_len, h->K, h->cfg.max_frames, frames_cap, onepass_reach(h->tpl_len_host.data(), h->K));
     const uint32_t per = std::min(p.rows, n_rows);
     if ((rc = order_after_scratch_users(h, s))) return rc;  // the keys, the prefix costs and the saved columns are the engine's
     if ((rc = h->s_ch_a.reserve(per * p.a_row)) || (rc = h->s_ch_e.reserve(per * p.e_row)) || (rc = h->s_op_cols.reserve(per * p.col_row))) return rc;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     for (uint32_t r0 = 0; r0 < n_rows; r0 += per) {  // the groups follow each other on s: one scratch serves them all
         launch_onepass(OnePassArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                                    std::min(per, n_rows - r0), h->cfg.max_frames, p.cap, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K,
                                    h->tpl_stride, tpl_len, words_cap, skip_cost, word_cost, h->s_ch_a.p, h->s_ch_e.p, h->s_op_cols.p,
-                                   t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0,
+                                   wt.group_of_slot, wt.word_id, d_rec + r0,
                                    d_words + (size_t)r0 * words_cap},
                        p.blocks.data(), (uint32_t)p.blocks.size(), s);
     }
@@ -91,23 +82,11 @@ int sr_decode_onepass_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_f
 {
     int rc = check_stage(h, mfcc, in_frames, frames_stride, n_rows, frames_cap, words_cap, skip_cost, word_cost, rec, words);
     if (rc || !n_rows) return rc;
-    ENTER_HOST_CALL(h);
-    const size_t n_w = (size_t)n_rows * words_cap;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_rec.reserve(n_rows)) ||
-        (rc = d_words.reserve(n_w)))
-        return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    if ((rc = sr_decode_onepass_dp_dev(h, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, frames_cap, words_cap, skip_cost, word_cost, d_rec.p, d_words.p,
-                                       nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    return SR_OK;
+    return decode_rows_host(h, mfcc, in_frames, frames_stride, n_rows, words_cap, rec, words, nullptr,
+                            [&](const int16_t *d_mfcc, const uint32_t *d_frames, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+                                return sr_decode_onepass_dp_dev(h, d_mfcc, d_frames, 1, n_rows, frames_cap, words_cap, skip_cost, word_cost, d_rec, d_words,
+                                                                nullptr);
+                            });
 }
 
 }  // extern "C"

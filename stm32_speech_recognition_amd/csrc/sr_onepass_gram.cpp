@@ -3,8 +3,9 @@
 // launch groups are the one-pass decoder's -- host-only code) and the sequencing.  Per launch group: k_onepass_gram_init, per
 // block (k_onepass_gram_words, k_onepass_gram_close), k_onepass_gram_trace, everything on the caller's stream; a grammar with
 // a nonzero cost takes k_onepass_gram_words_w and k_onepass_gram_trace_w in their places.  frames_cap fixes the blocks,
-// nothing is read back.  The whole-path host form is in sr_host.cpp, next to sr_decode_onepass_batch.
-#include "sr_host_call.h"
+// nothing is read back.  The host form stages its rows and outputs through sr_stage_host.h; the whole-path host form is in
+// sr_host.cpp, next to sr_decode_onepass_batch.
+#include "sr_stage_host.h"
 #include "sr_onepass_gram_plan.h"
 
 using namespace sr;
@@ -31,12 +32,6 @@ OnePassGramPlan plan_for(const sr_grammar *g, const Kept &k, uint32_t frames_cap
     return onepass_gram_plan(g->tpl_len, g->n_states, k.items, k.states, g->max_frames, frames_cap, onepass_reach(h->tpl_len_host.data(), h->K),
                              block > 0 ? (uint32_t)std::min<int64_t>(block, 16383) : 0u,
                              rows > 0 ? (uint32_t)std::min<int64_t>(rows, kOnePassMaxRows) : 0u);
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
 }
 
 int check_stage(const sr_engine *h, const sr_grammar *g, const void *mfcc, const void *frames, uint32_t frames_stride, uint32_t n_rows,
@@ -99,7 +94,7 @@ int sr_decode_onepass_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const in
     if ((rc = h->s_ch_a.reserve(per * p.a_row)) || (rc = h->s_ch_e.reserve(per * p.e_row)) ||
         (rc = h->s_op_cols.reserve(std::max<size_t>(per * p.col_row, 1))))
         return rc;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     OnePassGramArgs a{};
     a.n_states = g->n_states;
     a.n_items = g->n_items;
@@ -115,7 +110,7 @@ int sr_decode_onepass_grammar_dp_dev(sr_engine *h, const sr_grammar *g, const in
         a.o = OnePassArgs{d_mfcc + (size_t)r0 * h->cfg.max_frames * kCoef, d_in_frames + (size_t)r0 * frames_stride, frames_stride,
                           std::min(per, n_rows - r0), h->cfg.max_frames, p.o.cap, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K,
                           h->tpl_stride, g->tpl_len, words_cap, skip_cost, word_cost, h->s_ch_a.p, h->s_ch_e.p, h->s_op_cols.p,
-                          t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec + r0, d_words + (size_t)r0 * words_cap};
+                          wt.group_of_slot, wt.word_id, d_rec + r0, d_words + (size_t)r0 * words_cap};
         launch_onepass_gram(a, g->weighted ? &w : nullptr, p.o.blocks.data(), (uint32_t)p.o.blocks.size(), s);
     }
     HIP_TRY(hipGetLastError());
@@ -128,23 +123,11 @@ int sr_decode_onepass_grammar_dp(sr_engine *h, const sr_grammar *g, const int16_
 {
     int rc = check_stage(h, g, mfcc, in_frames, frames_stride, n_rows, frames_cap, words_cap, skip_cost, word_cost, rec, words);
     if (rc || !n_rows) return rc;
-    ENTER_HOST_CALL(h);
-    const size_t n_w = (size_t)n_rows * words_cap;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows)) || (rc = d_rec.reserve(n_rows)) ||
-        (rc = d_words.reserve(n_w)))
-        return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    if ((rc = sr_decode_onepass_grammar_dp_dev(h, g, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, frames_cap, words_cap, skip_cost, word_cost, d_rec.p,
-                                               d_words.p, nullptr)))
-        return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    return SR_OK;
+    return decode_rows_host(h, mfcc, in_frames, frames_stride, n_rows, words_cap, rec, words, nullptr,
+                            [&](const int16_t *d_mfcc, const uint32_t *d_frames, sr_chain_rec *d_rec, sr_chain_word *d_words, uint32_t *) {
+                                return sr_decode_onepass_grammar_dp_dev(h, g, d_mfcc, d_frames, 1, n_rows, frames_cap, words_cap, skip_cost, word_cost,
+                                                                        d_rec, d_words, nullptr);
+                            });
 }
 
 }  // extern "C"

@@ -92,11 +92,11 @@ OnePassGramLiveArgs live_args(const sr_onepass_gram_live *l, const int16_t *d_mf
 {
     const sr_engine *h = l->h;
     const sr_grammar *g = l->g;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     OnePassGramLiveArgs a{};
     a.o = OnePassLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride, l->tpl_len,
                           l->om.d.utt_frames + 1u, block, l->words_cap, l->tail, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p, l->hist.p,
-                          t ? t + h->K + 2 * (size_t)h->wg_words + 1 : nullptr, t ? t + h->K + h->wg_words + 1 : nullptr, d_rec,
+                          wt.group_of_slot, wt.word_id, d_rec,
                           d_words};  // (no grouping: only a dropped recording is traced then, which reads neither)
     a.n_states = l->S;
     a.n_items = g->n_items;
@@ -211,8 +211,8 @@ int plan_commit(const sr_onepass_gram_live *l, const uint32_t *channels, uint32_
     if (!crec || !cwords || !rows) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc = check_store(l)) return rc;
     const size_t n_c = n_out * sizeof *crec, n_w = n_out * l->words_cap * sizeof *cwords, n_r = n_out * sizeof *rows;
-    if (live_overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
-    if (host && (live_overlap(rows, n_r, crec, n_c) || live_overlap(rows, n_r, cwords, n_w)))
+    if (overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
+    if (host && (overlap(rows, n_r, crec, n_c) || overlap(rows, n_r, cwords, n_w)))
         return fail(SR_ERR_BAD_ARG, "rows overlaps crec or cwords");
     return SR_OK;
 }

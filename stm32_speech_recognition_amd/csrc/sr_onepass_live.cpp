@@ -42,7 +42,7 @@ int check_store(const sr_onepass_live *l) { return check_chain(l->h, 1, 0, l->sk
 int relayout(sr_onepass_live *l)
 {
     const sr_engine *h = l->h;
-    const uint32_t tpl_len = h->tpl_rows - 1;
+    const uint32_t tpl_len = store_tpl_len(h);
     if (int rc = l->cols.reserve((size_t)l->C * h->K * tpl_len)) return rc;
     l->K = h->K;
     l->tpl_len = tpl_len;
@@ -71,10 +71,10 @@ OnePassLiveArgs live_args(const sr_onepass_live *l, const int16_t *d_mfcc, uint6
                           sr_chain_word *d_words)
 {
     const sr_engine *h = l->h;
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     return OnePassLiveArgs{d_mfcc, row_stride, l->d_chan.p, l->C, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, l->K, h->tpl_stride, l->tpl_len,
                            l->om.d.utt_frames + 1u, block, l->words_cap, l->tail, l->skip_cost, l->word_cost, l->cols.p, l->A.p, l->E.p, l->hist.p,
-                           t + h->K + 2 * (size_t)h->wg_words + 1, t + h->K + h->wg_words + 1, d_rec, d_words};
+                           wt.group_of_slot, wt.word_id, d_rec, d_words};
 }
 
 // the blocks over the new frames of every channel and the trace of every emitting one, enqueued on s (PCM: samples, but no
@@ -118,8 +118,8 @@ int plan_commit(const sr_onepass_live *l, const uint32_t *channels, uint32_t n_c
     if (!crec || !cwords || !rows) return fail(SR_ERR_BAD_ARG, "null argument");
     if (int rc = check_store(l)) return rc;
     const size_t n_c = n_out * sizeof *crec, n_w = n_out * l->words_cap * sizeof *cwords, n_r = n_out * sizeof *rows;
-    if (live_overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
-    if (host && (live_overlap(rows, n_r, crec, n_c) || live_overlap(rows, n_r, cwords, n_w)))
+    if (overlap(crec, n_c, cwords, n_w)) return fail(SR_ERR_BAD_ARG, "crec and cwords overlap");
+    if (host && (overlap(rows, n_r, crec, n_c) || overlap(rows, n_r, cwords, n_w)))
         return fail(SR_ERR_BAD_ARG, "rows overlaps crec or cwords");
     return SR_OK;
 }
@@ -131,11 +131,11 @@ int enqueue_commit(sr_onepass_live *l, const std::vector<sr_chain_live_row> &ord
     if (int rc = l->order_after_last_push(s)) return rc;
     // (a pageable source is staged before the call returns: the list may go out of scope)
     HIP_TRY(hipMemcpyAsync(l->commit_rows.p, order.data(), order.size() * sizeof(sr_chain_live_row), hipMemcpyHostToDevice, s));
-    const uint32_t *t = h->wg_tab.p;  // order[K] | group_start[n_words + 1] | word_id[n_words] | group_of_slot[K]
+    const WordTab wt = word_tab(h);
     launch_onepass_live_commit(
         OnePassCommitArgs{l->commit_rows.p, (uint32_t)order.size(), l->om.d.utt_frames + 1u, onepass_commit_window(h->tpl_len_host.data(), h->K),
-                          l->words_cap, l->word_cost, l->A.p, l->E.p, l->cursor.p, h->tpl_frames.p, t + h->K + 2 * (size_t)h->wg_words + 1,
-                          t + h->K + h->wg_words + 1, d_crec, d_cwords},
+                          l->words_cap, l->word_cost, l->A.p, l->E.p, l->cursor.p, h->tpl_frames.p, wt.group_of_slot,
+                          wt.word_id, d_crec, d_cwords},
         s);
     HIP_TRY(hipGetLastError());
     return l->mark_push(s);

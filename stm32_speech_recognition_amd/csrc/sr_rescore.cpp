@@ -1,8 +1,9 @@
 // Two-pass recognition (include/sr_engine.h, "second pass"): the N-best words of a first pass rescored with the full-DP
 // scorer and ranked again, on the device.  Three launches per rescoring behind two fills: k_rescore_mark (the pair set),
 // the sparse form of the full-DP kernels (k_dtw_dp.hip: those pairs only), k_nbest over the second-pass score rows.  The
-// whole-path device form runs the same sequence per chunk from sr_launch.cpp, the whole-path host form is in sr_host.cpp.
-#include "sr_host_call.h"
+// whole-path device form runs the same sequence per chunk from sr_launch.cpp, the whole-path host form is in sr_host.cpp; the
+// host form here stages its rows through sr_stage_host.h.
+#include "sr_stage_host.h"
 
 using namespace sr;
 
@@ -30,8 +31,8 @@ int launch_rescore(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_frames
     // no pair marked, every second-pass score dis_err (0xFF bytes): what the sparse scorer does not reach stays that way
     HIP_TRY(hipMemsetAsync(marks, 0, (size_t)K * stride, s));
     HIP_TRY(hipMemsetAsync(scores, 0xFF, (size_t)n * K * 4, s));
-    const uint32_t *t = h->wg_tab.p, *group_of = t + K + 2 * (size_t)h->wg_words + 1;
-    launch_rescore_mark(RescoreMarkArgs{in + row0 * n_best, n, n_best, K, t, t + K, group_of, h->tpl_rank.p, marks, stride}, s);
+    const WordTab wt = word_tab(h);
+    launch_rescore_mark(RescoreMarkArgs{in + row0 * n_best, n, n_best, K, wt.order, wt.group_start, wt.group_of_slot, h->tpl_rank.p, marks, stride}, s);
     DtwArgs a = dtw_args(h, d_mfcc + h->mfcc_elems(row0), nullptr, d_frames + row0 * frames_stride, n, scores, nullptr);
     if (!h->tpl_staged_ok) a.tplR = nullptr;  // as sr_dtw_dp_batch_dev: such a store takes the generic kernel
     launch_dtw_dp_sparse(a, marks, stride, frames_stride, h->tpl_rank.p, h->dp_lanes, h->lds, s);
@@ -75,16 +76,11 @@ int sr_rescore_nbest_dp(sr_engine *h, const int16_t *mfcc, const uint32_t *in_fr
     int rc = check_stage(h, mfcc, in_frames, frames_stride, n_rows, n_best, nbest_in, nbest_out);
     if (rc || !n_rows) return rc;
     ENTER_HOST_CALL(h);
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows)))) return rc;
-    if ((rc = h->s_u32a.reserve(n_rows))) return rc;
+    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows))) return rc;
     if ((rc = h->s_nbest.reserve((size_t)n_rows * n_best))) return rc;
     if ((rc = h->s_rs_out.reserve((size_t)n_rows * n_best))) return rc;
     if ((rc = h->s_rs_n.reserve(n_rows))) return rc;
     if ((rc = reserve_rescore(h, 1, n_rows, n_rows))) return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
     COPY_UP(h->s_nbest.p, nbest_in, (size_t)n_rows * n_best * sizeof(sr_nbest_entry));
     if ((rc = launch_rescore(h, h->s_mfcc.p, h->s_u32a.p, 1, n_best, h->s_nbest.p, RescoreOut{h->s_rs_out.p, h->s_rs_n.p}, 0, n_rows, 0, n_rows,
                              nullptr)))

@@ -1,18 +1,12 @@
 // Word alternatives (include/sr_engine.h, "word alternatives"): the checks and the launches of the span scorer (k_span.hip),
 // and the unconstrained decoder with alternatives -- sr_decode_words_dp_dev as it stands, k_span_words over its word rows,
 // sr_nbest_batch_dev's reduction over the span score rows -- everything on the caller's stream.  The host knows every count:
-// nothing is read back.
-#include "sr_host_call.h"
+// nothing is read back.  The host forms stage their rows (and the decoder's outputs) through sr_stage_host.h.
+#include "sr_stage_host.h"
 
 using namespace sr;
 
 static constexpr uint32_t kSpanMaxSpans = 0x7FFFFFFFu;
-
-static bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && na && nb && x < y + nb && y < x + na;
-}
 
 // the conditions of sr_score_word_spans_dev on the engine, the store and the parameters (not on the buffers)
 static int check_span(const sr_engine *h, uint32_t frames_stride, uint32_t n_rows, uint32_t words_per_row, uint32_t mode)
@@ -24,7 +18,7 @@ static int check_span(const sr_engine *h, uint32_t frames_stride, uint32_t n_row
     if (mode != SR_SPAN_ACC && mode != SR_SPAN_DIS) return fail(SR_ERR_BAD_ARG, "mode must be SR_SPAN_ACC or SR_SPAN_DIS");
     if ((uint64_t)n_rows * words_per_row > kSpanMaxSpans) return fail(SR_ERR_BAD_ARG, "too many spans");
     if (h->K > kChainMaxSlots) return fail(SR_ERR_BAD_ARG, "the span scorer takes a store of at most 65536 slots");
-    if (h->tpl_rows - 1 > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the span scorer's LDS image");
+    if (store_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the span scorer's LDS image");
     return SR_OK;
 }
 
@@ -44,21 +38,9 @@ static void launch_span_stage(const sr_engine *h, const int16_t *d_mfcc, const u
     // testing build: few groups per launch put slice seams into small test shapes
     const int64_t groups = dev_hook(kHookSpanGroups);
     launch_span(SpanArgs{d_mfcc, d_frames, frames_stride, h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K, h->tpl_stride,
-                         h->tpl_rows - 1, d_words, words_per_row, n_rows * words_per_row, mode,
+                         store_tpl_len(h), d_words, words_per_row, n_rows * words_per_row, mode,
                          groups > 0 ? (uint32_t)std::min<int64_t>(groups, 65535) : 65535u, d_scores},
                 s);
-}
-
-// the dense frame counts and the feature records of a host-buffer call, into s_u32a and s_mfcc
-static int stage_rows(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frames, uint32_t frames_stride, uint32_t n_rows)
-{
-    int rc;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows))) || (rc = h->s_u32a.reserve(n_rows))) return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
-    return SR_OK;
 }
 
 extern "C" {
@@ -141,19 +123,16 @@ int sr_decode_words_alts(sr_engine *h, const int16_t *mfcc, const uint32_t *in_f
     if (rc || (rc = check_alts(h, n_rows, max_words, rec, words, level_cost, n_best, mode, alts, n_matched, span_scores)) || !n_rows) return rc;
     ENTER_HOST_CALL(h);
     const size_t n_w = (size_t)n_rows * max_words;
-    TmpDevBuf<sr_chain_rec> d_rec;
-    TmpDevBuf<sr_chain_word> d_words;
-    TmpDevBuf<uint32_t> d_lc, d_nm;
+    HostOutputs o(n_rows, max_words, rec, words, level_cost);  // the decoder's three; the alternatives' own copies beside them
+    TmpDevBuf<uint32_t> d_nm;
     TmpDevBuf<sr_nbest_entry> d_alts;
-    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows)) || (rc = d_rec.reserve(n_rows)) || (rc = d_words.reserve(n_w)) ||
-        (level_cost && (rc = d_lc.reserve(n_w))) || (rc = d_alts.reserve(n_w * n_best)) || (n_matched && (rc = d_nm.reserve(n_w))))
+    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows)) || (rc = o.reserve()) || (rc = d_alts.reserve(n_w * n_best)) ||
+        (n_matched && (rc = d_nm.reserve(n_w))))
         return rc;
-    if ((rc = sr_decode_words_alts_dev(h, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, d_rec.p, d_words.p,
-                                       level_cost ? d_lc.p : nullptr, n_best, mode, d_alts.p, n_matched ? d_nm.p : nullptr, nullptr, nullptr)))
+    if ((rc = sr_decode_words_alts_dev(h, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, max_words, n_words_exact, skip_cost, word_cost, o.rec.p, o.words.p,
+                                       o.lc.p, n_best, mode, d_alts.p, n_matched ? d_nm.p : nullptr, nullptr, nullptr)) ||
+        (rc = o.down()))
         return rc;
-    COPY_DOWN(rec, d_rec.p, (size_t)n_rows * sizeof *rec);
-    COPY_DOWN(words, d_words.p, n_w * sizeof *words);
-    if (level_cost) COPY_DOWN(level_cost, d_lc.p, n_w * 4);
     COPY_DOWN(alts, d_alts.p, n_w * n_best * sizeof *alts);
     if (n_matched) COPY_DOWN(n_matched, d_nm.p, n_w * 4);
     if (span_scores) COPY_DOWN(span_scores, h->s_span_scores.p, n_w * h->K * 4);  // the scratch the device form left them in

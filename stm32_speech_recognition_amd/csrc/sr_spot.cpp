@@ -1,14 +1,12 @@
 // Word spotting (include/sr_engine.h, "word spotting"): subsequence DTW of the templates inside long feature rows.  One
 // launch of k_spot per call, plus k_spot_finish when a window is longer than a kernel chunk; the partial records of such a
-// call live in the engine's scratch.  The whole-path host form is in sr_host.cpp, next to sr_mfcc_batch_status.
-#include "sr_host_call.h"
+// call live in the engine's scratch.  The host form stages its rows through sr_stage_host.h; the whole-path host form is in
+// sr_host.cpp, next to sr_mfcc_batch_status.
+#include "sr_stage_host.h"
 
 using namespace sr;
 
 static constexpr uint32_t kSpotMaxWindows = 65535u * 256u;  // n_rows * n_win of one call, as the rows of a rescoring
-
-// the longest template of the store: upload_templates keeps one row of slack behind it
-static inline uint32_t spot_tpl_len(const sr_engine *h) { return h->tpl_rows - 1; }
 
 static uint32_t spot_forced_cols()
 {
@@ -20,8 +18,8 @@ int check_spot(const sr_engine *h, uint32_t n_rows, uint32_t win_frames, SpotGeo
 {
     if (h->nc != (uint32_t)kCoef) return fail(SR_ERR_BAD_CONFIG, "the word spotter is built for 12-coefficient records");
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
-    if (spot_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the word spotter's LDS image");
-    *g = spot_geom(spot_tpl_len(h), h->cfg.max_frames, win_frames, spot_forced_cols());
+    if (store_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the word spotter's LDS image");
+    *g = spot_geom(store_tpl_len(h), h->cfg.max_frames, win_frames, spot_forced_cols());
     if ((uint64_t)n_rows * g->n_win > kSpotMaxWindows) return fail(SR_ERR_BAD_ARG, "too many windows (n_rows * n_win)");
     return SR_OK;
 }
@@ -33,7 +31,7 @@ int launch_spot_stage(sr_engine *h, const int16_t *d_mfcc, const uint32_t *d_fra
     if (g.split)
         if (int rc = h->s_spot_part.reserve((size_t)n_rows * g.n_chunks * h->K)) return rc;
     launch_spot(SpotArgs{d_mfcc, d_frames, frames_stride, n_rows, h->cfg.max_frames, h->tpl.p, h->tpl_frames.p, h->tpl_valid.p, h->K,
-                         h->tpl_stride, spot_tpl_len(h), g.n_win, g.win, g.chunk_cols, g.n_chunks, g.split, g.per, d_hits, d_scores,
+                         h->tpl_stride, store_tpl_len(h), g.n_win, g.win, g.chunk_cols, g.n_chunks, g.split, g.per, d_hits, d_scores,
                          g.split ? h->s_spot_part.p : nullptr},
                 s);
     HIP_TRY(hipGetLastError());
@@ -84,14 +82,9 @@ int sr_spot_dp_batch(sr_engine *h, const int16_t *mfcc, const uint32_t *in_frame
     if (rc || !n_rows) return rc;
     ENTER_HOST_CALL(h);
     const size_t n_rec = (size_t)n_rows * g.n_win * h->K;
-    if ((rc = h->s_mfcc.reserve(h->mfcc_elems(n_rows)))) return rc;
-    if ((rc = h->s_u32a.reserve(n_rows))) return rc;
+    if ((rc = stage_rows(h, mfcc, in_frames, frames_stride, n_rows))) return rc;
     if ((rc = h->s_spot_hits.reserve(n_rec))) return rc;
     if (scores && (rc = h->s_spot_scores.reserve(n_rec))) return rc;
-    std::vector<uint32_t> frames(n_rows);  // the counts go up dense, whatever records they came in
-    for (uint32_t r = 0; r < n_rows; r++) frames[r] = in_frames[(size_t)r * frames_stride];
-    COPY_UP(h->s_mfcc.p, mfcc, h->mfcc_elems(n_rows) * 2);
-    COPY_UP(h->s_u32a.p, frames.data(), (size_t)n_rows * 4);
     if ((rc = launch_spot_stage(h, h->s_mfcc.p, h->s_u32a.p, 1, n_rows, g, h->s_spot_hits.p, scores ? h->s_spot_scores.p : nullptr, nullptr)))
         return rc;
     COPY_DOWN(hits, h->s_spot_hits.p, n_rec * sizeof(sr_spot_hit));

@@ -25,7 +25,7 @@ int check_store(const sr_engine *h)
 {
     if (h->nc != (uint32_t)kCoef) return fail(SR_ERR_BAD_CONFIG, "the word spotter is built for 12-coefficient records");
     if (!h->K) return fail(SR_ERR_NO_TEMPLATES, "no templates set");
-    if (h->tpl_rows - 1 > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the word spotter's LDS image");
+    if (store_tpl_len(h) > spot_max_tpl(h->lds)) return fail(SR_ERR_BAD_ARG, "templates too long for the word spotter's LDS image");
     return SR_OK;
 }
 
@@ -33,10 +33,10 @@ int check_store(const sr_engine *h)
 int relayout(sr_spot_live *l)
 {
     const sr_engine *h = l->h;
-    const uint64_t per = spot_live_state_bytes(h->K, h->tpl_rows - 1);
+    const uint64_t per = spot_live_state_bytes(h->K, store_tpl_len(h));
     if (int rc = l->state.reserve((size_t)(per * l->C))) return rc;
     l->K = h->K;
-    l->tpl_len = h->tpl_rows - 1;
+    l->tpl_len = store_tpl_len(h);
     l->chan_stride = per;
     l->layout_serial = h->store_serial;
     return SR_OK;

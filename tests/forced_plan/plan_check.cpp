@@ -140,6 +140,18 @@ int main()
         CHECK(forced_overlap(buf, 16, buf + 15, 4) && !forced_overlap(buf, 16, buf + 16, 4) && !forced_overlap(buf, 0, buf, 4) &&
               !forced_overlap(nullptr, 16, buf, 4));
     }
+    // the one overlap test of every stage's buffer checks (csrc/sr_overlap.h)
+    {
+        char buf[64];
+        CHECK(!overlap(nullptr, 8, nullptr, 8) && !overlap(buf, 8, nullptr, 8) && !overlap(nullptr, 8, buf, 8));  // null: never
+        CHECK(!overlap(buf, 0, buf, 8) && !overlap(buf, 8, buf, 0) && !overlap(buf + 4, 0, buf, 8) && !overlap(buf, 0, buf, 0));  // empty: never
+        CHECK(!overlap(buf, 8, buf + 8, 8) && !overlap(buf + 8, 8, buf, 8));  // touching ranges share no byte ...
+        CHECK(overlap(buf, 9, buf + 8, 8) && overlap(buf + 8, 8, buf, 9));    // ... one byte more and they do, either way round
+        CHECK(overlap(buf, 8, buf, 8) && overlap(buf, 1, buf, 1));            // the same range
+        CHECK(overlap(buf, 32, buf + 8, 4) && overlap(buf + 8, 4, buf, 32));  // nested, either way round
+        CHECK(overlap(buf, 32, buf + 31, 1) && overlap(buf, 32, buf, 1) && !overlap(buf, 32, buf + 32, 1));  // the first and last byte; one past
+        CHECK(!overlap(buf, 4, buf + 40, 4) && !overlap(buf + 40, 4, buf, 4));  // far apart
+    }
     // the gather's table
     {
         std::vector<uint32_t> src;
